@@ -27,6 +27,10 @@ compares the gathered frame BIT FOR BIT with the same frame rendered by itself a
 multi-GPU node is a parity test of the sharded path as well.  `dist` in the line records what the process group was:
 world size, backend, RCCL version, the device of every rank.
 
+`--dump-outputs DIR` writes what the last timed step delivered on rank 0, the (rgb, depth) image, as DIR/rgb.npy (H, W, 3) and
+DIR/depth.npy (H, W) in float32; scene, weights and the frame seeds are fixed, so two builds run with the same arguments can be
+compared output for output.
+
 The JSON line also carries
   roofline      the dominant kernel (per-view MLP part, ~86 % of the time): executed MFMA FLOP / HIP-event duration
                 measured in this run, against the dense MFMA peak of the dtype the products are issued in
@@ -107,6 +111,10 @@ def parse(argv=None):
     ap.add_argument("--no-power", action="store_true", help="do not sample rocm-smi (power / sclk) during the timed region")
     ap.add_argument("--precision", choices=["f16x3", "fp32", "f16"], default=None,
                     help="MLP GEMM arithmetic of the headline number (default: the library default, f16x3)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last timed step returned on rank 0 -- the frame's colours and depths -- "
+                         "as DIR/rgb.npy and DIR/depth.npy (float32); the inputs are seeded, so runs with the same arguments compare "
+                         "output for output")
     return ap.parse_args(argv)
 
 
@@ -377,6 +385,19 @@ def train_entry(torch, ops, dev, msd, make_scene, build_modules, n_steps, SB=4, 
                     "reference's), frac against the dense fp16 peak"}
 
 
+def dump_outputs(path, tile, W, H):
+    """--dump-outputs: the (rays, 4) tile of the last timed step (rgb, depth per ray) -> path/rgb.npy (H, W, 3), path/depth.npy (H, W);
+    a tile that is not a whole frame (--emulate-shard, --weak on rank 0's own range) keeps its ray axis: (rays, 3), (rays,)."""
+    import numpy as np
+    a = tile.detach().float().cpu().numpy()
+    rgb, depth = a[:, :3], a[:, 3]
+    if a.shape[0] == W * H:
+        rgb, depth = rgb.reshape(H, W, 3), depth.reshape(H, W)
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "rgb.npy"), np.ascontiguousarray(rgb, dtype=np.float32))
+    np.save(os.path.join(path, "depth.npy"), np.ascontiguousarray(depth, dtype=np.float32))
+
+
 def main():
     args = parse()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ and not os.environ.get(CHILD_ENV):
@@ -634,6 +655,8 @@ def main():
         elapsed, prof = timed(args.steps, head, args.warmup, profile=True)
     head_fallbacks = wl_head["mlp"].fallback_launches(reset=True)
     wl_head["record_phases"] = False
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, frame[0] if frame[0] is not None else out, W, H)
     if not os.environ.get("DINER_AMD_LIB"):        # (timing experiments with ablated libraries produce garbage)
         if out is not None:
             assert torch.isfinite(out).all(), "non-finite render output"

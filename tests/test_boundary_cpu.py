@@ -4,6 +4,7 @@ fail loudly (no fallback) off the HIP device or in grad mode."""
 import os
 import re
 
+import numpy as np
 import pytest
 import torch
 
@@ -121,17 +122,17 @@ def test_state_dict_contract():
 
 
 def test_state_dict_matches_imported_reference():
-    from oracle.ref_import import reference_available, import_reference, build_reference_nerf
-    if not reference_available():
-        pytest.skip("reference tree only exists in the build container")
-    ref = build_reference_nerf(import_reference()).state_dict()
+    """Against the imported reference's state dict, stored by oracle/make_golden_state_dict.py (G21): every entry outside the
+    ResNet trunk (a torchvision stub in the reference import) with its shape, and the positional-encoding buffers' values."""
+    ref = np.load(os.path.join(ROOT, "tests", "golden", "g21_reference_state_dict.npz"), allow_pickle=False)
+    shapes = {k[len("shape:"):]: tuple(int(x) for x in ref[k]) for k in ref.files if k.startswith("shape:")}
+    values = {k[len("value:"):]: torch.from_numpy(ref[k]) for k in ref.files if k.startswith("value:")}
+    assert len(shapes) == 36 and set(values) == {"poscode._freqs", "poscode._phases", "depthcode._freqs"}
     mine = build_nerf().state_dict()
-    for k, v in ref.items():
-        if k.startswith("encoder.model."):
-            continue                       # the reference's trunk is a torchvision stub in this container
-        assert k in mine and tuple(mine[k].shape) == tuple(v.shape), k
-    for k in ("poscode._freqs", "poscode._phases", "depthcode._freqs"):
-        assert torch.equal(mine[k], ref[k])
+    for k, shape in shapes.items():
+        assert k in mine and tuple(mine[k].shape) == shape, k
+    for k, v in values.items():
+        assert torch.equal(mine[k], v)
 
 
 def test_renderer_contract_and_no_fallback():

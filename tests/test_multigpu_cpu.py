@@ -46,7 +46,7 @@ def _worker(rank, world, port, W, H, q):
         geo = depth[:, :1] - 0.242 - pos                         # what the fake renderer computes from the rays alone
         off = depth_b[:, :1] - pos - geo
         assert float(off.max() - off.min()) < 1e-4, "the two ranks rendered their shards with different frame seeds"
-        q.put((rgb, depth))
+        q.put((rgb.numpy(), depth.numpy()))       # by value: a tensor goes as a file descriptor the exiting worker may close first
     else:
         assert rgb is None and depth is None
     dist.barrier()
@@ -67,7 +67,7 @@ def test_sharded_render_equals_single_process():
     procs = [ctx.Process(target=_worker, args=(r, 2, port, W, H, q)) for r in range(2)]
     for p in procs:
         p.start()
-    rgb2, d2 = q.get(timeout=120)
+    rgb2, d2 = (torch.from_numpy(a) for a in q.get(timeout=120))
     for p in procs:
         p.join(timeout=120)
         assert p.exitcode == 0
