@@ -4,8 +4,10 @@
 
 namespace diner {
 
-constexpr int kCompMaxPerLane = 4;   // K <= 256
+constexpr int kCompMaxPerLane = 4;       // K <= 256: the bounded entry
+constexpr int kCompLongPerLane = 16;     // K <= 1024: the long entry above 256 samples
 
+template <int kPerLane>
 __global__ __launch_bounds__(256) void k_composite(const float4* __restrict__ field, const float* __restrict__ z,
                                                    const float* __restrict__ rays, int NR, int K, int per_lane,
                                                    int white_bkgd, float* __restrict__ rgb_out,
@@ -17,11 +19,11 @@ __global__ __launch_bounds__(256) void k_composite(const float4* __restrict__ fi
   const float* zr = z + (size_t)ray * K;
   const float4* fr = field + (size_t)ray * K;
 
-  float alpha[kCompMaxPerLane], zz[kCompMaxPerLane];
-  float4 f[kCompMaxPerLane];
+  float alpha[kPerLane], zz[kPerLane];
+  float4 f[kPerLane];
   float prod = 1.0f;
 #pragma unroll
-  for (int j = 0; j < kCompMaxPerLane; ++j) {
+  for (int j = 0; j < kPerLane; ++j) {
     const int k = lane * per_lane + j;
     alpha[j] = 0.0f; zz[j] = 0.0f; f[j] = make_float4(0.f, 0.f, 0.f, 0.f);
     if (j < per_lane && k < K) {
@@ -44,7 +46,7 @@ __global__ __launch_bounds__(256) void k_composite(const float4* __restrict__ fi
   if (lane == 0) T = 1.0f;
   float r = 0.f, g = 0.f, b = 0.f, d = 0.f, wsum = 0.f;
 #pragma unroll
-  for (int j = 0; j < kCompMaxPerLane; ++j) {
+  for (int j = 0; j < kPerLane; ++j) {
     const int k = lane * per_lane + j;
     if (j < per_lane && k < K) {
       const float w = __fmul_rn(alpha[j], T);                                // :351
@@ -79,8 +81,24 @@ extern "C" int diner_composite_f32(const float* field, const float* z, const flo
   DINER_CHECK_ARG(NR > 0 && K > 0 && K <= kWave * kCompMaxPerLane, "composite: bad sizes NR=%d K=%d (K <= %d)", NR, K,
                   kWave * kCompMaxPerLane);
   const int per_lane = (K + kWave - 1) / kWave;
-  hipLaunchKernelGGL(k_composite, dim3((NR + 3) / 4), dim3(256), 0, (hipStream_t)stream, (const float4*)field, z, rays,
+  hipLaunchKernelGGL(k_composite<kCompMaxPerLane>, dim3((NR + 3) / 4), dim3(256), 0, (hipStream_t)stream, (const float4*)field, z, rays,
                      NR, K, per_lane, white_bkgd, rgb_out, depth_out, weights_out);
+  DINER_LAUNCH_OK();
+  return 0;
+}
+
+// long entry: today's instance wherever it fits (K <= 256), 16 samples per lane above
+extern "C" int diner_composite_long_f32(const float* field, const float* z, const float* rays, int NR, int K,
+                                        int white_bkgd, float* rgb_out, float* depth_out, float* weights_out,
+                                        void* stream) {
+  DINER_CHECK_ARG(field && z && rays && rgb_out && depth_out, "composite_long: null pointer argument");
+  DINER_CHECK_ARG(NR > 0 && K > 0 && K <= kWave * kCompLongPerLane, "composite_long: bad sizes NR=%d K=%d (K <= %d)", NR, K,
+                  kWave * kCompLongPerLane);
+  if (K <= kWave * kCompMaxPerLane)
+    return diner_composite_f32(field, z, rays, NR, K, white_bkgd, rgb_out, depth_out, weights_out, stream);
+  const int per_lane = (K + kWave - 1) / kWave;
+  hipLaunchKernelGGL(k_composite<kCompLongPerLane>, dim3((NR + 3) / 4), dim3(256), 0, (hipStream_t)stream,
+                     (const float4*)field, z, rays, NR, K, per_lane, white_bkgd, rgb_out, depth_out, weights_out);
   DINER_LAUNCH_OK();
   return 0;
 }

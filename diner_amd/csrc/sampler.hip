@@ -78,11 +78,43 @@ __device__ __forceinline__ float view_likelihood(const SceneDev& sc, int v, floa
   return (L == L) ? L : 0.0f;
 }
 
-// in-LDS bitonic sort (ascending) of n2 (power of two <= 256) floats by one wave; block-uniform control flow
+// ---- the wide kernels: one workgroup of kWideThreads per ray (n_cand <= 4096, K <= 1024) --------------
+constexpr int kWideThreads = 256;
+constexpr int kWideWaves = kWideThreads / kWave;             // 4
+constexpr int kWideMaxCand = kWideThreads * kCandPerLane;    // 4096: candidate i at thread i / 16, slot i % 16
+constexpr int kLongMaxK = 1024;
+
+// per-wave partials of the workgroup reductions, double-buffered: a reduction writes buffer `par`, waits at one barrier
+// and reads it; the next one uses the other buffer, so the reads of this one are done before the buffer is written again
+struct WgRed {
+  float f[2][kWideWaves];
+  int i[2][kWideWaves];
+};
+
+__device__ __forceinline__ float wg_sum(float v, float (*buf)[kWideWaves], int& par, int tid) {
+  v = wave_sum(v);
+  if ((tid & (kWave - 1)) == 0) buf[par][tid >> 6] = v;
+  __syncthreads();
+  const float s = ((buf[par][0] + buf[par][1]) + buf[par][2]) + buf[par][3];
+  par ^= 1;
+  return s;
+}
+__device__ __forceinline__ int wg_sum_i(int v, int (*buf)[kWideWaves], int& par, int tid) {
+  v = wave_sum_i(v);
+  if ((tid & (kWave - 1)) == 0) buf[par][tid >> 6] = v;
+  __syncthreads();
+  const int s = buf[par][0] + buf[par][1] + buf[par][2] + buf[par][3];
+  par ^= 1;
+  return s;
+}
+
+// in-LDS bitonic sort (ascending) of n2 (power of two) floats by kThreads threads (one wave: n2 <= 256, one
+// workgroup of the wide kernels: n2 <= 1024); every thread of the block calls it (block-uniform control flow)
+template <int kThreads = kWave>
 __device__ __forceinline__ void bitonic_sort(float* s, int n2, int lane) {
   for (int k = 2; k <= n2; k <<= 1) {
     for (int j = k >> 1; j > 0; j >>= 1) {
-      for (int t = lane; t < n2 / 2; t += kWave) {
+      for (int t = lane; t < n2 / 2; t += kThreads) {
         const int lo = ((t / j) * 2 * j) + (t % j);
         const int hi = lo + j;
         const bool up = ((lo & k) == 0);
@@ -94,16 +126,19 @@ __device__ __forceinline__ void bitonic_sort(float* s, int n2, int lane) {
   }
 }
 
-// fill_up_uniform_samples on a K-slot LDS row (nerf_renderer.py:367-397); row padded with +inf to n2
+// fill_up_uniform_samples on a K-slot LDS row (nerf_renderer.py:367-397); row padded with +inf to n2.
+// kThreads == kWave: one wave per row; kThreads == kWideThreads: one workgroup per row, `red` holds the count's partials.
+template <int kThreads = kWave>
 __device__ __forceinline__ void fill_and_sort(float* s, int K, int n2, float near, float far, const float* noise_row,
-                                              uint64_t seed, int ray, int lane) {
-  bitonic_sort(s, n2, lane);                                                 // :377
+                                              uint64_t seed, int ray, int lane, WgRed* red = nullptr, int par = 0) {
+  bitonic_sort<kThreads>(s, n2, lane);                                       // :377
   int m = 0;
-  for (int j = lane; j < K; j += kWave) m += (s[j] == 0.0f);
-  m = wave_sum_i(m);                                                          // :382
+  for (int j = lane; j < K; j += kThreads) m += (s[j] == 0.0f);
+  if constexpr (kThreads == kWave) m = wave_sum_i(m);                        // :382
+  else m = wg_sum_i(m, red->i, par, lane);
   if (m > 0) {
     const float step = __fdiv_rn(__fsub_rn(far, near), (float)m);             // :388
-    for (int j = lane; j < K; j += kWave) {
+    for (int j = lane; j < K; j += kThreads) {
       if (s[j] == 0.0f) {
         const float u = noise_row ? noise_row[j] : rng_uniform(seed, 2u, (uint32_t)ray, (uint32_t)j);      // (`ray` here: the noise key of the ray)
         float z = __fadd_rn(near, __fmul_rn((float)j, step));                 // :389
@@ -113,7 +148,7 @@ __device__ __forceinline__ void fill_and_sort(float* s, int K, int n2, float nea
     }
   }
   __syncthreads();
-  bitonic_sort(s, n2, lane);                                                 // :396
+  bitonic_sort<kThreads>(s, n2, lane);                                       // :396
 }
 
 __global__ __launch_bounds__(kRaysPerBlock* kWave) void k_sample_depthguided(SceneDev sc, SamplerArgs a) {
@@ -294,6 +329,198 @@ __global__ __launch_bounds__(kRaysPerBlock* kWave) void k_fill_uniform(const flo
     for (int j = lane; j < K; j += kWave) z_out[(size_t)ray * K + j] = S[j];
 }
 
+// Wide sampler: the per-thread structure of k_sample_depthguided (16 candidates per thread, same arithmetic per candidate)
+// with the workgroup as the ray, so n_cand <= 256 x 16 = 4096 and K <= 1024.  The transmittance product, the sums of the
+// gaussian fit, the radix-select counts and the compaction offsets are wave scans / sums plus a 4-entry LDS carry.  The
+// likelihood bits are view_likelihood's, the pick rule (all candidates above the threshold T, ties at T in index order)
+// and the noise keys are the bounded kernel's: a ray's picks and draws do not depend on which kernel ran.
+// LDS: 2 x 16 KB candidate rows + 4 KB slot row + the reduction carries (~36 KB, 4 workgroups per CU).
+__global__ __launch_bounds__(kWideThreads) void k_sample_depthguided_wide(SceneDev sc, SamplerArgs a) {
+  __shared__ float L[kWideMaxCand];
+  __shared__ float Z[kWideMaxCand];
+  __shared__ float S[kLongMaxK];
+  __shared__ WgRed red;
+  __shared__ float wprod[kWideWaves];
+  __shared__ int wscan[2][kWideWaves];
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int ray = blockIdx.x;                       // grid == NR: every workgroup has a ray
+  int par = 0;
+
+  const float* r = a.rays + (size_t)ray * 8;
+  const float ox = r[0], oy = r[1], oz = r[2], dx = r[3], dy = r[4], dz = r[5], near = r[6], far = r[7];
+  const int n_cand = a.n_cand;
+  const float step_size = __fdiv_rn(__fsub_rn(far, near), (float)n_cand);       // nerf_renderer.py:95
+  const float jitter = (float)(1.0 / (double)n_cand);                           // :53, applied in fp32 at :57
+
+  float dcam[kMaxViews][3];
+#pragma unroll
+  for (int v = 0; v < kMaxViews; ++v) {                                         // :102-103
+    dcam[v][0] = rot_row(sc.R[v] + 0, dx, dy, dz);
+    dcam[v][1] = rot_row(sc.R[v] + 3, dx, dy, dz);
+    dcam[v][2] = rot_row(sc.R[v] + 6, dx, dy, dz);
+  }
+
+  // ---- candidates: thread owns i = tid + 256 c (coalesced noise reads); slots >= n_cand are zero -------
+  for (int cidx = 0; cidx < kCandPerLane; ++cidx) {
+    const int i = tid + kWideThreads * cidx;
+    float lk = 0.0f, z = 0.0f;
+    if (i < n_cand) {
+      const float un = a.noise_coarse ? a.noise_coarse[(size_t)ray * n_cand + i]
+                                      : rng_uniform(a.seed, 0u, a.ray_key0 + (uint32_t)ray, (uint32_t)i);
+      const float t = __fadd_rn(a.t_base[i], __fmul_rn(un, jitter));            // :57
+      z = __fadd_rn(__fmul_rn(near, __fsub_rn(1.0f, t)), __fmul_rn(far, t));    // :60
+      const float px = __fadd_rn(ox, __fmul_rn(z, dx));                         // :96
+      const float py = __fadd_rn(oy, __fmul_rn(z, dy));
+      const float pz = __fadd_rn(oz, __fmul_rn(z, dz));
+      for (int v = 0; v < sc.nv; ++v)
+        lk = fmaxf(lk, view_likelihood(sc, v, px, py, pz, dcam[v], step_size, a.depth_diff_max));   // :129
+    }
+    L[i] = lk;
+    Z[i] = z;
+  }
+  for (int j = tid; j < kLongMaxK; j += kWideThreads) S[j] = (j < a.K) ? 0.0f : __builtin_inff();
+  __syncthreads();
+
+  // ---- thread-contiguous view: i = 16 tid + k ---------------------------------------------------------
+  float lv[kCandPerLane], zv[kCandPerLane];
+#pragma unroll
+  for (int k = 0; k < kCandPerLane; ++k) {
+    lv[k] = L[tid * kCandPerLane + k];
+    zv[k] = Z[tid * kCandPerLane + k];
+  }
+  // exclusive transmittance product  O_i = L_i * prod_{j<i} (1 - L_j)            (:131-132)
+  float run = 1.0f;
+#pragma unroll
+  for (int k = 0; k < kCandPerLane; ++k) run *= (1.0f - lv[k]);
+  float incl = run;                          // inclusive wave scan of the per-thread products
+#pragma unroll
+  for (int o = 1; o < kWave; o <<= 1) {
+    const float up = __shfl_up(incl, o, kWave);
+    if (lane >= o) incl *= up;
+  }
+  if (lane == kWave - 1) wprod[wave] = incl;
+  float carry = __shfl_up(incl, 1, kWave);
+  if (lane == 0) carry = 1.0f;
+  __syncthreads();
+  float wcarry = 1.0f;                       // product of the earlier waves' totals
+  for (int w = 0; w < wave; ++w) wcarry *= wprod[w];
+  carry *= wcarry;
+  float ov[kCandPerLane];
+  float osum = 0.0f;
+  int any_o = 0;
+#pragma unroll
+  for (int k = 0; k < kCandPerLane; ++k) {
+    ov[k] = lv[k] * carry;
+    carry *= (1.0f - lv[k]);
+    osum += ov[k];
+    any_o |= (ov[k] != 0.0f);
+  }
+  osum = wg_sum(osum, red.f, par, tid);
+  const bool has_surface = wg_sum_i(any_o, red.i, par, tid) > 0;                 // :182
+  // weighted mean / std of the candidate depths (torch_helpers.py:215-223)
+  float mean = 0.0f, sd = 0.0f;
+  if (has_surface) {
+    float acc = 0.0f;
+#pragma unroll
+    for (int k = 0; k < kCandPerLane; ++k) acc += zv[k] * (ov[k] / osum);
+    mean = wg_sum(acc, red.f, par, tid);
+    acc = 0.0f;
+#pragma unroll
+    for (int k = 0; k < kCandPerLane; ++k) {
+      const float dlt = zv[k] - mean;
+      acc += (dlt * dlt) * (ov[k] / osum);
+    }
+    sd = sqrtf(wg_sum(acc, red.f, par, tid));
+  }
+
+  // ---- top-(K-G) by likelihood: radix select on the (non-negative) float bit patterns (:172-178) ----
+  const int K = a.K, G = a.G, want = K - G;
+  uint32_t ub[kCandPerLane];
+#pragma unroll
+  for (int k = 0; k < kCandPerLane; ++k) ub[k] = __float_as_uint(lv[k]);
+  uint32_t T = 0;
+  if (want > 0) {
+    for (int bit = 30; bit >= 0; --bit) {
+      const uint32_t trial = T | (1u << bit);
+      int cnt = 0;
+#pragma unroll
+      for (int k = 0; k < kCandPerLane; ++k) cnt += (ub[k] >= trial);
+      if (wg_sum_i(cnt, red.i, par, tid) >= want) T = trial;
+    }
+  }
+  // candidates strictly above T are all taken; ties at T (only if T > 0) fill the remainder in index order
+  int n_gt = 0, n_eq = 0;
+#pragma unroll
+  for (int k = 0; k < kCandPerLane; ++k) {
+    n_gt += (ub[k] > T);
+    n_eq += (ub[k] == T);
+  }
+  int pre_gt = n_gt, pre_eq = n_eq;          // inclusive scans over the wave's threads
+#pragma unroll
+  for (int o = 1; o < kWave; o <<= 1) {
+    const int g1 = __shfl_up(pre_gt, o, kWave), e1 = __shfl_up(pre_eq, o, kWave);
+    if (lane >= o) { pre_gt += g1; pre_eq += e1; }
+  }
+  if (lane == kWave - 1) { wscan[0][wave] = pre_gt; wscan[1][wave] = pre_eq; }
+  __syncthreads();
+  int base_gt = 0, base_eq = 0, tot_gt = 0;  // earlier waves' totals (exclusive scan over waves) and the ray's total
+  for (int w = 0; w < kWideWaves; ++w) {
+    if (w < wave) { base_gt += wscan[0][w]; base_eq += wscan[1][w]; }
+    tot_gt += wscan[0][w];
+  }
+  const int eq_take = (T > 0 && want > 0) ? max(want - tot_gt, 0) : 0;
+  int off_gt = base_gt + pre_gt - n_gt;
+  int off_eq = base_eq + pre_eq - n_eq;
+  if (want > 0) {
+#pragma unroll
+    for (int k = 0; k < kCandPerLane; ++k) {
+      if (ub[k] > T) {
+        S[off_gt++] = zv[k];
+      } else if (ub[k] == T && T > 0) {
+        if (off_eq < eq_take) S[tot_gt + off_eq] = zv[k];
+        ++off_eq;
+      }
+    }
+  }
+  // gaussian samples into the LAST G slots of every ray (zeros when the ray sees no surface)   (:181-190)
+  for (int g = tid; g < G; g += kWideThreads) {
+    float zg = 0.0f;
+    if (has_surface) {
+      const float n = a.noise_gauss ? a.noise_gauss[(size_t)ray * G + g]
+                                    : rng_normal(a.seed, 1u, a.ray_key0 + (uint32_t)ray, (uint32_t)g);
+      zg = __fadd_rn(__fmul_rn(n, sd), mean);                                    // :188
+    }
+    S[want + g] = zg;
+  }
+  __syncthreads();
+  if (a.z_unfilled)
+    for (int j = tid; j < K; j += kWideThreads) a.z_unfilled[(size_t)ray * K + j] = S[j];
+  __syncthreads();      // the four waves share S: the sort below must not swap slots another wave has yet to copy out
+
+  int n2 = 2;
+  while (n2 < K) n2 <<= 1;
+  fill_and_sort<kWideThreads>(S, K, n2, near, far, a.noise_fill ? a.noise_fill + (size_t)ray * K : nullptr, a.seed,
+                              (int)(a.ray_key0 + (uint32_t)ray), tid, &red, par);
+  for (int j = tid; j < K; j += kWideThreads) a.z_out[(size_t)ray * K + j] = S[j];
+}
+
+// fill_up_uniform_samples alone on rows of up to 1024 slots: one workgroup per ray, the wide kernel's sort
+__global__ __launch_bounds__(kWideThreads) void k_fill_uniform_wide(const float* z_in, const float* rays, int K,
+                                                                   const float* noise_fill, uint64_t seed,
+                                                                   uint32_t ray_key0, float* z_out) {
+  __shared__ float S[kLongMaxK];
+  __shared__ WgRed red;
+  const int tid = threadIdx.x, ray = blockIdx.x;
+  for (int j = tid; j < kLongMaxK; j += kWideThreads) S[j] = (j < K) ? z_in[(size_t)ray * K + j] : __builtin_inff();
+  __syncthreads();
+  int n2 = 2;
+  while (n2 < K) n2 <<= 1;
+  fill_and_sort<kWideThreads>(S, K, n2, rays[(size_t)ray * 8 + 6], rays[(size_t)ray * 8 + 7],
+                              noise_fill ? noise_fill + (size_t)ray * K : nullptr, seed, (int)(ray_key0 + (uint32_t)ray), tid,
+                              &red);
+  for (int j = tid; j < K; j += kWideThreads) z_out[(size_t)ray * K + j] = S[j];
+}
+
 }  // namespace diner
 
 using namespace diner;
@@ -332,6 +559,50 @@ extern "C" int diner_fill_uniform_f32(const float* z_in, const float* rays, int 
   const int blocks = (NR + kRaysPerBlock - 1) / kRaysPerBlock;
   hipLaunchKernelGGL(k_fill_uniform, dim3(blocks), dim3(kRaysPerBlock * kWave), 0, (hipStream_t)stream, z_in, rays, NR,
                      K, noise_fill, seed, (uint32_t)ray_index0, z_out);
+  DINER_LAUNCH_OK();
+  return 0;
+}
+
+// ---- long entries: the whole range, the kernel picked from the sizes.  Where the bounded kernels fit (K <= 256,
+// n_cand <= 1024) they run with the same arguments, so results there are bit-identical to the bounded entries.
+extern "C" int diner_sample_depthguided_long_f32(const DinerScene* scene, const float* rays, int NR, int n_cand, int K,
+                                                 int G, float depth_diff_max, const float* t_base,
+                                                 const float* noise_coarse, const float* noise_gauss,
+                                                 const float* noise_fill, uint64_t seed, long long ray_index0,
+                                                 float* z_out, float* z_unfilled, void* stream) {
+  DINER_CHECK_ARG(scene && rays && t_base && z_out, "sample_depthguided_long: null pointer argument");
+  DINER_CHECK_ARG(NR > 0, "sample_depthguided_long: NR must be positive (got %d)", NR);
+  DINER_CHECK_ARG(n_cand > 0 && n_cand <= kWideMaxCand, "sample_depthguided_long: n_cand=%d outside [1,%d]", n_cand,
+                  kWideMaxCand);
+  DINER_CHECK_ARG(K > 0 && K <= kLongMaxK, "sample_depthguided_long: n_samples K=%d outside [1,%d]", K, kLongMaxK);
+  DINER_CHECK_ARG(G >= 0 && G <= K, "sample_depthguided_long: need 0 <= n_gaussian <= n_samples (got G=%d, K=%d)", G, K);
+  DINER_CHECK_ARG(ray_index0 >= 0 && ray_index0 + NR <= (1ll << 32),
+                  "sample_depthguided_long: ray_index0 = %lld outside [0, 2^32 - NR] (the noise key of a ray is a 32-bit index)",
+                  ray_index0);
+  if (K <= kMaxK && n_cand <= kMaxCand)
+    return diner_sample_depthguided_f32(scene, rays, NR, n_cand, K, G, depth_diff_max, t_base, noise_coarse, noise_gauss,
+                                        noise_fill, seed, ray_index0, z_out, z_unfilled, stream);
+  SceneDev sd;
+  int rc = make_scene_dev(scene, &sd);
+  if (rc) return rc;
+  DINER_CHECK_ARG(scene->depth && scene->depth_std && scene->normals && scene->std_pad_scale,
+                  "sample_depthguided_long: scene depth/std/normal maps missing");
+  SamplerArgs a{rays, t_base, noise_coarse, noise_gauss, noise_fill, z_out, z_unfilled, seed, (uint32_t)ray_index0, NR, n_cand, K,
+                G, depth_diff_max};
+  hipLaunchKernelGGL(k_sample_depthguided_wide, dim3(NR), dim3(kWideThreads), 0, (hipStream_t)stream, sd, a);
+  DINER_LAUNCH_OK();
+  return 0;
+}
+
+extern "C" int diner_fill_uniform_long_f32(const float* z_in, const float* rays, int NR, int K, const float* noise_fill,
+                                           uint64_t seed, long long ray_index0, float* z_out, void* stream) {
+  DINER_CHECK_ARG(z_in && rays && z_out, "fill_uniform_long: null pointer argument");
+  DINER_CHECK_ARG(NR > 0 && K > 0 && K <= kLongMaxK, "fill_uniform_long: bad sizes NR=%d K=%d (K <= %d)", NR, K, kLongMaxK);
+  DINER_CHECK_ARG(ray_index0 >= 0 && ray_index0 + NR <= (1ll << 32),
+                  "fill_uniform_long: ray_index0 = %lld outside [0, 2^32 - NR] (the noise key of a ray is a 32-bit index)", ray_index0);
+  if (K <= kMaxK) return diner_fill_uniform_f32(z_in, rays, NR, K, noise_fill, seed, ray_index0, z_out, stream);
+  hipLaunchKernelGGL(k_fill_uniform_wide, dim3(NR), dim3(kWideThreads), 0, (hipStream_t)stream, z_in, rays, K, noise_fill,
+                     seed, (uint32_t)ray_index0, z_out);
   DINER_LAUNCH_OK();
   return 0;
 }

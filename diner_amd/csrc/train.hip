@@ -1189,9 +1189,9 @@ __global__ __launch_bounds__(256) void k_lin_out_bwd(const float* __restrict__ x
 // Adjoint of the compositing arithmetic (nerf_renderer.py:299-301, :341-360) with respect to the field values:
 //   delta_k = z_{k+1} - z_k (last: far - z_K); s_k = relu(sigma_k); a_k = 1 - exp(-delta_k s_k); t_k = 1 - a_k + 1e-10;
 //   T_k = prod_{j<k} t_j; w_k = a_k T_k; rgb = sum w c (+ 1 - sum w); depth = sum w z.
-// One thread per ray (K <= 256): G_k = g_rgb.c_k + g_depth z_k - [white] sum(g_rgb); dL/da_k = G_k T_k - S_k / t_k with
+// One thread per ray (K <= 1024; no per-K storage beyond d_field itself): G_k = g_rgb.c_k + g_depth z_k - [white] sum(g_rgb); dL/da_k = G_k T_k - S_k / t_k with
 // S_k = sum_{m>k} G_m w_m; dL/dsigma_k = dL/da_k * delta_k (1 - a_k) * [sigma_k > 0]; dL/dc_k = w_k g_rgb.
-constexpr int kCompBwdMaxK = 256;
+constexpr int kCompBwdMaxK = 1024;
 __global__ void k_composite_bwd(const float* __restrict__ field, const float* __restrict__ z, const float* __restrict__ rays,
                                 int NR, int K, int white, const float* __restrict__ g_rgb, const float* __restrict__ g_depth,
                                 float* __restrict__ d_field) {

@@ -373,7 +373,22 @@ def sample_depthguided(scene: HipScene, rays, n_samples, n_candidates, n_gaussia
                        noise=None, seed=0, want_unfilled=False, ray_index0=0):
     """rays (NR,8) -> ascending z (NR,K) [, unfilled z with zeros].  noise = (coarse, gauss, fill) or None
     (in-kernel Philox keyed by (`seed`, ray_index0 + i): pass the index of rays[0] in the frame's ray list and one seed per
-    frame, and the frame does not depend on how its rays are batched or sharded)."""
+    frame, and the frame does not depend on how its rays are batched or sharded).  The bounded entry: K <= 256,
+    n_candidates <= 1024 (sample_depthguided_long: K <= 1024, n_candidates <= 4096)."""
+    return _sample_depthguided(lib.diner_sample_depthguided_f32, scene, rays, n_samples, n_candidates, n_gaussian,
+                               depth_diff_max, noise, seed, want_unfilled, ray_index0)
+
+
+def sample_depthguided_long(scene: HipScene, rays, n_samples, n_candidates, n_gaussian, depth_diff_max=0.05,
+                            noise=None, seed=0, want_unfilled=False, ray_index0=0):
+    """sample_depthguided for K <= 1024 samples and n_candidates <= 4096 (the reference's --nsamples): the same kernel as
+    sample_depthguided where it fits (K <= 256, n_candidates <= 1024, bit-identical results), one workgroup per ray above."""
+    return _sample_depthguided(lib.diner_sample_depthguided_long_f32, scene, rays, n_samples, n_candidates, n_gaussian,
+                               depth_diff_max, noise, seed, want_unfilled, ray_index0)
+
+
+def _sample_depthguided(entry, scene, rays, n_samples, n_candidates, n_gaussian, depth_diff_max, noise, seed, want_unfilled,
+                        ray_index0):
     _require_hip(rays)
     rays = _f32c(rays)
     NR = rays.shape[0]
@@ -390,7 +405,7 @@ def sample_depthguided(scene: HipScene, rays, n_samples, n_candidates, n_gaussia
         assert ng is None or tuple(ng.shape) == (NR, G)
         assert nf is None or tuple(nf.shape) == (NR, K)
     with torch.cuda.device(rays.device):
-        _lib.check(lib.diner_sample_depthguided_f32(
+        _lib.check(entry(
             scene.ref, _ptr(rays), NR, int(n_candidates), K, G, float(depth_diff_max),
             _ptr(_t_base(int(n_candidates), rays.device)), _ptr(nc), _ptr(ng), _ptr(nf),
             C.c_uint64(int(seed) & (2 ** 64 - 1)), int(ray_index0), _ptr(z), _ptr(zu), _stream()))
@@ -398,6 +413,7 @@ def sample_depthguided(scene: HipScene, rays, n_samples, n_candidates, n_gaussia
 
 
 def fill_uniform(z_in, rays, noise_fill=None, seed=0, ray_index0=0):
+    """Stratified fill of the zero slots of z_in (NR,K), K <= 1024 -> ascending z (the bounded kernel for K <= 256)."""
     _require_hip(z_in, rays, noise_fill)
     z_in, rays = _f32c(z_in), _f32c(rays)
     NR, K = z_in.shape
@@ -406,8 +422,8 @@ def fill_uniform(z_in, rays, noise_fill=None, seed=0, ray_index0=0):
         return out
     nf = _f32c(noise_fill) if noise_fill is not None else None
     with torch.cuda.device(rays.device):
-        _lib.check(lib.diner_fill_uniform_f32(_ptr(z_in), _ptr(rays), NR, K, _ptr(nf),
-                                              C.c_uint64(int(seed) & (2 ** 64 - 1)), int(ray_index0), _ptr(out), _stream()))
+        _lib.check(lib.diner_fill_uniform_long_f32(_ptr(z_in), _ptr(rays), NR, K, _ptr(nf),
+                                                   C.c_uint64(int(seed) & (2 ** 64 - 1)), int(ray_index0), _ptr(out), _stream()))
     return out
 
 
@@ -473,7 +489,7 @@ def mlp_forward(mlp: HipMlp, zx):
 
 
 def composite(field, z, rays, white_bkgd, want_weights=True):
-    """(NR,K,4),(NR,K),(NR,8) -> weights (NR,K) | None, rgb (NR,3), depth (NR)."""
+    """(NR,K,4),(NR,K),(NR,8) -> weights (NR,K) | None, rgb (NR,3), depth (NR); K <= 1024 (the bounded kernel for K <= 256)."""
     _require_hip(field, z, rays)
     field, z, rays = _f32c(field), _f32c(z), _f32c(rays)
     NR, K = z.shape
@@ -483,8 +499,8 @@ def composite(field, z, rays, white_bkgd, want_weights=True):
     if NR == 0:
         return w, rgb, depth
     with torch.cuda.device(z.device):
-        _lib.check(lib.diner_composite_f32(_ptr(field), _ptr(z), _ptr(rays), NR, K, int(bool(white_bkgd)),
-                                           _ptr(rgb), _ptr(depth), _ptr(w), _stream()))
+        _lib.check(lib.diner_composite_long_f32(_ptr(field), _ptr(z), _ptr(rays), NR, K, int(bool(white_bkgd)),
+                                                _ptr(rgb), _ptr(depth), _ptr(w), _stream()))
     return w, rgb, depth
 
 

@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define DINER_ABI_VERSION 6
+#define DINER_ABI_VERSION 6   /* the *_long_f32 entry points were added without a bump: new symbols, no v6 contract changed */
 
 #define DINER_E_INVALID     (-1)  /* bad argument (null pointer, size, unsupported configuration) */
 #define DINER_E_UNSUPPORTED (-2)  /* configuration outside what the kernels are built for        */
@@ -137,9 +137,26 @@ int diner_sample_depthguided_f32(const DinerScene* scene, const float* rays, int
                                  const float* noise_coarse, const float* noise_gauss, const float* noise_fill,
                                  uint64_t seed, long long ray_index0, float* z_out, float* z_unfilled, void* stream);
 
-/* Stage-level entry for tests: fill_up_uniform_samples alone (nerf_renderer.py:367-397). */
+/* Stage-level entry for tests: fill_up_uniform_samples alone (nerf_renderer.py:367-397).  Limits: K <= 256. */
 int diner_fill_uniform_f32(const float* z_in, const float* rays, int NR, int K, const float* noise_fill,
                            uint64_t seed, long long ray_index0, float* z_out, void* stream);
+
+/* Long-ray entries (the reference's --nsamples takes any count, create_prediction_folder.py:43-47): same signatures and
+ * arguments as the bounded siblings above / below, whole range, the kernel picked from the sizes.
+ * Limits: 1 <= K <= 1024, 1 <= n_cand <= 4096, 0 <= G <= K; anything outside is DINER_E_INVALID before any device work.
+ * Where the bounded kernels fit (K <= 256 and n_cand <= 1024) they run with the same arguments, so results there are
+ * bit-identical to diner_sample_depthguided_f32 / diner_fill_uniform_f32 / diner_composite_f32.  Above, the sampler runs one
+ * workgroup per ray (same per-candidate likelihood, pick rule and noise keys: a ray's picks and draws do not depend on the
+ * kernel, nor on batching) and the compositor carries 16 samples per lane.  K > n_cand keeps K columns, the extra slots
+ * filled stratified (the reference returns min(K, n_cand) columns). */
+int diner_sample_depthguided_long_f32(const DinerScene* scene, const float* rays, int NR, int n_cand, int K, int G,
+                                      float depth_diff_max, const float* t_base,
+                                      const float* noise_coarse, const float* noise_gauss, const float* noise_fill,
+                                      uint64_t seed, long long ray_index0, float* z_out, float* z_unfilled, void* stream);
+int diner_fill_uniform_long_f32(const float* z_in, const float* rays, int NR, int K, const float* noise_fill,
+                                uint64_t seed, long long ray_index0, float* z_out, void* stream);
+int diner_composite_long_f32(const float* field, const float* z, const float* rays, int NR, int K, int white_bkgd,
+                             float* rgb_out, float* depth_out, float* weights_out, void* stream);
 
 /* ---- per-scene preparation: hoist of the three lin_z projections (resnetfc.py:153-155) ---------
  * lin_z[b] is linear and bilinear/border weights sum to 1, so lin_z[b](interp(latent)) == interp(lin_z[b](latent)):
@@ -192,7 +209,8 @@ int diner_mlp_forward_f32(const DinerMlp* mlp, const float* zx, long long B, flo
                           void* workspace, void* stream);
 
 /* ---- a9: compositing (nerf_renderer.py:299-301, :341-360) ------------------------------------
- *   field (NR*K,4), z (NR,K), rays (NR,8) -> rgb (NR,3), depth (NR), weights (NR,K) or NULL */
+ *   field (NR*K,4), z (NR,K), rays (NR,8) -> rgb (NR,3), depth (NR), weights (NR,K) or NULL.  Limits: K <= 256
+ *   (diner_composite_long_f32 above: K <= 1024). */
 int diner_composite_f32(const float* field, const float* z, const float* rays, int NR, int K, int white_bkgd,
                         float* rgb_out, float* depth_out, float* weights_out, void* stream);
 
@@ -286,7 +304,8 @@ int diner_colsum_f32(const float* dY, long long M, int N, int ld, float* db, voi
  * dout (P,4) given: out (P, ld) = its adjoint with respect to raw (columns >= 4 zero) */
 int diner_field_act_f32(const float* raw, const float* dout, long long P, int ld, float* out, void* stream);
 /* adjoint of diner_composite_f32 with respect to the field values (nerf_renderer.py:299-301, :341-360):
- *   g_rgb (NR,3), g_depth (NR) or NULL -> d_field (NR,K,4).  z and rays carry no gradient (the sampler is no_grad). */
+ *   g_rgb (NR,3), g_depth (NR) or NULL -> d_field (NR,K,4).  z and rays carry no gradient (the sampler is no_grad).
+ *   K <= 1024 (the range of diner_composite_long_f32; K <= 256 before the long entries). */
 int diner_composite_bwd_f32(const float* field, const float* z, const float* rays, int NR, int K, int white_bkgd,
                             const float* g_rgb, const float* g_depth, float* d_field, void* stream);
 

@@ -3,9 +3,11 @@ attributes (`n_samples`, `n_gaussian`, `n_depth_candidates`, `eval_batch_size`, 
 create_prediction_folder.py:44-47 relies on), public methods and return types.
 
 Everything runs in hand-written HIP kernels behind the C ABI of include/diner_hip.h:
-  sample_depthguided / fill_up_uniform_samples  -> diner_sample_depthguided_f32 / diner_fill_uniform_f32 (sampler.hip)
-  composite                                     -> diner_field_from_rays_f32 (mlp.hip) + diner_composite_f32
+  sample_depthguided / fill_up_uniform_samples  -> diner_sample_depthguided_long_f32 / diner_fill_uniform_long_f32 (sampler.hip)
+  composite                                     -> diner_field_from_rays_f32 (mlp.hip) + diner_composite_long_f32
   forward                                       -> the three above, per object of the batch
+The long entries take n_samples <= 1024 and n_depth_candidates <= 4096 (the reference's --nsamples); up to 256 samples and
+1024 candidates they run the bounded kernels, so results there are those of the bounded entries bit for bit.
 `model` must be the MI355X PixelNeRF of this package (it carries the channels-last scene and the packed weights).
 
 Noise: the reference draws rand/randn from torch's global generator; here the kernels draw the same three noise
@@ -90,8 +92,8 @@ class NeRFRendererDGS(torch.nn.Module):
         for sb in range(SB):
             nz = None if inj is None else tuple(None if t is None else t[sb] for t in inj)
             seed, r0 = _key(sb)
-            _, zu = ops.sample_depthguided(model.hip_scene(sb), rays[sb], n_samples, n_candidates, n_gaussian,
-                                           depth_diff_max, noise=nz, seed=seed, want_unfilled=True, ray_index0=r0)
+            _, zu = ops.sample_depthguided_long(model.hip_scene(sb), rays[sb], n_samples, n_candidates, n_gaussian,
+                                                depth_diff_max, noise=nz, seed=seed, want_unfilled=True, ray_index0=r0)
             out.append(zu)
         return torch.stack(out)
 
@@ -136,16 +138,16 @@ class NeRFRendererDGS(torch.nn.Module):
             for sb in range(SB):
                 nz = None if inj is None else tuple(None if t is None else t[sb] for t in inj)
                 seed, r0 = _key(sb)
-                zs.append(ops.sample_depthguided(model.hip_scene(sb), rays[sb], self.n_samples, self.n_depth_candidates, self.n_gaussian,
-                                                 0.05, noise=nz, seed=seed, ray_index0=r0))
+                zs.append(ops.sample_depthguided_long(model.hip_scene(sb), rays[sb], self.n_samples, self.n_depth_candidates,
+                                                      self.n_gaussian, 0.05, noise=nz, seed=seed, ray_index0=r0))
             w, rgb, depth = self._render_train_batch(model, rays, torch.stack(zs), want_weights)
             return DotMap(fine=self._format_outputs(w, rgb, depth, want_weights=want_weights))
         for sb in range(SB):
             scene = model.hip_scene(sb)
             nz = None if inj is None else tuple(None if t is None else t[sb] for t in inj)
             seed, r0 = _key(sb)
-            z = ops.sample_depthguided(scene, rays[sb], self.n_samples, self.n_depth_candidates, self.n_gaussian,
-                                       0.05, noise=nz, seed=seed, ray_index0=r0)
+            z = ops.sample_depthguided_long(scene, rays[sb], self.n_samples, self.n_depth_candidates, self.n_gaussian,
+                                            0.05, noise=nz, seed=seed, ray_index0=r0)
             w, rgb, depth = ops.render(scene, mlp, rays[sb], z, self.white_bkgd, want_weights=want_weights)
             rgbs.append(rgb)
             depths.append(depth)
