@@ -156,7 +156,8 @@ def load():
 
 
 MLP_UPDATE_TRAIN_ONLY = 1      # DINER_MLP_UPDATE_TRAIN_ONLY
-E_INVALID, E_UNSUPPORTED, E_HIP = -1, -2, -3            # include/diner_hip.h:31-33
+E_INVALID, E_UNSUPPORTED, E_HIP = -1, -2, -3            # DINER_E_* of include/diner_hip.h
+MAX_VIEWS = 16                                          # DINER_MAX_VIEWS: source views a scene may have
 
 
 def check(rc):

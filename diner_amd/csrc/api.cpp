@@ -13,9 +13,18 @@ void set_error(const char* fmt, ...) {
   va_end(ap);
 }
 
-int make_scene_dev(const DinerScene* s, SceneDev* out) {
-  DINER_CHECK_ARG(s != nullptr, "scene is null");
-  DINER_CHECK_ARG(s->nv >= 1 && s->nv <= kMaxViews, "scene: nv=%d outside [1,%d]", s->nv, kMaxViews);
+int check_fused_views(int nv, const char* who) {
+  DINER_CHECK_ARG(nv >= 1 && nv <= kMaxViewsWide, "%s: nv=%d outside [1,%d]", who, nv, kMaxViewsWide);
+  if (nv > kMaxViews) {
+    set_error("%s: nv=%d source views -- this entry is built for at most %d (the 4-view limit of the fused kernels); scenes with up to "
+              "%d views render, sample and train on the generic exact-fp32 path", who, nv, kMaxViews, kMaxViewsWide);
+    return DINER_E_UNSUPPORTED;
+  }
+  return 0;
+}
+
+template <int NMAX>
+static int fill_scene_dev(const DinerScene* s, SceneDevT<NMAX>* out) {
   DINER_CHECK_ARG(s->poses_host && s->focal_host && s->c_host, "scene: poses_host/focal_host/c_host (host arrays) missing");
   DINER_CHECK_ARG(s->img_w > 0 && s->img_h > 0, "scene: image_shape must be positive");
   memset(out, 0, sizeof(*out));
@@ -45,6 +54,19 @@ int make_scene_dev(const DinerScene* s, SceneDev* out) {
   out->Hs = s->Hs;
   out->Ws = s->Ws;
   return 0;
+}
+
+int make_scene_dev(const DinerScene* s, SceneDev* out) {
+  DINER_CHECK_ARG(s != nullptr, "scene is null");
+  int rc = check_fused_views(s->nv, "scene");
+  if (rc) return rc;
+  return fill_scene_dev(s, out);
+}
+
+int make_scene_dev(const DinerScene* s, SceneDevWide* out) {
+  DINER_CHECK_ARG(s != nullptr, "scene is null");
+  DINER_CHECK_ARG(s->nv >= 1 && s->nv <= kMaxViewsWide, "scene: nv=%d outside [1,%d]", s->nv, kMaxViewsWide);
+  return fill_scene_dev(s, out);
 }
 
 int check_mlp_config(const DinerMlpParams* p, const char* who, bool poscode) {

@@ -40,26 +40,39 @@ int validate_scene(const DinerScene* s);
 // poscode = false skips the encoding fields (gradient structs carry none)
 int check_mlp_config(const DinerMlpParams* p, const char* who, bool poscode);
 
-constexpr int kMaxViews = 4;      // NV of every shipped config (dtu.py:48, facescape.py:42, multiface.py:46)
+constexpr int kMaxViews = 4;      // NV of the fused field / training kernels and of every shipped config (dtu.py:48, facescape.py:42,
+                                  // multiface.py:46); the sampler, the index lookups and the generic path take up to kMaxViewsWide
+constexpr int kMaxViewsWide = DINER_MAX_VIEWS;   // 16
 constexpr int kStdPad = 100;      // image_encoder.py:190-191
 constexpr int kWave = 64;
 
-// Scene constants copied by value into kernel arguments (poses etc. are tiny; keeps them in SGPRs).
-struct SceneDev {
+// Scene constants copied by value into kernel arguments (poses etc. are tiny; keeps them in SGPRs).  NMAX cameras: SceneDev (4) is what
+// every kernel took before the wide route existed, layout unchanged; SceneDevWide (16 cameras, 1 KiB of kernel arguments) feeds the
+// NV-generic kernels' 5..16-view instances.
+template <int NMAX>
+struct SceneDevT {
+  static constexpr int kMax = NMAX;
   const float* latent_cl;
   const float* depth;
   const float* depth_std;
   const float* normals;
   const float* std_pad_scale;
-  float R[kMaxViews][9];
-  float t[kMaxViews][3];
-  float focal[kMaxViews][2];
-  float c[kMaxViews][2];
+  float R[NMAX][9];
+  float t[NMAX][3];
+  float focal[NMAX][2];
+  float c[NMAX][2];
   float img_w, img_h, feature_padding;
   int nv, C, Hf, Wf, Hs, Ws;
 };
-// Builds SceneDev from the C-ABI struct (poses / focal / c are host arrays there): no device access, no sync.
+using SceneDev = SceneDevT<kMaxViews>;
+using SceneDevWide = SceneDevT<kMaxViewsWide>;
+// Builds the kernel-argument scene from the C-ABI struct (poses / focal / c are host arrays there): no device access, no sync.
+// SceneDev: 1 <= nv <= 4 (5..16 views: DINER_E_UNSUPPORTED, the entry is built for four); SceneDevWide: 1 <= nv <= 16.
 int make_scene_dev(const DinerScene* s, SceneDev* out);
+int make_scene_dev(const DinerScene* s, SceneDevWide* out);
+// The refusal of an entry built for at most four source views, for entries that do not build a SceneDev (host-only, before any
+// device work): 0, DINER_E_UNSUPPORTED for 5..16 views, DINER_E_INVALID outside [1, 16].
+int check_fused_views(int nv, const char* who);
 
 // ---- device geometry (bit-compatible with the torch CPU ops of the reference) ---------------------
 #ifdef __HIPCC__

@@ -44,10 +44,15 @@ __global__ void k_fill_zero(float* __restrict__ y, long long n) {
   for (long long i = blockIdx.x * 256ll + threadIdx.x; i < n; i += gridDim.x * 256ll) y[i] = 0.0f;
 }
 
+// element i of a three-vector in registers
+__device__ __forceinline__ float pick3(const float (&a)[3], int i) { return i == 0 ? a[0] : (i == 1 ? a[1] : a[2]); }
+
 // One wave per (view, point): the reference's per-view MLP input row [latent C ; poscode(x_c) ; R d ; poscode(depth - z_c)]
-// (pixelnerf.py:91-128), any number of views <= 4, latent channels and encoding frequencies.  Geometry in the arithmetic of the fused
-// kernels (common.hpp: the reference's rounding points), the encoding as k_posenc, the latent lookup as k_index_latent.
-__global__ __launch_bounds__(256) void k_generic_inputs(SceneDev sc, FieldArgs fa, int F, int include_input, float* __restrict__ zx) {
+// (pixelnerf.py:91-128), any number of views <= 16, latent channels and encoding frequencies.  Geometry in the arithmetic of the fused
+// kernels (common.hpp: the reference's rounding points), the encoding as k_posenc, the latent lookup as k_index_latent.  Scene: SceneDev
+// (1..4 views) or SceneDevWide (5..16); the view index is wave-uniform, so the cameras are read with scalar loads in either instance.
+template <class Scene>
+__global__ __launch_bounds__(256) void k_generic_inputs(Scene sc, FieldArgs fa, int F, int include_input, float* __restrict__ zx) {
   const long long gw = (blockIdx.x * 256ll + threadIdx.x) >> 6;
   const int lane = threadIdx.x & 63;
   if (gw >= (long long)sc.nv * fa.P) return;
@@ -85,22 +90,25 @@ __global__ __launch_bounds__(256) void k_generic_inputs(SceneDev sc, FieldArgs f
     for (int ch = lane; ch < C; ch += kWave) row[ch] = p00[ch] * w00 + p01[ch] * w01 + p10[ch] * w10 + p11[ch] * w11;
   }
   // ---- the encoded inputs (positional_encoding.py:33-53: inputs first, then j-major / d-minor sin(fma(x_d, f_j, phase_j)))
+  // kSel: the wide scene's instance picks the element by selects (the lane-varying index of xc / vd / dd would otherwise put them in
+  // scratch); the four-view instance is the kernel as it was
+  constexpr bool kSel = Scene::kMax > kMaxViews;
   for (int o = lane; o < d_in; o += kWave) {
     float val;
     int D, oo = o;
     const float* src;
     float one[1] = {dd};
     if (o < 3 * per) { D = 3; src = xc; }
-    else if (o < 3 * per + 3) { row[C + o] = vd[o - 3 * per]; continue; }
+    else if (o < 3 * per + 3) { row[C + o] = kSel ? pick3(vd, o - 3 * per) : vd[o - 3 * per]; continue; }
     else { D = 1; src = one; oo = o - 3 * per - 3; }
     if (include_input && oo < D) {
-      val = src[oo];
+      val = kSel ? (D == 3 ? pick3(xc, oo) : dd) : src[oo];
     } else {
       if (include_input) oo -= D;
       const int j = oo / D, d = oo - j * D;
       const float freq = __fmul_rn(fa.freq_factor, (float)(1 << (j >> 1)));
       const float phase = (j & 1) ? 1.57079637050628662109375f : 0.0f;
-      const float arg = __fmaf_rn(src[d], freq, phase);
+      const float arg = __fmaf_rn(kSel ? (D == 3 ? pick3(xc, d) : dd) : src[d], freq, phase);
       val = fabsf(arg) < 8192.0f ? sin_posenc(arg) : sinf(arg);
     }
     row[C + o] = val;
@@ -108,7 +116,8 @@ __global__ __launch_bounds__(256) void k_generic_inputs(SceneDev sc, FieldArgs f
 }
 
 // adjoint of the latent part of k_generic_inputs: d_latent_cl[v][tap_k][ch] += w_k d_zx[v][p][ch] (float atomics; the geometry is recomputed)
-__global__ __launch_bounds__(256) void k_generic_latent_bwd(SceneDev sc, FieldArgs fa, int d_row, const float* __restrict__ d_zx,
+template <class Scene>
+__global__ __launch_bounds__(256) void k_generic_latent_bwd(Scene sc, FieldArgs fa, int d_row, const float* __restrict__ d_zx,
                                                             float* __restrict__ d_latent_cl) {
   const long long gw = (blockIdx.x * 256ll + threadIdx.x) >> 6;
   const int lane = threadIdx.x & 63;
@@ -229,6 +238,37 @@ extern "C" int diner_mlp_generic_forward_f32(const DinerMlpParams* p, float beta
   return 0;
 }
 
+namespace diner {
+namespace {
+// 1..4 views on the SceneDev instance (the kernel as it was before the wide scene existed), 5..16 on the SceneDevWide one
+template <class Scene>
+int launch_generic_inputs(const DinerScene* scene, const FieldArgs& fa, int num_freqs, int include_input, float* zx, hipStream_t stream) {
+  Scene sd;
+  int rc = make_scene_dev(scene, &sd);
+  if (rc) return rc;
+  DINER_CHECK_ARG(scene->depth && (sd.C == 0 || scene->latent_cl), "field_inputs_generic: depth / latent maps missing");
+  const long long waves = fa.P * sd.nv;
+  hipLaunchKernelGGL(k_generic_inputs<Scene>, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, stream, sd, fa, num_freqs,
+                     include_input ? 1 : 0, zx);
+  DINER_LAUNCH_OK();
+  return 0;
+}
+template <class Scene>
+int launch_generic_latent_bwd(const DinerScene* scene, const FieldArgs& fa, int d_row, const float* d_zx, float* d_latent_cl,
+                              hipStream_t stream) {
+  Scene sd;
+  int rc = make_scene_dev(scene, &sd);
+  if (rc) return rc;
+  DINER_CHECK_ARG(sd.C > 0 && d_row >= sd.C && scene->latent_cl, "field_inputs_generic_bwd: latent missing or d_row < C");
+  DINER_HIP_OK(hipMemsetAsync(d_latent_cl, 0, (size_t)sd.nv * sd.Hf * sd.Wf * sd.C * sizeof(float), stream));
+  const long long waves = fa.P * sd.nv;
+  hipLaunchKernelGGL(k_generic_latent_bwd<Scene>, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, stream, sd, fa, d_row, d_zx, d_latent_cl);
+  DINER_LAUNCH_OK();
+  return 0;
+}
+}  // namespace
+}  // namespace diner
+
 // The per-view MLP inputs of PixelNeRF.forward for any poscode / latent width: zx (nv, P, C + d_in), d_in = 4 (2 F + include_input) + 3.
 // Point source: (rays, z) with K samples per ray, or explicit xyz / viewdirs (rays == NULL).
 extern "C" int diner_field_inputs_generic_f32(const DinerScene* scene, const float* rays, const float* z, int K, const float* xyz,
@@ -237,10 +277,7 @@ extern "C" int diner_field_inputs_generic_f32(const DinerScene* scene, const flo
   DINER_CHECK_ARG(scene && zx && P > 0, "field_inputs_generic: bad arguments");
   DINER_CHECK_ARG((rays && z && K > 0 && !xyz) || (!rays && xyz && viewdirs), "field_inputs_generic: give (rays, z, K) or (xyz, viewdirs)");
   DINER_CHECK_ARG(num_freqs >= 0 && num_freqs <= 30 && (num_freqs > 0 || include_input), "field_inputs_generic: bad positional encoding");
-  SceneDev sd;
-  int rc = make_scene_dev(scene, &sd);
-  if (rc) return rc;
-  DINER_CHECK_ARG(scene->depth && (sd.C == 0 || scene->latent_cl), "field_inputs_generic: depth / latent maps missing");
+  DINER_CHECK_ARG(scene->nv >= 1 && scene->nv <= kMaxViewsWide, "scene: nv=%d outside [1,%d]", scene->nv, kMaxViewsWide);
   FieldArgs fa;
   memset(&fa, 0, sizeof(fa));
   fa.rays = rays;
@@ -250,11 +287,8 @@ extern "C" int diner_field_inputs_generic_f32(const DinerScene* scene, const flo
   fa.K = rays ? K : 1;
   fa.P = P;
   fa.freq_factor = freq_factor;
-  const long long waves = P * sd.nv;
-  hipLaunchKernelGGL(k_generic_inputs, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, (hipStream_t)stream, sd, fa, num_freqs,
-                     include_input ? 1 : 0, zx);
-  DINER_LAUNCH_OK();
-  return 0;
+  return scene->nv <= kMaxViews ? launch_generic_inputs<SceneDev>(scene, fa, num_freqs, include_input, zx, (hipStream_t)stream)
+                                : launch_generic_inputs<SceneDevWide>(scene, fa, num_freqs, include_input, zx, (hipStream_t)stream);
 }
 
 
@@ -436,19 +470,13 @@ extern "C" int diner_mlp_generic_backward_f32(const DinerMlpParams* p, const Din
 extern "C" int diner_field_inputs_generic_bwd_f32(const DinerScene* scene, const float* xyz, const float* viewdirs, long long P, int d_row,
                                                   const float* d_zx, float* d_latent_cl, void* stream) {
   DINER_CHECK_ARG(scene && xyz && viewdirs && d_zx && d_latent_cl && P > 0, "field_inputs_generic_bwd: bad arguments");
-  SceneDev sd;
-  int rc = make_scene_dev(scene, &sd);
-  if (rc) return rc;
-  DINER_CHECK_ARG(sd.C > 0 && d_row >= sd.C && scene->latent_cl, "field_inputs_generic_bwd: latent missing or d_row < C");
+  DINER_CHECK_ARG(scene->nv >= 1 && scene->nv <= kMaxViewsWide, "scene: nv=%d outside [1,%d]", scene->nv, kMaxViewsWide);
   FieldArgs fa;
   memset(&fa, 0, sizeof(fa));
   fa.xyz = xyz;
   fa.viewdirs = viewdirs;
   fa.K = 1;
   fa.P = P;
-  DINER_HIP_OK(hipMemsetAsync(d_latent_cl, 0, (size_t)sd.nv * sd.Hf * sd.Wf * sd.C * sizeof(float), (hipStream_t)stream));
-  const long long waves = P * sd.nv;
-  hipLaunchKernelGGL(k_generic_latent_bwd, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, (hipStream_t)stream, sd, fa, d_row, d_zx, d_latent_cl);
-  DINER_LAUNCH_OK();
-  return 0;
+  return scene->nv <= kMaxViews ? launch_generic_latent_bwd<SceneDev>(scene, fa, d_row, d_zx, d_latent_cl, (hipStream_t)stream)
+                                : launch_generic_latent_bwd<SceneDevWide>(scene, fa, d_row, d_zx, d_latent_cl, (hipStream_t)stream);
 }

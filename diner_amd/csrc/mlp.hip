@@ -952,7 +952,9 @@ extern "C" size_t diner_mlp_forward_workspace_bytes(long long B) {
 }
 
 static int check_field_scene(const DinerScene* scene, const DinerMlp* mlp, SceneDev* sd, int precision) {
-  int rc = make_scene_dev(scene, sd);
+  int rc = check_fused_views(scene->nv, "field");      // 5..16 views: the generic path (before the handle is read)
+  if (rc) return rc;
+  rc = make_scene_dev(scene, sd);
   if (rc) return rc;
   DINER_CHECK_ARG(scene->proj_stamp == mlp->impl.stamp,
                   "field: scene->latent_proj was prepared with another packed-weights handle (proj_stamp %llu, this handle %llu): "
@@ -1113,13 +1115,16 @@ extern "C" int diner_mlp_forward_f32(const DinerMlp* mlp, const float* zx, long 
 }
 
 extern "C" size_t diner_scene_proj_bytes(const DinerScene* scene) {
-  if (!scene || scene->nv <= 0 || scene->Hf <= 0 || scene->Wf <= 0) return 0;
+  // the projected maps feed the fused kernels only: no size for a scene they do not take (nv outside [1, 4])
+  if (!scene || scene->nv <= 0 || scene->nv > kMaxViews || scene->Hf <= 0 || scene->Wf <= 0) return 0;
   return (size_t)3 * scene->nv * scene->Hf * scene->Wf * kLatent * sizeof(float);
 }
 
 extern "C" int diner_scene_prepare_f32(const DinerScene* scene, const DinerMlp* mlp, float* latent_proj_out,
                                        void* stream) {
   DINER_CHECK_ARG(scene && mlp && latent_proj_out, "scene_prepare: null pointer argument");
+  int rc = check_fused_views(scene->nv, "scene_prepare");
+  if (rc) return rc;
   DINER_CHECK_ARG(scene->latent_cl && scene->C == kLatent && scene->Hf > 0 && scene->Wf > 0 && scene->nv > 0,
                   "scene_prepare: channels-last latent (NV,Hf,Wf,%d) missing", kLatent);
   return launch_hoist(&mlp->impl, scene->latent_cl, (long long)scene->nv * scene->Hf * scene->Wf, latent_proj_out,
@@ -1130,6 +1135,8 @@ extern "C" size_t diner_scene_proj_f16_bytes(const DinerScene* scene) { return d
 
 extern "C" int diner_scene_prepare_f16(const DinerScene* scene, void* latent_proj_f16_out, void* stream) {
   DINER_CHECK_ARG(scene && latent_proj_f16_out, "scene_prepare_f16: null pointer argument");
+  int rc = check_fused_views(scene->nv, "scene_prepare_f16");
+  if (rc) return rc;
   DINER_CHECK_ARG(scene->latent_proj && scene->C == kLatent && scene->Hf > 0 && scene->Wf > 0 && scene->nv > 0,
                   "scene_prepare_f16: scene->latent_proj (diner_scene_prepare_f32) missing");
   DINER_CHECK_ARG((reinterpret_cast<size_t>(latent_proj_f16_out) & 15) == 0, "scene_prepare_f16: output must be 16-byte aligned");

@@ -36,8 +36,12 @@ struct SamplerArgs {
 };
 
 // surface likelihood of one candidate in one source view (nerf_renderer.py:107-128)
-__device__ __forceinline__ float view_likelihood(const SceneDev& sc, int v, float px, float py, float pz,
-                                                 const float* dcam, float step_size, float ddmax) {
+// kDirHere: the ray direction in this camera is rotated here, where the normal test needs it (dcam unused; dx, dy, dz the world
+// direction) -- the wide scene's instances, which keep no per-view array
+template <class Scene, bool kDirHere = false>
+__device__ __forceinline__ float view_likelihood(const Scene& sc, int v, float px, float py, float pz,
+                                                 const float* dcam, float step_size, float ddmax, float dx = 0.0f, float dy = 0.0f,
+                                                 float dz = 0.0f) {
   float xc, yc, zc;
   world_to_cam(sc.R[v], sc.t[v], px, py, pz, xc, yc, zc);
   const float u = project_axis(xc, zc, sc.focal[v][0], sc.c[v][0], sc.img_w);
@@ -66,6 +70,13 @@ __device__ __forceinline__ float view_likelihood(const SceneDev& sc, int v, floa
   const int nx = nearest_zeros(u, Ws), ny = nearest_zeros(w, Hs);
   if (nx >= 0 && ny >= 0) {
     const float* np_ = sc.normals + (size_t)v * 3 * plane + (size_t)ny * Ws + nx;
+    float dhere[3];
+    if constexpr (kDirHere) {                                                // :102-103
+      dhere[0] = rot_row(sc.R[v] + 0, dx, dy, dz);
+      dhere[1] = rot_row(sc.R[v] + 3, dx, dy, dz);
+      dhere[2] = rot_row(sc.R[v] + 6, dx, dy, dz);
+      dcam = dhere;
+    }
     const float cosd = __fadd_rn(__fadd_rn(__fmul_rn(dcam[0], np_[0]), __fmul_rn(dcam[1], np_[plane])),
                                  __fmul_rn(dcam[2], np_[2 * plane]));        // :119
     if (!(cosd <= 0.0f)) return 0.0f;                                        // :121
@@ -151,7 +162,10 @@ __device__ __forceinline__ void fill_and_sort(float* s, int K, int n2, float nea
   bitonic_sort<kThreads>(s, n2, lane);                                       // :396
 }
 
-__global__ __launch_bounds__(kRaysPerBlock* kWave) void k_sample_depthguided(SceneDev sc, SamplerArgs a) {
+// Scene: SceneDev (1..4 views, the instance every 4-view call runs) or SceneDevWide (5..16 views).  The body is a device function of its
+// own: written inside the kernel, the 16-view instance's register allocation left a 64-byte stack slot behind (no scratch access)
+template <class Scene>
+__device__ __forceinline__ void sample_depthguided_body(const Scene& sc, const SamplerArgs& a) {
   __shared__ float sL[kRaysPerBlock][kMaxCand];
   __shared__ float sZ[kRaysPerBlock][kMaxCand];
   __shared__ float sS[kRaysPerBlock][kMaxK];
@@ -169,12 +183,17 @@ __global__ __launch_bounds__(kRaysPerBlock* kWave) void k_sample_depthguided(Sce
   const float step_size = __fdiv_rn(__fsub_rn(far, near), (float)n_cand);       // nerf_renderer.py:95
   const float jitter = (float)(1.0 / (double)n_cand);                           // :53, applied in fp32 at :57
 
-  float dcam[kMaxViews][3];
+  // the ray direction in each camera (:102-103): four views unrolled into registers once per ray; the wide scene's instance rotates it
+  // inside view_likelihood (a dynamically indexed array of 16 views would live in scratch) -- the same rot_row arithmetic either way
+  constexpr bool kFew = Scene::kMax <= kMaxViews;
+  float dcam[kFew ? kMaxViews : 1][3];
+  if constexpr (kFew) {
 #pragma unroll
-  for (int v = 0; v < kMaxViews; ++v) {                                         // :102-103
-    dcam[v][0] = rot_row(sc.R[v] + 0, dx, dy, dz);
-    dcam[v][1] = rot_row(sc.R[v] + 3, dx, dy, dz);
-    dcam[v][2] = rot_row(sc.R[v] + 6, dx, dy, dz);
+    for (int v = 0; v < kMaxViews; ++v) {                                       // :102-103
+      dcam[v][0] = rot_row(sc.R[v] + 0, dx, dy, dz);
+      dcam[v][1] = rot_row(sc.R[v] + 3, dx, dy, dz);
+      dcam[v][2] = rot_row(sc.R[v] + 6, dx, dy, dz);
+    }
   }
 
   // ---- candidates: lane owns i = lane + 64 c (coalesced noise reads) -----------------------------
@@ -189,8 +208,13 @@ __global__ __launch_bounds__(kRaysPerBlock* kWave) void k_sample_depthguided(Sce
       const float px = __fadd_rn(ox, __fmul_rn(z, dx));                         // :96
       const float py = __fadd_rn(oy, __fmul_rn(z, dy));
       const float pz = __fadd_rn(oz, __fmul_rn(z, dz));
-      for (int v = 0; v < sc.nv; ++v)
-        lk = fmaxf(lk, view_likelihood(sc, v, px, py, pz, dcam[v], step_size, a.depth_diff_max));   // :129
+      for (int v = 0; v < sc.nv; ++v) {
+        if constexpr (kFew) {
+          lk = fmaxf(lk, view_likelihood(sc, v, px, py, pz, dcam[v], step_size, a.depth_diff_max));   // :129
+        } else {
+          lk = fmaxf(lk, view_likelihood<Scene, true>(sc, v, px, py, pz, nullptr, step_size, a.depth_diff_max, dx, dy, dz));
+        }
+      }
     }
     L[i] = lk;
     Z[i] = z;
@@ -310,6 +334,9 @@ __global__ __launch_bounds__(kRaysPerBlock* kWave) void k_sample_depthguided(Sce
     for (int j = lane; j < K; j += kWave) a.z_out[(size_t)ray * K + j] = S[j];
 }
 
+template <class Scene>
+__global__ __launch_bounds__(kRaysPerBlock* kWave) void k_sample_depthguided(Scene sc, SamplerArgs a) { sample_depthguided_body(sc, a); }
+
 __global__ __launch_bounds__(kRaysPerBlock* kWave) void k_fill_uniform(const float* z_in, const float* rays, int NR, int K,
                                                                         const float* noise_fill, uint64_t seed,
                                                                         uint32_t ray_key0, float* z_out) {
@@ -335,7 +362,8 @@ __global__ __launch_bounds__(kRaysPerBlock* kWave) void k_fill_uniform(const flo
 // likelihood bits are view_likelihood's, the pick rule (all candidates above the threshold T, ties at T in index order)
 // and the noise keys are the bounded kernel's: a ray's picks and draws do not depend on which kernel ran.
 // LDS: 2 x 16 KB candidate rows + 4 KB slot row + the reduction carries (~36 KB, 4 workgroups per CU).
-__global__ __launch_bounds__(kWideThreads) void k_sample_depthguided_wide(SceneDev sc, SamplerArgs a) {
+template <class Scene>
+__global__ __launch_bounds__(kWideThreads) void k_sample_depthguided_wide(Scene sc, SamplerArgs a) {
   __shared__ float L[kWideMaxCand];
   __shared__ float Z[kWideMaxCand];
   __shared__ float S[kLongMaxK];
@@ -352,12 +380,17 @@ __global__ __launch_bounds__(kWideThreads) void k_sample_depthguided_wide(SceneD
   const float step_size = __fdiv_rn(__fsub_rn(far, near), (float)n_cand);       // nerf_renderer.py:95
   const float jitter = (float)(1.0 / (double)n_cand);                           // :53, applied in fp32 at :57
 
-  float dcam[kMaxViews][3];
+  // the ray direction in each camera (:102-103): four views unrolled into registers once per ray; the wide scene's instance rotates it
+  // inside view_likelihood (a dynamically indexed array of 16 views would live in scratch) -- the same rot_row arithmetic either way
+  constexpr bool kFew = Scene::kMax <= kMaxViews;
+  float dcam[kFew ? kMaxViews : 1][3];
+  if constexpr (kFew) {
 #pragma unroll
-  for (int v = 0; v < kMaxViews; ++v) {                                         // :102-103
-    dcam[v][0] = rot_row(sc.R[v] + 0, dx, dy, dz);
-    dcam[v][1] = rot_row(sc.R[v] + 3, dx, dy, dz);
-    dcam[v][2] = rot_row(sc.R[v] + 6, dx, dy, dz);
+    for (int v = 0; v < kMaxViews; ++v) {                                       // :102-103
+      dcam[v][0] = rot_row(sc.R[v] + 0, dx, dy, dz);
+      dcam[v][1] = rot_row(sc.R[v] + 3, dx, dy, dz);
+      dcam[v][2] = rot_row(sc.R[v] + 6, dx, dy, dz);
+    }
   }
 
   // ---- candidates: thread owns i = tid + 256 c (coalesced noise reads); slots >= n_cand are zero -------
@@ -372,8 +405,13 @@ __global__ __launch_bounds__(kWideThreads) void k_sample_depthguided_wide(SceneD
       const float px = __fadd_rn(ox, __fmul_rn(z, dx));                         // :96
       const float py = __fadd_rn(oy, __fmul_rn(z, dy));
       const float pz = __fadd_rn(oz, __fmul_rn(z, dz));
-      for (int v = 0; v < sc.nv; ++v)
-        lk = fmaxf(lk, view_likelihood(sc, v, px, py, pz, dcam[v], step_size, a.depth_diff_max));   // :129
+      for (int v = 0; v < sc.nv; ++v) {
+        if constexpr (kFew) {
+          lk = fmaxf(lk, view_likelihood(sc, v, px, py, pz, dcam[v], step_size, a.depth_diff_max));   // :129
+        } else {
+          lk = fmaxf(lk, view_likelihood<Scene, true>(sc, v, px, py, pz, nullptr, step_size, a.depth_diff_max, dx, dy, dz));
+        }
+      }
     }
     L[i] = lk;
     Z[i] = z;
@@ -521,6 +559,27 @@ __global__ __launch_bounds__(kWideThreads) void k_fill_uniform_wide(const float*
   for (int j = tid; j < K; j += kWideThreads) z_out[(size_t)ray * K + j] = S[j];
 }
 
+// the scene's cameras into the kernel arguments and the launch: 1..4 views on the SceneDev instance (the kernels as they were before the
+// wide scene existed), 5..16 on the SceneDevWide one
+template <class Scene>
+static int launch_sampler(const DinerScene* scene, const SamplerArgs& a, bool wide, const char* who, hipStream_t stream) {
+  Scene sd;
+  int rc = make_scene_dev(scene, &sd);
+  if (rc) return rc;
+  DINER_CHECK_ARG(scene->depth && scene->depth_std && scene->normals && scene->std_pad_scale, "%s: scene depth/std/normal maps missing", who);
+  if (wide)
+    hipLaunchKernelGGL(k_sample_depthguided_wide<Scene>, dim3(a.NR), dim3(kWideThreads), 0, stream, sd, a);
+  else
+    hipLaunchKernelGGL(k_sample_depthguided<Scene>, dim3((a.NR + kRaysPerBlock - 1) / kRaysPerBlock), dim3(kRaysPerBlock * kWave), 0,
+                       stream, sd, a);
+  DINER_LAUNCH_OK();
+  return 0;
+}
+static int sample(const DinerScene* scene, const SamplerArgs& a, bool wide, const char* who, hipStream_t stream) {
+  DINER_CHECK_ARG(scene->nv >= 1 && scene->nv <= kMaxViewsWide, "scene: nv=%d outside [1,%d]", scene->nv, kMaxViewsWide);
+  return scene->nv <= kMaxViews ? launch_sampler<SceneDev>(scene, a, wide, who, stream)
+                                : launch_sampler<SceneDevWide>(scene, a, wide, who, stream);
+}
 }  // namespace diner
 
 using namespace diner;
@@ -537,17 +596,9 @@ extern "C" int diner_sample_depthguided_f32(const DinerScene* scene, const float
   DINER_CHECK_ARG(G >= 0 && G <= K, "sample_depthguided: need 0 <= n_gaussian <= n_samples (got %d, %d)", G, K);
   DINER_CHECK_ARG(ray_index0 >= 0 && ray_index0 + NR <= (1ll << 32),
                   "sample_depthguided: ray_index0 = %lld outside [0, 2^32 - NR] (the noise key of a ray is a 32-bit index)", ray_index0);
-  SceneDev sd;
-  int rc = make_scene_dev(scene, &sd);
-  if (rc) return rc;
-  DINER_CHECK_ARG(scene->depth && scene->depth_std && scene->normals && scene->std_pad_scale,
-                  "sample_depthguided: scene depth/std/normal maps missing");
   SamplerArgs a{rays, t_base, noise_coarse, noise_gauss, noise_fill, z_out, z_unfilled, seed, (uint32_t)ray_index0, NR, n_cand, K,
                 G, depth_diff_max};
-  const int blocks = (NR + kRaysPerBlock - 1) / kRaysPerBlock;
-  hipLaunchKernelGGL(k_sample_depthguided, dim3(blocks), dim3(kRaysPerBlock * kWave), 0, (hipStream_t)stream, sd, a);
-  DINER_LAUNCH_OK();
-  return 0;
+  return sample(scene, a, false, "sample_depthguided", (hipStream_t)stream);
 }
 
 extern "C" int diner_fill_uniform_f32(const float* z_in, const float* rays, int NR, int K, const float* noise_fill,
@@ -582,16 +633,9 @@ extern "C" int diner_sample_depthguided_long_f32(const DinerScene* scene, const 
   if (K <= kMaxK && n_cand <= kMaxCand)
     return diner_sample_depthguided_f32(scene, rays, NR, n_cand, K, G, depth_diff_max, t_base, noise_coarse, noise_gauss,
                                         noise_fill, seed, ray_index0, z_out, z_unfilled, stream);
-  SceneDev sd;
-  int rc = make_scene_dev(scene, &sd);
-  if (rc) return rc;
-  DINER_CHECK_ARG(scene->depth && scene->depth_std && scene->normals && scene->std_pad_scale,
-                  "sample_depthguided_long: scene depth/std/normal maps missing");
   SamplerArgs a{rays, t_base, noise_coarse, noise_gauss, noise_fill, z_out, z_unfilled, seed, (uint32_t)ray_index0, NR, n_cand, K,
                 G, depth_diff_max};
-  hipLaunchKernelGGL(k_sample_depthguided_wide, dim3(NR), dim3(kWideThreads), 0, (hipStream_t)stream, sd, a);
-  DINER_LAUNCH_OK();
-  return 0;
+  return sample(scene, a, true, "sample_depthguided_long", (hipStream_t)stream);
 }
 
 extern "C" int diner_fill_uniform_long_f32(const float* z_in, const float* rays, int NR, int K, const float* noise_fill,

@@ -32,7 +32,9 @@ __global__ void k_posenc(const float* __restrict__ x, long long N, int D, int F,
   }
 }
 
-__global__ void k_index(SceneDev sc, int mode, const float* __restrict__ uv, long long N, float* __restrict__ out) {
+// Scene: SceneDev (1..4 views) or SceneDevWide (5..16): the kernels read the maps, not the cameras
+template <class Scene>
+__global__ void k_index(Scene sc, int mode, const float* __restrict__ uv, long long N, float* __restrict__ out) {
   // one thread per (view, point) for the nearest-neighbour lookups; the latent map has its own kernel
   const long long total = (long long)sc.nv * N;
   for (long long idx = blockIdx.x * (long long)blockDim.x + threadIdx.x; idx < total;
@@ -71,7 +73,8 @@ __global__ void k_index(SceneDev sc, int mode, const float* __restrict__ uv, lon
 }
 
 // bilinear / border on the channels-last feature map; one wave per (view, point), lanes over channels.
-__global__ __launch_bounds__(256) void k_index_latent(SceneDev sc, const float* __restrict__ uv, long long N,
+template <class Scene>
+__global__ __launch_bounds__(256) void k_index_latent(Scene sc, const float* __restrict__ uv, long long N,
                                                       float* __restrict__ out) {
   const long long gw = (blockIdx.x * (long long)blockDim.x + threadIdx.x) >> 6;
   const int lane = threadIdx.x & 63;
@@ -116,26 +119,34 @@ extern "C" int diner_posenc_f32(const float* x, long long N, int d_in, int num_f
   return 0;
 }
 
-extern "C" int diner_index_f32(const DinerScene* scene, int mode, const float* uv, long long N, float* out,
-                               void* stream) {
-  DINER_CHECK_ARG(scene && uv && out, "index: null pointer argument");
-  DINER_CHECK_ARG(mode >= 0 && mode <= 3, "index: mode %d outside [0,3]", mode);
-  SceneDev sd;
+namespace diner {
+template <class Scene>
+static int launch_index(const DinerScene* scene, int mode, const float* uv, long long N, float* out, hipStream_t stream) {
+  Scene sd;
   int rc = make_scene_dev(scene, &sd);
   if (rc) return rc;
   if (N == 0) return 0;
   if (mode == 0) {
     DINER_CHECK_ARG(scene->latent_cl && sd.C > 0 && sd.Hf > 0 && sd.Wf > 0, "index: latent map missing");
     const long long waves = (long long)sd.nv * N;
-    hipLaunchKernelGGL(k_index_latent, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, (hipStream_t)stream, sd, uv, N,
-                       out);
+    hipLaunchKernelGGL(k_index_latent<Scene>, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, stream, sd, uv, N, out);
   } else {
     DINER_CHECK_ARG(scene->depth && scene->depth_std && scene->normals && scene->std_pad_scale,
                     "index: depth/std/normal maps missing");
     const long long total = (long long)sd.nv * N;
     const int blocks = (int)((total + 255) / 256 > 8192 ? 8192 : (total + 255) / 256);
-    hipLaunchKernelGGL(k_index, dim3(blocks), dim3(256), 0, (hipStream_t)stream, sd, mode, uv, N, out);
+    hipLaunchKernelGGL(k_index<Scene>, dim3(blocks), dim3(256), 0, stream, sd, mode, uv, N, out);
   }
   DINER_LAUNCH_OK();
   return 0;
+}
+}  // namespace diner
+
+extern "C" int diner_index_f32(const DinerScene* scene, int mode, const float* uv, long long N, float* out,
+                               void* stream) {
+  DINER_CHECK_ARG(scene && uv && out, "index: null pointer argument");
+  DINER_CHECK_ARG(mode >= 0 && mode <= 3, "index: mode %d outside [0,3]", mode);
+  DINER_CHECK_ARG(scene->nv >= 1 && scene->nv <= kMaxViewsWide, "scene: nv=%d outside [1,%d]", scene->nv, kMaxViewsWide);
+  return scene->nv <= kMaxViews ? launch_index<SceneDev>(scene, mode, uv, N, out, (hipStream_t)stream)
+                                : launch_index<SceneDevWide>(scene, mode, uv, N, out, (hipStream_t)stream);
 }

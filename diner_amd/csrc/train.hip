@@ -1326,8 +1326,10 @@ static int train_inputs(const DinerScene* scene, const float* xyz, const float* 
                         float* tap_w, float* lat, void* stream, bool gather) {
   DINER_CHECK_ARG(scene && xyz && viewdirs && feat && tap_row && tap_w && lat, "train_inputs: null pointer argument");
   DINER_CHECK_ARG(P > 0, "train_inputs: P must be positive");
+  int rc = check_fused_views(scene->nv, "train_inputs");
+  if (rc) return rc;
   SceneDev sd;
-  int rc = make_scene_dev(scene, &sd);
+  rc = make_scene_dev(scene, &sd);
   if (rc) return rc;
   DINER_CHECK_ARG(scene->latent_cl && scene->depth && sd.C == kLatent, "train_inputs: latent (512 channels-last) / depth maps missing");
   FieldArgs fa;
@@ -1584,7 +1586,7 @@ int linear_bwd(const float* dy, int ldy, const float* x, int ldx, bool relu_in, 
 }  // namespace
 
 extern "C" size_t diner_field_train_workspace_bytes(long long P, int nv) {
-  if (P <= 0 || nv <= 0) return 0;
+  if (P <= 0 || nv <= 0 || nv > kMaxViews) return 0;      // the shipped-shape training takes 1..4 views (5..16: the generic path)
   return train_ws(P, nv).total * sizeof(float);
 }
 
@@ -1592,6 +1594,8 @@ extern "C" size_t diner_field_train_workspace_bytes(long long P, int nv) {
 // rows = P nv for b < 3, P behind the view mean), H[0..4] (fc_0 outputs), x_last (entering lin_out), raw (lin_out's outputs)
 extern "C" int diner_field_train_ws_layout(long long P, int nv, long long* float_offsets, int n) {
   DINER_CHECK_ARG(P > 0 && nv > 0 && float_offsets && n >= 12, "field_train_ws_layout: bad arguments (12 offsets)");
+  int rc = check_fused_views(nv, "field_train_ws_layout");
+  if (rc) return rc;
   const TrainWs w = train_ws(P, nv);
   for (int b = 0; b < 5; ++b) {
     float_offsets[b] = (long long)w.X[b];
@@ -1725,7 +1729,9 @@ static int forward_layerwise(const DinerScene* scene, const DinerMlpParams* p, c
 extern "C" int diner_field_train_forward_s_f32(const DinerScene* scene, const DinerMlpParams* p, const float* xyz, const float* viewdirs,
                                                long long P, float* out, void* workspace, void* scratch, void* stream) {
   DINER_CHECK_ARG(scene && xyz && viewdirs && out && workspace && P > 0, "field_train_forward: bad arguments");
-  int rc = check_train_params(p, true);
+  int rc = check_fused_views(scene->nv, "field_train_forward");
+  if (rc) return rc;
+  rc = check_train_params(p, true);
   if (rc) return rc;
   const TrainWs w = train_ws(P, scene->nv);
   return forward_layerwise(scene, p, xyz, viewdirs, P, out, (float*)workspace, scratch_base((float*)workspace, scratch, w), w, stream, nullptr);
@@ -1739,6 +1745,8 @@ extern "C" int diner_field_train_forward_f32(const DinerScene* scene, const Dine
 // (may be one buffer shared by the objects of a step: calls on one stream use it one after the other)
 extern "C" int diner_field_train_workspace_split(long long P, int nv, size_t* saved_bytes, size_t* scratch_bytes) {
   DINER_CHECK_ARG(P > 0 && nv > 0 && saved_bytes && scratch_bytes, "field_train_workspace_split: bad arguments");
+  int rc = check_fused_views(nv, "field_train_workspace_split");
+  if (rc) return rc;
   const TrainWs w = train_ws(P, nv);
   *saved_bytes = w.saved_total * sizeof(float);
   *scratch_bytes = (w.total - w.saved_total) * sizeof(float);
@@ -1867,7 +1875,9 @@ extern "C" int diner_field_train_forward_fused_f32(const DinerScene* scene, cons
                                                    const float* viewdirs, long long P, float* out, void* workspace, void* scratch,
                                                    float* latent_proj_out, void* stream) {
   DINER_CHECK_ARG(scene && mlp && xyz && viewdirs && out && workspace && P > 0, "field_train_forward_fused: bad arguments");
-  int rc = check_train_params(p, true);
+  int rc = check_fused_views(scene->nv, "field_train_forward_fused");
+  if (rc) return rc;
+  rc = check_train_params(p, true);
   if (rc) return rc;
   DINER_CHECK_ARG(use_lin512() && (use_fwd_f16() || use_bwd_f16()), "field_train_forward_fused: needs the 512-layer kernels of the backward");
   float* ws = (float*)workspace;
@@ -1879,6 +1889,8 @@ extern "C" int diner_field_train_forward_fused_f32(const DinerScene* scene, cons
 // waits for `stream` (one 4-byte read back)
 extern "C" int diner_field_train_fused_overflowed(const void* workspace, long long P, int nv, int* overflowed, void* stream) {
   DINER_CHECK_ARG(workspace && overflowed && P > 0 && nv > 0, "field_train_fused_overflowed: bad arguments");
+  int rc = check_fused_views(nv, "field_train_fused_overflowed");
+  if (rc) return rc;
   const TrainWs w = train_ws(P, nv);
   DINER_HIP_OK(hipMemcpyAsync(overflowed, reinterpret_cast<const int*>((const float*)workspace + w.flags) + kFlagFusedOvf, sizeof(int),
                               hipMemcpyDeviceToHost, (hipStream_t)stream));
@@ -2141,7 +2153,9 @@ static int backward_core(const DinerScene* const* scenes, int n_obj, const Diner
 extern "C" int diner_field_train_backward_s_f32(const DinerScene* scene, const DinerMlpParams* p, const DinerMlpParams* grads, long long P,
                                                 const float* d_out, void* workspace, void* scratch, float* d_latent_cl, void* stream) {
   DINER_CHECK_ARG(scene && d_out && workspace && P > 0, "field_train_backward: bad arguments");
-  int rc = check_train_params(p, false);
+  int rc = check_fused_views(scene->nv, "field_train_backward");
+  if (rc) return rc;
+  rc = check_train_params(p, false);
   if (rc) return rc;
   rc = check_train_params(grads, false);
   if (rc) return rc;
@@ -2183,12 +2197,14 @@ int check_batch(const DinerScene* const* scenes, int n_obj, long long P) {
   DINER_CHECK_ARG(scenes && n_obj > 0 && n_obj <= 64 && P > 0, "field_train_batch: bad arguments (1 <= n_obj <= 64)");
   for (int o = 0; o < n_obj; ++o)
     DINER_CHECK_ARG(scenes[o] && scenes[o]->nv == scenes[0]->nv, "field_train_batch: every object needs the same number of source views");
-  return 0;
+  return check_fused_views(scenes[0]->nv, "field_train_batch");
 }
 }  // namespace
 
 extern "C" int diner_field_train_batch_workspace_split(long long P, int nv, int n_obj, size_t* saved_bytes, size_t* scratch_bytes) {
   DINER_CHECK_ARG(P > 0 && nv > 0 && n_obj > 0 && saved_bytes && scratch_bytes, "field_train_batch_workspace_split: bad arguments");
+  int rc = check_fused_views(nv, "field_train_batch_workspace_split");
+  if (rc) return rc;
   return diner_field_train_workspace_split(P * n_obj, nv, saved_bytes, scratch_bytes);
 }
 

@@ -77,6 +77,10 @@ class HipScene:
     """
 
     def __init__(self, latent, depths, depths_std, normals, poses, focal, c, image_shape, feature_padding):
+        nv = int(poses.shape[0])
+        if not 1 <= nv <= _lib.MAX_VIEWS:          # before any device work: the library takes 1 .. DINER_MAX_VIEWS source views
+            raise ValueError(f"diner_amd: a scene has 1 to {_lib.MAX_VIEWS} source views (got {nv}); four run on the fused kernels, "
+                             f"any other number on the generic exact-fp32 path")
         dev = None
         for t in (latent, depths, depths_std, normals):
             if t is not None:
@@ -85,7 +89,7 @@ class HipScene:
         if dev is None:
             raise ValueError("HipScene needs at least one map on a HIP device")
         self.device = dev
-        self.nv = int(poses.shape[0])
+        self.nv = nv
         self.latent_cl = None
         self.C = self.Hf = self.Wf = 0
         if latent is not None:
@@ -328,6 +332,12 @@ class GenericMlp:
 GENERIC_POINTS_PER_LAUNCH = 1 << 18      # bounds the (NV, P, d_latent + d_in) matrix of the generic path (2.4 GB at NV 4 x 567 floats)
 
 
+def generic_points_per_launch(nv):
+    """Points per generic launch for a scene of nv views: GENERIC_POINTS_PER_LAUNCH up to four views, scaled by 4 / nv above, so that the
+    (nv, P, d_row) matrix and the 3 nv P d_hidden floats of MLP workspace stay at the four-view size."""
+    return max(1, GENERIC_POINTS_PER_LAUNCH * 4 // max(4, int(nv)))
+
+
 def field_generic(scene: HipScene, mlp: GenericMlp, rays=None, z=None, xyz=None, viewdirs=None):
     """PixelNeRF.forward on the generic slow path: (rays (NR,8), z (NR,K)) or (xyz, viewdirs) (P,3) -> (P,4) [r, g, b, sigma]
     (sigmoid / relu applied, pixelnerf.py:139-143).  The network must combine its views (combine_layer < n_blocks), as PixelNeRF's does."""
@@ -350,7 +360,8 @@ def field_generic(scene: HipScene, mlp: GenericMlp, rays=None, z=None, xyz=None,
     if P == 0:
         return out
     D = mlp.d_latent + mlp.d_in
-    step = GENERIC_POINTS_PER_LAUNCH if rays is None else max(1, GENERIC_POINTS_PER_LAUNCH // K) * K
+    per_launch = generic_points_per_launch(scene.nv)
+    step = per_launch if rays is None else max(1, per_launch // K) * K
     with torch.cuda.device(dev):
         for p0 in range(0, P, step):
             p1 = min(P, p0 + step)

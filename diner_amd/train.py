@@ -126,7 +126,7 @@ def _param_struct(tensors, freq_factor=6.28):
 
 def fused_forward_enabled(P=None, scene=None):
     """DINER_TRAIN_FUSED_FWD: 1 = always, 0 = never, unset = by size (from 16384 sample points per object on)."""
-    if scene is not None and scene.nv != 4:          # the fused kernels are built for four source views (the layer-wise forward: any)
+    if scene is not None and scene.nv != 4:          # the fused kernels are built for four source views (the layer-wise forward: 1..4)
         return False
     e = os.environ.get("DINER_TRAIN_FUSED_FWD", "")
     if e in ("0", "1"):
@@ -543,7 +543,7 @@ class _FieldAct(torch.autograd.Function):
 
 def field_train_generic(scene: HipScene, mlp_module, xyz, viewdirs, latent, num_freqs, include_input, freq_factor):
     """PixelNeRF.forward for one object in grad mode on the generic path: (P, 3) x 2 -> (P, 4), differentiable with respect to the latent
-    (NV, C, Hf, Wf) and the MLP parameters (any d_hidden / n_blocks / combine_layer < n_blocks / encoding / latent width / NV <= 4 / Softplus)."""
+    (NV, C, Hf, Wf) and the MLP parameters (any d_hidden / n_blocks / combine_layer < n_blocks / encoding / latent width / NV <= 16 / Softplus)."""
     per = 2 * int(num_freqs) + (1 if include_input else 0)
     d_row = scene.C + 4 * per + 3
     zx = _GenericInputs.apply(scene, xyz, viewdirs, latent, num_freqs, include_input, freq_factor, d_row)

@@ -28,6 +28,11 @@ extern "C" {
 
 #define DINER_ABI_VERSION 6   /* the *_long_f32 entry points were added without a bump: new symbols, no v6 contract changed */
 
+/* Source views a scene may have (DinerScene.nv).  The fused field / training kernels are built for exactly 4 (every shipped config);
+ * the sampler, diner_index_f32 and the generic path (diner_field_inputs_generic_*) take 1 .. DINER_MAX_VIEWS.  Added without an ABI bump:
+ * no struct or signature changed. */
+#define DINER_MAX_VIEWS 16
+
 #define DINER_E_INVALID     (-1)  /* bad argument (null pointer, size, unsupported configuration) */
 #define DINER_E_UNSUPPORTED (-2)  /* configuration outside what the kernels are built for        */
 #define DINER_E_HIP         (-3)  /* a HIP runtime call failed                                     */
@@ -55,7 +60,9 @@ typedef struct DinerScene {
                                                  reference does so that padded sigma values are bit-identical        */
   float img_w, img_h;       /* PixelNeRF.image_shape = [W, H] (pixelnerf.py:50-51)                         */
   float feature_padding;    /* SpatialEncoder.feature_padding (image_encoder.py:59), 32 in the shipped configs */
-  int32_t nv, C, Hf, Wf, Hs, Ws;
+  int32_t nv, C, Hf, Wf, Hs, Ws; /* nv: source views, 1 .. DINER_MAX_VIEWS.  Entries built for the fused kernels (field, scene preparation,
+                               shipped-shape training, diner_train_inputs_f32) return DINER_E_UNSUPPORTED for 5 .. 16 views; every entry
+                               returns DINER_E_INVALID outside [1, DINER_MAX_VIEWS] */
   uint64_t proj_stamp;      /* diner_mlp_stamp() of the handle that wrote latent_proj (set by the caller after
                                diner_scene_prepare_f32).  The field entry points return DINER_E_INVALID when it is not the
                                stamp of the handle they are called with: maps prepared with another (or an older) handle carry
@@ -408,7 +415,7 @@ int diner_mlp_generic_backward_f32(const DinerMlpParams* p, const DinerMlpParams
  * (nv, Hf, Wf, C) channels-last, overwritten, from the first C columns of d_zx (nv, P, d_row); points given as xyz / viewdirs (P, 3). */
 int diner_field_inputs_generic_bwd_f32(const DinerScene* scene, const float* xyz, const float* viewdirs, long long P, int d_row,
                                        const float* d_zx, float* d_latent_cl, void* stream);
-/* The matrix PixelNeRF.forward hands to its MLP (pixelnerf.py:84-128) for any positional encoding / latent width / NV <= 4:
+/* The matrix PixelNeRF.forward hands to its MLP (pixelnerf.py:84-128) for any positional encoding / latent width / NV <= DINER_MAX_VIEWS:
  * zx (nv, P, C + d_in) with d_in = 4 (2 num_freqs + include_input) + 3, rows [latent (bilinear / border) ; poscode(x_c) ; R d ;
  * poscode(depth_nearest - z_c)].  Point source: (rays (NR,8), z (NR,K), K) with P = NR K, or (xyz, viewdirs) (P,3) with rays == NULL. */
 int diner_field_inputs_generic_f32(const DinerScene* scene, const float* rays, const float* z, int K, const float* xyz,
