@@ -21,19 +21,22 @@ per-scene hoist (that, the ragged last shard and the gather are inside the timed
 
 `--gpus N` without a launcher's WORLD_SIZE in the environment starts the N ranks itself (one child process per rank,
 rendezvous on 127.0.0.1 and a free port); the parent's stdout carries exactly rank 0's JSON line and its exit status is
-non-zero when any rank failed.  After the timed region an N-rank run renders one more frame with a fixed seed and rank 0
-compares the gathered frame BIT FOR BIT with the same frame rendered by itself alone (`frame_check`; a ray's noise is keyed by
-(frame seed, index of the ray in the frame), so the frame cannot depend on the number of ranks): the first run on a
-multi-GPU node is a parity test of the sharded path as well.  `dist` in the line records what the process group was:
+non-zero when any rank failed.  With --full, after the timed region an N-rank run renders one more frame with a fixed seed and
+rank 0 compares the gathered frame BIT FOR BIT with the same frame rendered by itself alone (`frame_check`; a ray's noise is
+keyed by (frame seed, index of the ray in the frame), so the frame cannot depend on the number of ranks): the first full run on
+a multi-GPU node is a parity test of the sharded path as well.  `dist` in the line records what the process group was:
 world size, backend, RCCL version, the device of every rank.
 
 `--dump-outputs DIR` writes what the last timed step delivered on rank 0, the (rgb, depth) image, as DIR/rgb.npy (H, W, 3) and
 DIR/depth.npy (H, W) in float32; scene, weights and the frame seeds are fixed, so two builds run with the same arguments can be
 compared output for output.
 
-The JSON line also carries
+A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the line.  Beside the headline the line
+carries
   roofline      the dominant kernel (per-view MLP part, ~86 % of the time): executed MFMA FLOP / HIP-event duration
-                measured in this run, against the dense MFMA peak of the dtype the products are issued in
+                measured in the timed steps, against the dense MFMA peak of the dtype the products are issued in
+
+Everything else the benchmark measures or checks runs only with --full (the --no-* options switch single entries off):
   modes         the same frame in each other arithmetic mode (exact fp32; plain fp16 operands): median of 3 timed frames,
                 each entry with its own roofline figures
   configs       the other single-GPU BASELINE configurations (400x300; 1024x1024 K=192 in f16 and f16x3) and the 800x600
@@ -42,6 +45,11 @@ The JSON line also carries
   cpu_baseline  the CPU oracle (torch restatement of the reference renderer, pinned bit-exact against it) timed on the
                 host cores of the same box: 4096 rays of the same frame, one warm-up at size + 3 timed repeats (rank 0,
                 N = 1 only).
+  encode        PixelNeRF.encode on 4 source images of the frame size (N = 1 only)
+  train         the training step of row f1, forward + backward (N = 1 only)
+  energy        rocm-smi power / clock samples taken by a side process during the timed steps
+  frame_check   N > 1: the sharded frame against the single-rank frame (above)
+A plain run reports these as null (modes / configs: {}).
 """
 import argparse
 import hashlib
@@ -75,15 +83,19 @@ def parse(argv=None):
                     help="Facescape depth range / sigma law (BASELINE configs[4]): znear/zfar 1.0/2.5, white background")
     ap.add_argument("--weak", action="store_true",
                     help="every rank renders its own full frame (weak scaling) instead of sharding one frame")
-    ap.add_argument("--cpu-rays", type=int, default=4096, help="rays of the CPU baseline sample (0 disables)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also measure and check what it does not need: the other arithmetic modes and configs, the CPU "
+                         "baseline, encode, the training step, power samples during the timed steps and (N > 1) the sharded-frame check; "
+                         "the --no-* options below switch single entries of a full run off")
+    ap.add_argument("--cpu-rays", type=int, default=4096, help="rays of the CPU baseline sample of a --full run (0 disables)")
     ap.add_argument("--cpu-repeats", type=int, default=3)
-    ap.add_argument("--no-modes", action="store_true", help="skip the extra passes in the other arithmetic modes")
+    ap.add_argument("--no-modes", action="store_true", help="skip the extra passes in the other arithmetic modes (--full)")
     ap.add_argument("--modes-multi", action="store_true",
-                    help="with N > 1 the extra passes in the other arithmetic modes are OFF by default (a scaling run needs the headline only); "
-                         "this switches them on")
+                    help="with N > 1 the extra passes in the other arithmetic modes are OFF even with --full (a scaling run needs the "
+                         "headline only); this switches them on in a --full run")
     ap.add_argument("--no-configs", action="store_true",
                     help="skip the extra passes of the other single-GPU BASELINE configs (400x300; 1024x1024 K=192 f16 / f16x3; "
-                         "800x600 through the drop-in modules)")
+                         "800x600 through the drop-in modules) in a --full run")
     ap.add_argument("--extra-steps", type=int, default=3, help="timed frames (median) of every modes / configs entry")
     ap.add_argument("--ray-batch", type=int, default=8192, help="rays per launch group (bounds the workspace)")
     ap.add_argument("--via-modules", action="store_true",
@@ -103,12 +115,15 @@ def parse(argv=None):
                          "then exercise RCCL itself: communicator creation, barrier, gather, all-reduce on device tensors)")
     ap.add_argument("--check-frame", dest="check_frame", action="store_true", default=None,
                     help="after the timed region render one frame with a fixed seed sharded and once more on rank 0 alone; compare bit "
-                         "for bit (default: on for N > 1; with one rank the shards are emulated as 8 ray ranges rendered in turn)")
+                         "for bit (default: on for N > 1 with --full, else off; with one rank the shards are emulated as 8 ray ranges "
+                         "rendered in turn)")
     ap.add_argument("--no-check-frame", dest="check_frame", action="store_false")
-    ap.add_argument("--no-train", action="store_true", help="skip the training-step entry (row f1: SB 4 x 4096 rays x 40 samples, forward + backward)")
+    ap.add_argument("--no-train", action="store_true", help="skip the training-step entry of a --full run (row f1: SB 4 x 4096 rays x 40 samples, "
+                                                            "forward + backward)")
     ap.add_argument("--train-steps", type=int, default=7, help="timed training steps (median; >= 5)")
-    ap.add_argument("--no-encode", action="store_true", help="skip the encode_ms entry (PixelNeRF.encode on 4 x 800x600 images, reported beside the metric)")
-    ap.add_argument("--no-power", action="store_true", help="do not sample rocm-smi (power / sclk) during the timed region")
+    ap.add_argument("--no-encode", action="store_true", help="skip the encode_ms entry of a --full run (PixelNeRF.encode on 4 x 800x600 images, "
+                                                             "reported beside the metric)")
+    ap.add_argument("--no-power", action="store_true", help="do not sample rocm-smi (power / sclk) during the timed region of a --full run")
     ap.add_argument("--precision", choices=["f16x3", "fp32", "f16"], default=None,
                     help="MLP GEMM arithmetic of the headline number (default: the library default, f16x3)")
     ap.add_argument("--dump-outputs", default=None, metavar="DIR",
@@ -651,7 +666,7 @@ def main():
         step(i, head)
     wl_head["record_phases"] = bool(multi and not args.weak and not args.via_modules)
     wl_head["mlp"].fallback_launches(reset=True)
-    with PowerSampler(dev.index or 0, enabled=not args.no_power and rank == 0) as psamp:
+    with PowerSampler(dev.index or 0, enabled=args.full and not args.no_power and rank == 0) as psamp:
         elapsed, prof = timed(args.steps, head, args.warmup, profile=True)
     head_fallbacks = wl_head["mlp"].fallback_launches(reset=True)
     wl_head["record_phases"] = False
@@ -670,7 +685,7 @@ def main():
 
     # ---- sharded frame == single-rank frame (bit for bit) -----------------------------------------------------------------------
     frame_check = None
-    do_check = args.check_frame if args.check_frame is not None else (world > 1)
+    do_check = args.check_frame if args.check_frame is not None else (args.full and world > 1)
     if do_check and not args.weak and not args.emulate_shard and not args.via_modules:
         rr = wl_head["render_range"]
         if world > 1 or args.force_dist:
@@ -741,7 +756,7 @@ def main():
 
     # ---- the other arithmetic modes ------------------------------------------------------------------------------------------
     modes = {}
-    if not args.no_modes and (world == 1 or args.modes_multi):
+    if args.full and not args.no_modes and (world == 1 or args.modes_multi):
         for m in (ops.PRECISION_FP32, ops.PRECISION_F16X3, ops.PRECISION_F16):
             if m == head:
                 continue
@@ -780,7 +795,7 @@ def main():
 
     # ---- CPU baseline: the oracle on the host cores of this box (rank 0, N = 1 only) ----
     cpu = None
-    if rank == 0 and world == 1 and args.cpu_rays != 0:
+    if args.full and rank == 0 and world == 1 and args.cpu_rays != 0:
         from oracle import diner_oracle as O
         lat = scene.latent_cl.permute(0, 3, 1, 2).contiguous().cpu()         # the same feature maps, reference layout
         oscene = O.Scene(latent=lat, depths=sc["depths"], depths_std=sc["depths_std"], normals=normals.cpu(),
@@ -833,7 +848,7 @@ def main():
 
     # ---- the other single-GPU configurations of BASELINE.json + the module-level API (N = 1 only) ---------------------
     configs = {}
-    if world == 1 and not args.no_configs and not args.emulate_shard and not args.via_modules \
+    if args.full and world == 1 and not args.no_configs and not args.emulate_shard and not args.via_modules \
             and (W, H, K, bool(args.facescape)) == (800, 600, 128, False):
         nx = max(1, args.extra_steps)
         plan = {
@@ -862,7 +877,7 @@ def main():
 
     # ---- encode, reported beside the metric ("encode excluded, reported separately"; pixelnerf.py:35-53) ------------------------
     encode = None
-    if world == 1 and not args.no_encode and not args.emulate_shard:
+    if args.full and world == 1 and not args.no_encode and not args.emulate_shard:
         try:
             encode = encode_entry(torch, ops, dev, msd, W, H, make_scene, build_modules)
         except Exception as e:      # (a trunk that does not run on this box must not cost the headline)
@@ -871,7 +886,7 @@ def main():
 
     # ---- the training step, row f1 (N = 1 only; DINER.calc_losses, diner.py:217-290 at configs/train_dtu.yaml:16,52-63) -----------------
     train_line = None
-    if world == 1 and not args.no_train and not args.emulate_shard:
+    if args.full and world == 1 and not args.no_train and not args.emulate_shard:
         del wl_head, step, out, frame, scene
         torch.cuda.empty_cache()
         train_line = train_entry(torch, ops, dev, msd, make_scene, build_modules, max(5, args.train_steps))
@@ -922,7 +937,7 @@ def main():
             "backend": backend, "ranks_share_gpu": bool(shared and world > 1),
             "fallback_launches": head_fallbacks,
             # (N > 1: rank 0 samples ITS device only -- power_w / sclk_mhz are that device's, the energy per ray of the job is not computed)
-            "energy": psamp.summary(elapsed, rays_per_step * args.steps if world == 1 else 0),
+            "energy": psamp.summary(elapsed, rays_per_step * args.steps if world == 1 else 0) if args.full else None,
             "encode": encode,
             "train": train_line,
             "dist": dist_info, "frame_check": frame_check,

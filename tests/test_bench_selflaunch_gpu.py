@@ -26,7 +26,7 @@ def test_bench_launches_its_own_ranks(n):
     import torch
     if n > 2 and torch.cuda.device_count() < n:             # (with this test's process that would be n + 1 processes on one GPU)
         pytest.skip(f"needs {n} GPUs, found {torch.cuda.device_count()}")
-    rc, out, err = _run(["--gpus", str(n), "--steps", "2", "--warmup", "1"])
+    rc, out, err = _run(["--gpus", str(n), "--steps", "2", "--warmup", "1", "--full"])     # --full: frame_check
     assert rc == 0, err[-3000:]
     lines = [l for l in out.splitlines() if l.strip()]
     assert len(lines) == 1, f"stdout must carry exactly the JSON line, got {len(lines)} lines:\n{out[:2000]}"
@@ -46,7 +46,7 @@ def test_bench_launches_its_own_ranks(n):
     assert b["frame_ms"] == pytest.approx(line["ms_per_step"], rel=1e-3)
     assert 0 < b["scaling_efficiency_vs_emulated"] <= 1.25 and b["shard_ms_min"] <= b["shard_ms_max"]
     assert b["slowest_rank_hoist_plus_shard_ms"] <= b["frame_ms"] * 1.25       # (medians of 2 frames of ranks that time-slice one GPU)
-    assert line["modes"] == {}                                            # off by default for N > 1 (a scaling run needs the headline only)
+    assert line["modes"] == {}                                            # off even with --full for N > 1 (a scaling run needs the headline only)
     fc = line["frame_check"]
     assert fc["bit_equal"] is True and fc["sha256_sharded"] == fc["sha256_single_rank"] and fc["max_abs_diff"] == 0.0
     if torch.cuda.device_count() < n:                                     # a one-GPU box: the two ranks share the GPU
@@ -70,3 +70,24 @@ def test_failing_rank_gives_nonzero_status():
     """A rank that dies takes the run down with a non-zero status and no JSON line (an impossible frame: zero width)."""
     rc, out, err = _run(["--gpus", "2", "--steps", "1", "--warmup", "0", "--width", "0", "--height", "8"], timeout=600)
     assert rc != 0 and not out.strip()
+
+
+def test_plain_run_measures_the_headline_only():
+    """Without --full the line carries the headline and its roofline; the other modes, configs, CPU baseline, encode, training step,
+    power samples and frame check are left to --full.  With --full the other arithmetic modes ride in the line again."""
+    small = ["--gpus", "1", "--steps", "1", "--warmup", "1", "--width", "200", "--height", "152"]
+    rc, out, err = _run(small)
+    assert rc == 0, err[-3000:]
+    lines = [l for l in out.splitlines() if l.strip()]
+    assert len(lines) == 1
+    line = json.loads(lines[0])
+    assert line["value"] > 0 and line["unit"] == "rays/s" and line["higher_is_better"] is True and line["steps"] == 1
+    assert line["roofline"]["achieved"] > 0 and line["fallback_launches"] == 0
+    assert line["modes"] == {} and line["configs"] == {}
+    for k in ("cpu_baseline", "encode", "train", "energy", "frame_check"):
+        assert line[k] is None, k
+    rc, out, err = _run(small + ["--full", "--cpu-rays", "0", "--no-train", "--no-encode", "--no-power"])
+    assert rc == 0, err[-3000:]
+    line = json.loads(out.strip().splitlines()[-1])
+    assert sorted(line["modes"]) == ["f16", "fp32"] and all(e["rays_per_s"] > 0 for e in line["modes"].values())
+    assert line["energy"] is not None and line["frame_check"] is None

@@ -9,7 +9,7 @@
 #   train-prof [rays] [obj]    rocprofv3 kernel trace of the training step (tools/prof_train.sh)
 #   train-pmc [rays] [obj]     HBM bytes / MfmaUtil per kernel of the training step (tools/pmc_train.sh)
 #   l512-prof [rows]           phase timer of lin512_body (needs libdiner_hip_l512prof.so: build_variant('l512prof', ['DINER_L512_PROF']))
-#   bench [bench args]         the driver's command (default --gpus 1 --steps 20 --warmup 5) -> gpurun_out/bench_line.json + a digest on stdout
+#   bench [bench args]         bench.py (default --gpus 1 --steps 20 --warmup 5 --full) -> bench_line.json in the output folder + a digest on stdout
 #   profile <tag> [bench args] rocprofv3 stats + PMC passes of the bench (tools/profile_round.sh)
 #   smoke                      __graft_entry__.smoke()
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}" || exit 1
@@ -41,7 +41,7 @@ case "$job" in
     DINER_AMD_LIB=$PWD/diner_amd/libdiner_hip_l512prof.so timeout 600 python tools/prof_l512.py "$@" > gpurun_out/prof_l512.log 2>&1
     grep -v amdgpu.ids gpurun_out/prof_l512.log ;;
   bench)
-    [ $# -eq 0 ] && set -- --gpus 1 --steps 20 --warmup 5
+    [ $# -eq 0 ] && set -- --gpus 1 --steps 20 --warmup 5 --full
     ( time python bench.py "$@" ) > gpurun_out/bench_line.json 2> gpurun_out/bench_stderr.log; echo "rc=$?" >> gpurun_out/bench_stderr.log
     tail -5 gpurun_out/bench_stderr.log
     python - <<'PY'

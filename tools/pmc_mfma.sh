@@ -2,7 +2,7 @@
 # MFMA utilisation + effective clock of the field kernels: PMC pass (kernel-trace only) + kernel durations.
 cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
 OUT=gpurun_out/${1:-pmc_mfma}; mkdir -p $OUT
-CMD="python bench.py --steps 1 --warmup 1 --cpu-rays 0 --width 256 --height 256"
+CMD="python bench.py --steps 1 --warmup 1 --full --cpu-rays 0 --width 256 --height 256"
 rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_BUSY_CYCLES SQ_WAVE_CYCLES --output-format csv -d $OUT/p -o pmc -- $CMD > $OUT/p.log 2>&1
 python - <<PY
 import csv, glob, collections
