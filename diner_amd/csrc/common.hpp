@@ -142,6 +142,14 @@ __device__ __forceinline__ float sin_posenc(float x) {
   return (k & 2) ? -v : v;
 }
 
+// torchvision save_image's quantisation of one value: uint8(clamp(v * 255 + 0.5, 0, 255)) in fp32, NaN -> 0 (k_quantize_rgb and the
+// fp32 route of the image metrics, which must score a render exactly as the PNG it would be written to)
+__device__ __forceinline__ unsigned char quantize_u8(float x) {
+  float v = __fadd_rn(__fmul_rn(x, 255.0f), 0.5f);
+  v = fminf(fmaxf(v, 0.0f), 255.0f);                                     // NaN -> 0 like clamp_ + the uint8 cast of 0
+  return (unsigned char)(v != v ? 0.0f : v);
+}
+
 // wave-level helpers (64 lanes)
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

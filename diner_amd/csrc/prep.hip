@@ -112,11 +112,7 @@ __global__ void k_gen_rays(RayCams cams, int B, int W, long long ray0, long long
 __global__ void k_quantize_rgb(const float* __restrict__ img, long long HW, unsigned char* __restrict__ out) {
   for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < HW; i += (long long)gridDim.x * blockDim.x) {
 #pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      float v = __fadd_rn(__fmul_rn(img[(size_t)c * HW + i], 255.0f), 0.5f);
-      v = fminf(fmaxf(v, 0.0f), 255.0f);                                   // NaN -> 0 like clamp_ + the uint8 cast of 0
-      out[i * 3 + c] = (unsigned char)(v != v ? 0.0f : v);
-    }
+    for (int c = 0; c < 3; ++c) out[i * 3 + c] = quantize_u8(img[(size_t)c * HW + i]);
   }
 }
 

@@ -1,0 +1,185 @@
+"""Evaluation on the device: the counterparts of DINER.create_prediction_folder (diner.py:99-136) and of the reference's
+evaluate_folder (eval_suite.py:44-118), with the per-image scores computed by the HIP kernels of diner_amd.metrics.
+
+    python -m diner_amd.evaluate --eval_path DIR      # scores DIR/visualizations, writes the reports into DIR
+
+write_prediction_folder renders the sample dicts of diner_amd.datasets and writes <stem>-pred.png, -depth.png, -ref.png and -gt.png
+per sample (the reference's suffixes); evaluate_folder pairs the -gt / -pred files of a folder, scores them on the device and writes
+average_scores.json, detailed_report.json and examples.png.  LPIPS needs network weights that are not part of this project: it is
+computed by a caller-supplied `lpips_fn` or by the `lpips` package when that is importable, and otherwise left out with a warning."""
+import argparse
+import json
+import os
+import warnings
+from collections import defaultdict
+from pathlib import Path
+
+import numpy as np
+import torch
+
+from .png import read_png, write_png
+
+PRED_SUFFIX = "-pred.png"
+GT_SUFFIX = "-gt.png"
+REF_SUFFIX = "-ref.png"
+DEPTH_SUFFIX = "-depth.png"
+AVERAGE_SCORE_FILENAME = "average_scores.json"
+REPORT_DETAIL_FILENAME = "detailed_report.json"
+EXAMPLE_PLOT_FILENAME = "examples.png"
+N_EXAMPLE_PLOTS = 5
+BATCH = 16                       # same-sized pairs scored per kernel call
+
+
+def _hip_device(device):
+    if device is None:
+        if not torch.cuda.is_available():
+            raise RuntimeError("diner_amd.evaluate: no HIP device; the metrics run on the device and there is no CPU fallback")
+        return torch.device("cuda", torch.cuda.current_device())
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError(f"diner_amd.evaluate: device {device} is not a HIP device; there is no CPU fallback")
+    if device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    return device
+
+
+@torch.no_grad()
+def write_prediction_folder(nerf, renderer, batches, outdir, znear, zfar, ray_batch_size=8192):
+    """Render every target view of `batches` (collated sample dicts of diner_amd.datasets) with `nerf` / `renderer` and write
+    <sample_name>{-pred,-depth,-ref,-gt}.png into `outdir`: the render and its colour-mapped depth, the source views side by side and
+    the target, each quantised as save_image does.  Returns {"sample_name": [...], "l1", "l2", "psnr", "ssim": float64 (N,)} -- the
+    scores of the renders against their targets, computed on the device from the fp32 tensors (not from the files)."""
+    from .datasets import encode_args
+    from .imageio import depth_to_uint8, to_uint8
+    from .metrics import KEYS, image_metrics
+    from .render import predict_image
+    os.makedirs(outdir, exist_ok=True)
+    dev = next(nerf.parameters()).device
+    names, scores = [], defaultdict(list)
+    for batch in batches:
+        nerf.encode(**encode_args(batch, dev))
+        gt = batch["target_rgb"].to(dev)
+        H, W = gt.shape[-2:]
+        rgb, depth = predict_image(nerf, renderer, batch["target_extrinsics"].to(dev), batch["target_intrinsics"].to(dev), W, H,
+                                   znear, zfar, ray_batch_size=ray_batch_size)
+        src = batch["src_rgbs"].to(dev)
+        for i, stem in enumerate(batch["sample_name"]):
+            write_png(os.path.join(outdir, stem + PRED_SUFFIX), to_uint8(rgb[i]))
+            write_png(os.path.join(outdir, stem + DEPTH_SUFFIX), depth_to_uint8(depth[i]))
+            write_png(os.path.join(outdir, stem + REF_SUFFIX), to_uint8(torch.cat(src[i].unbind(0), dim=-1)))
+            write_png(os.path.join(outdir, stem + GT_SUFFIX), to_uint8(gt[i]))
+            names.append(stem)
+        s = image_metrics(rgb, gt)
+        for k in KEYS:
+            scores[k].append(s[k])
+    out = {"sample_name": names}
+    for k in KEYS:
+        out[k] = torch.cat(scores[k]) if scores[k] else torch.empty(0, dtype=torch.float64)
+    return out
+
+
+def _lpips_from_package(device):
+    try:
+        import lpips
+    except ImportError as e:
+        return None, f"the lpips package is not importable ({e})"
+    try:
+        return lpips.LPIPS(net="vgg").to(device=device), None
+    except Exception as e:        # the package fetches its VGG weights on first use
+        return None, f"lpips.LPIPS(net='vgg') could not be built ({type(e).__name__}: {e})"
+
+
+@torch.no_grad()
+def evaluate_folder(source_dir, outdir, device=None, pred_suffix=PRED_SUFFIX, gt_suffix=GT_SUFFIX, ref_suffix=REF_SUFFIX,
+                    depth_suffix=DEPTH_SUFFIX, show_tqdm=False, lpips_fn=None):
+    """Score every <x>{gt_suffix} / <x>{pred_suffix} pair of `source_dir` (sorted by file name) on the HIP device `device` (None:
+    the current one) and write AVERAGE_SCORE_FILENAME, REPORT_DETAIL_FILENAME and EXAMPLE_PLOT_FILENAME into `outdir`.  Returns the
+    averages {ssim, psnr, l2, l1[, lpips]}; an average over an infinite psnr stays inf.  `lpips_fn(pred, gt)` receives (1,3,H,W)
+    float32 device tensors in [-1, 1], as the reference calls lpips_vgg; without it the lpips package is used when importable."""
+    from .metrics import image_metrics
+    device = _hip_device(device)
+    outdir = Path(outdir)
+    os.makedirs(outdir, exist_ok=True)
+    source_dir = Path(source_dir)
+    gt_paths = [p for p in sorted(source_dir.iterdir()) if p.name.endswith(gt_suffix)]
+    pred_paths = [p.parent / p.name.replace(gt_suffix, pred_suffix) for p in gt_paths]
+    if not gt_paths:
+        raise FileNotFoundError(f"evaluate_folder: no *{gt_suffix} files in {source_dir}")
+
+    lpips_warn = None
+    if lpips_fn is None:
+        lpips_fn, lpips_warn = _lpips_from_package(device)
+    if lpips_fn is None:
+        warnings.warn(f"evaluate_folder: lpips is left out of the scores: {lpips_warn}; pass lpips_fn to include it")
+
+    n = len(gt_paths)
+    per = {k: [None] * n for k in ("ssim", "psnr", "l2", "l1")}
+    lp = [None] * n
+    groups = defaultdict(list)                  # (H, W, gt channels) -> indices, so that each kernel call holds one size
+    imgs = []
+    it = range(n)
+    if show_tqdm:
+        try:
+            import tqdm
+            it = tqdm.tqdm(it, total=n, mininterval=30.)
+        except ImportError:
+            pass
+    for i in it:
+        gt = read_png(gt_paths[i])
+        pred = read_png(pred_paths[i])
+        if gt.ndim == 2 or pred.ndim == 2 or pred.shape[2] != 3:
+            raise ValueError(f"evaluate_folder: {pred_paths[i].name} / {gt_paths[i].name}: need an RGB pred and an RGB(A) gt")
+        if pred.shape[:2] != gt.shape[:2]:
+            raise ValueError(f"evaluate_folder: {pred_paths[i].name} {pred.shape} and {gt_paths[i].name} {gt.shape} differ in size")
+        imgs.append((pred, gt))
+        groups[gt.shape].append(i)
+        if lpips_fn is not None:
+            to = lambda a: (torch.from_numpy(a[..., :3].astype(np.float32) / 255.0).permute(2, 0, 1)[None] * 2.0 - 1.0).to(device)  # noqa: E731
+            lp[i] = float(torch.as_tensor(lpips_fn(to(pred), to(gt))).flatten().cpu().item())
+    with torch.cuda.device(device):
+        for idx in groups.values():
+            for b in range(0, len(idx), BATCH):
+                chunk = idx[b:b + BATCH]
+                pred = torch.from_numpy(np.stack([imgs[i][0] for i in chunk])).to(device)
+                gt = torch.from_numpy(np.stack([imgs[i][1] for i in chunk])).to(device)
+                s = {k: v.cpu().tolist() for k, v in image_metrics(pred, gt).items()}
+                for j, i in enumerate(chunk):
+                    for k in per:
+                        per[k][i] = s[k][j]
+    scores = dict(per)
+    if lpips_fn is not None:
+        scores["lpips"] = lp
+
+    avg = {k: float(np.mean(v)) for k, v in scores.items()}
+    with open(outdir / AVERAGE_SCORE_FILENAME, "w") as f:
+        json.dump(avg, f, indent="\t")
+    report = [dict(path=str(pred_paths[i]), **{k: float(v[i]) for k, v in scores.items()}) for i in range(n)]
+    with open(outdir / REPORT_DETAIL_FILENAME, "w") as f:
+        json.dump(report, f, indent="\t")
+
+    rows = []
+    for i in np.linspace(0, n - 1, N_EXAMPLE_PLOTS).astype(int):
+        pp = pred_paths[i]
+        pred = imgs[i][0]
+
+        def side(suffix):
+            p = pp.parent / pp.name.replace(pred_suffix, suffix)
+            return read_png(p)[..., :3] if p.exists() else np.zeros_like(pred)
+
+        ref, gt, depth = side(ref_suffix), imgs[i][1][..., :3], side(depth_suffix)
+        nref = max(1, ref.shape[1] // pred.shape[1])
+        rows.append(np.concatenate([*np.hsplit(ref, nref), gt, pred, depth], axis=1))
+    write_png(outdir / EXAMPLE_PLOT_FILENAME, np.ascontiguousarray(np.concatenate(rows, axis=0)))
+    return avg
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description="Score the predictions of DIR/visualizations on the device; reports go to DIR.")
+    ap.add_argument("--eval_path", type=Path, required=True)
+    args = ap.parse_args(argv)
+    avg = evaluate_folder(args.eval_path / "visualizations", args.eval_path, show_tqdm=True)
+    print(json.dumps(avg, indent="\t"))
+
+
+if __name__ == "__main__":
+    main()

@@ -235,3 +235,67 @@ def as_encoded(latent):
     that the timed step sees the latent the way a real encoder hands it over."""
     import torch as _t
     return latent.flatten(0, 1).contiguous(memory_format=_t.channels_last).view(latent.shape)
+
+
+# ---- image pairs for the image-metric tests (G24, tools/make_golden_metrics.py) -----------------------------------------------
+# (kind, H, W, seed) of every pair G24 pins; metric_pair() regenerates the bytes (numpy only, no extension needed)
+METRIC_CASES = (
+    ("uniform", 7, 7, 1), ("near", 7, 7, 2), ("uniform", 7, 40, 3), ("constant", 7, 40, 4), ("uniform", 37, 53, 5),
+    ("smooth", 37, 53, 6), ("identical", 37, 53, 7), ("object", 128, 96, 8), ("rgba", 128, 96, 9), ("near", 128, 96, 10),
+    ("constant", 128, 96, 11), ("smooth", 256, 320, 12), ("object", 600, 800, 13),
+)
+
+
+def metric_pair(kind, H, W, seed):
+    """A seeded (pred (H,W,3), gt (H,W,3 or 4)) uint8 pair.  kind: "uniform" (independent uniform bytes), "smooth" (smooth colour
+    field, pred = gt + noise), "object" (a coloured disc on a white background, pred shifted and noisy), "identical", "constant"
+    (two flat colours), "rgba" (smooth pair, gt with a random alpha channel), "near" (pred = gt, a few pixels one level off)."""
+    import numpy as np
+    rs = np.random.RandomState(seed)
+
+    def smooth():
+        yy, xx = np.mgrid[0:H, 0:W].astype(np.float64)
+        f = rs.uniform(0.02, 0.2, size=(3, 2))
+        ph = rs.uniform(0, 6.28, size=3)
+        img = np.stack([0.5 + 0.45 * np.sin(f[c, 0] * yy + f[c, 1] * xx + ph[c]) for c in range(3)], -1)
+        return np.clip(np.round(img * 255), 0, 255).astype(np.uint8)
+
+    def noisy(img, std):
+        return np.clip(np.round(img.astype(np.float64) + rs.normal(0, std, img.shape)), 0, 255).astype(np.uint8)
+
+    if kind == "uniform":
+        return rs.randint(0, 256, (H, W, 3)).astype(np.uint8), rs.randint(0, 256, (H, W, 3)).astype(np.uint8)
+    if kind == "identical":
+        g = rs.randint(0, 256, (H, W, 3)).astype(np.uint8)
+        return g.copy(), g
+    if kind == "constant":
+        a, b = rs.randint(0, 256, 3), rs.randint(0, 256, 3)
+        return np.broadcast_to(a.astype(np.uint8), (H, W, 3)).copy(), np.broadcast_to(b.astype(np.uint8), (H, W, 3)).copy()
+    if kind == "smooth":
+        g = smooth()
+        return noisy(g, 6.0), g
+    if kind == "rgba":
+        g = smooth()
+        alpha = rs.randint(0, 256, (H, W, 1)).astype(np.uint8)
+        return noisy(g, 10.0), np.concatenate([g, alpha], -1)
+
+    if kind == "object":
+        yy, xx = np.mgrid[0:H, 0:W]
+
+        def disc(cy, cx):
+            img = np.full((H, W, 3), 255, np.uint8)
+            m = (yy - cy) ** 2 + (xx - cx) ** 2 < (0.3 * min(H, W)) ** 2
+            img[m] = rs.randint(0, 200, 3)
+            return img
+
+        cy, cx = H / 2, W / 2
+        g = disc(cy, cx)
+        return noisy(disc(cy + 0.02 * H, cx - 0.02 * W), 4.0), g
+    if kind == "near":
+        g = rs.randint(0, 256, (H, W, 3)).astype(np.uint8)
+        p = g.astype(np.int16)
+        n = max(1, H * W // 200)
+        idx = rs.randint(0, H * W * 3, n)
+        p.reshape(-1)[idx] += np.where(p.reshape(-1)[idx] == 255, -1, 1)
+        return p.astype(np.uint8), g
+    raise ValueError(f"metric_pair: unknown kind {kind!r}")

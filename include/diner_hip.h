@@ -422,6 +422,22 @@ int diner_field_inputs_generic_f32(const DinerScene* scene, const float* rays, c
                                    const float* viewdirs, long long P, int num_freqs, int include_input, float freq_factor,
                                    float* zx, void* stream);
 
+/* ---- image-quality metrics (the reference's evaluate_folder, eval_suite.py:62-68) ----------------------------------------------
+ * For N pairs of H x W images (H, W >= 7) writes out (N, 4) float64 = {l1, l2, psnr, ssim} per pair, in device memory:
+ * a pixel value is the float32 fl32(k) / 255; l1 = mean |fl32(p - g)|, l2 = mean fl32(fl32(p - g)^2) (both summed in double),
+ * psnr = 10 log10(1 / l2) (+inf when l2 == 0), ssim = skimage structural_similarity(channel_axis=-1, data_range=1) with its defaults
+ * (7x7 uniform window, K1 0.01, K2 0.03, sample covariance, map cropped by 3 px, mean over the channels; moments and the map in double).
+ * No floating-point atomics: the scores are bit-identical across runs, batch positions and the two routes.
+ *   _u8:  pred (N,H,W,pred_c) with pred_c == 3, gt (N,H,W,gt_c) with gt_c 3 or 4 (alpha dropped), uint8;
+ *   _f32: pred, gt (N,3,H,W) fp32, quantised in-kernel exactly as diner_quantize_rgb_u8 does (save_image).
+ * workspace: diner_image_metrics_workspace_bytes(N, H, W) bytes of device memory (0 for arguments the entries refuse).
+ * Bad arguments (null pointers, N < 1, H or W < 7, channel counts) return DINER_E_INVALID before any device work.
+ * Added without an ABI bump: new symbols, no existing contract changed. */
+size_t diner_image_metrics_workspace_bytes(int N, int H, int W);
+int diner_image_metrics_u8(const unsigned char* pred, const unsigned char* gt, int N, int H, int W, int pred_c, int gt_c,
+                           void* workspace, double* out, void* stream);
+int diner_image_metrics_f32(const float* pred, const float* gt, int N, int H, int W, void* workspace, double* out, void* stream);
+
 /* ---- measurement aid (bench.py): per-kernel durations of the two field kernels ------------------
  * With profiling enabled every field call brackets k_field_pre / k_field_post with HIP events on the
  * launch stream; diner_profile_collect waits for them, returns the summed durations (ms), the number
