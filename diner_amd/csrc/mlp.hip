@@ -46,8 +46,8 @@ struct DinerMlpImpl {
   float* b_pre;    // lin_in, then per block b<3: fc_0, fc_1  -> 7 x 512
   float* b_post;   // per block b=3,4: fc_0, fc_1 -> 4 x 512, then lin_out (4, padded to 16)
   // split-precision (f16x3 / f16) copies for the feature-sliced kernels of mlp_h3n.hip: fp16 hi/lo fragments and biases, x16
-  float* hn_w;     // n-split packing of lin_in + the 6 per-view layers + the 4 post layers
-  float* hn_w_out; // lin_out fragments
+  _Float16* hn_w;     // lin_in + the 6 per-view layers + the 4 post layers in the four-wave and the eight-wave order (mlp_h3n.hip, WeightLayout)
+  _Float16* hn_w_out; // lin_out fragments, then the fp32 pack of the vector-ALU lin_out
   float* hn_b_pre; // 7 x 512, x16
   float* hn_b_post;// 4 x 512 x16, then lin_out bias (scale 1, padded to 16)
   float* wmax_dev; // max |parameter| (device scalar, reduced at pack time)
@@ -84,12 +84,12 @@ static int mlp_fits(const DinerMlpImpl* m, bool* fits) {
 }
 
 // mlp_h3n.hip
-int h3n_alloc(float** w, float** w_out, float** b_pre, float** b_post);
-int h3n_pack(const DinerMlpParams* p, hipStream_t stream, float* w, float* w_out, float* b_pre, float* b_post, bool train_only);
+int h3n_alloc(_Float16** w, _Float16** w_out, float** b_pre, float** b_post);
+int h3n_pack(const DinerMlpParams* p, hipStream_t stream, _Float16* w, _Float16* w_out, float* b_pre, float* b_post, bool train_only);
 int h3n_set_attributes();
-void h3n_launch_pre(const SceneDev& sc, const FieldArgs& fa, const float* w, const float* b, int grid, bool split,
+void h3n_launch_pre(const SceneDev& sc, const FieldArgs& fa, const _Float16* w, const float* b, int grid, bool split,
                     unsigned* tile_counter, hipStream_t stream, const SaveActs* sv = nullptr);
-void h3n_launch_post(const PostArgs& pa, const float* w, const float* w_out, int grid, bool split, unsigned* tile_counter,
+void h3n_launch_post(const PostArgs& pa, const _Float16* w, const _Float16* w_out, int grid, bool split, unsigned* tile_counter,
                      hipStream_t stream, const SaveActs* sv = nullptr);
 
 // ------------------------------------------------------------------------------------------------------
@@ -599,7 +599,7 @@ __global__ void k_absmax(const float* __restrict__ x, long long n, float* __rest
   }
 }
 
-// fp32 projected maps -> fp16 in the plain-fp16 kernel's channel order (mlp_h3n.hip, GatherSideH): position 128 w + 32 mp + 8 q + 4 t + i
+// fp32 projected maps -> fp16 in the plain-fp16 kernel's channel order (mlp_h3n.hip, Gather8): position 128 w + 32 mp + 8 q + 4 t + i
 // of a texel's 512 halves holds channel 128 w + 16 (2 mp + t) + 4 q + i.  One thread per 8 output halves (two f32x4 reads 64 B apart).
 __global__ __launch_bounds__(256) void k_proj_to_f16(const float* __restrict__ src, long long rows, _Float16* __restrict__ dst) {
   typedef _Float16 h8v __attribute__((ext_vector_type(8)));
@@ -877,10 +877,10 @@ extern "C" int diner_mlp_update(DinerMlp* m, const DinerMlpParams* p, int flags,
 
 extern "C" int diner_mlp_destroy(DinerMlp* m) {
   if (!m) return 0;
-  float* bufs[] = {m->impl.w_hoist, m->impl.w_pre, m->impl.w_post, m->impl.b_hoist, m->impl.b_pre, m->impl.b_post,
-                   m->impl.hn_w, m->impl.hn_w_out, m->impl.hn_b_pre, m->impl.hn_b_post, m->impl.wmax_dev,
-                   (float*)m->impl.fallback_dev};
-  for (float* b : bufs)
+  void* bufs[] = {m->impl.w_hoist, m->impl.w_pre, m->impl.w_post, m->impl.b_hoist, m->impl.b_pre, m->impl.b_post,
+                  m->impl.hn_w, m->impl.hn_w_out, m->impl.hn_b_pre, m->impl.hn_b_post, m->impl.wmax_dev,
+                  m->impl.fallback_dev};
+  for (void* b : bufs)
     if (b) hipFree(b);
   delete m;
   return 0;

@@ -1,6 +1,7 @@
-// fp16-operand field kernels (DINER_PRECISION_F16X3: split products, three MFMAs per fp32 product; DINER_PRECISION_F16: plain
-// fp16 operands), feature-sliced ("n-split"): wave w owns output features [128 w, 128 w + 128) for ALL 64 columns of the
-// workgroup (4 views x 16 points).
+// fp16-operand field kernels, feature-sliced ("n-split").  DINER_PRECISION_F16X3 (split products, three MFMAs per fp32 product) runs on
+// four waves per workgroup: k_field_pre_h3n / k_field_post_h3n, described here; DINER_PRECISION_F16 (plain fp16 operands, one MFMA per
+// product) on eight: k_field_pre_h8 / k_field_post_h8, namespace w8 below.  Four waves: wave w owns output features
+// [128 w, 128 w + 128) for ALL 64 columns of the workgroup (4 views x 16 points).
 //   * every fp32 product a*w is evaluated as a_hi*w_hi + a_hi*w_lo + a_lo*w_hi (a = a_hi + a_lo, w = w_hi + w_lo, fp16 parts)
 //     on v_mfma_f32_16x16x32_f16 with fp32 accumulation; the network runs at a power-of-two scale (weights, biases x16,
 //     accumulators hold 16x the activations, the fp32 -> (hi, lo) conversion of every B operand folds the exact 1/16 back
@@ -158,27 +159,22 @@ struct QueueMap {
                                       // queue belongs to pass e / per_pass -- all rays' near segments first, then the far ones (1: as before)
   __host__ static QueueMap make(long long n_tiles, int K, bool rays) {
     QueueMap q{8, 1, 1, 0, 1, 0, 8};
-    // measurement aids (round 5, BASELINE configs[4]: K = 192 -> 12 segments): DINER_QMAP_PASSES = p splits the segments into p passes
-    // (12 = 2 x 6: a queue then holds 0.75 segments at a time instead of 1.5), DINER_QMAP_RMUL = k takes k times the rays per group
-    static const int env_passes = [] { const char* e = getenv("DINER_QMAP_PASSES"); return e ? atoi(e) : 0; }();
-    static const int env_rmul = [] { const char* e = getenv("DINER_QMAP_RMUL"); return e ? atoi(e) : 1; }();
     if (rays && K >= 16 && K % 16 == 0 && K / 16 <= 4096) {
       unsigned S_all = (unsigned)(K / 16);
-      // default: more than 8 segments per ray are dealt in passes of the largest power of two <= 8 (and >= 4) that divides them -- K = 192:
+      // more than 8 segments per ray are dealt in passes of the largest power of two <= 8 (and >= 4) that divides them -- K = 192:
       // 3 passes of 4 segments, every queue then holds ONE (segment, ray phase) at a time instead of 1.5 segments: per-view kernel 23.1-23.4
       // -> 22.5-22.8 ms per launch at 1024^2 in f16x3 (passes 2 / 4 / 6 / 12: 22.9-23.2; profiles/r05_qmap_passes_ab.txt); K = 128 (8 segments)
       // stays one pass (2 / 4 / 8 passes measured 0.4-3.7 % slower)
-      unsigned def_passes = 1;
+      unsigned passes = 1;
       if (S_all > 8)
         for (unsigned sp = 8; sp >= 4; sp >>= 1)
-          if (S_all % sp == 0) { def_passes = S_all / sp; break; }
-      unsigned passes = env_passes >= 1 && S_all % (unsigned)env_passes == 0 ? (unsigned)env_passes : def_passes;
+          if (S_all % sp == 0) { passes = S_all / sp; break; }
       q.S_all = S_all;
       q.passes = passes;
       q.S = S_all / passes;
       unsigned g = q.S & (0u - q.S);
       g = g > 8 ? 8 : g;
-      q.R = 8 / g * (env_rmul > 1 ? (unsigned)env_rmul : 1u);
+      q.R = 8 / g;
       q.m = q.S * q.R / 8;
     }
     const unsigned long long n_rays = ((unsigned long long)n_tiles + q.S_all - 1) / q.S_all;
@@ -198,7 +194,6 @@ struct Args {
   FieldArgs fa;
   const _Float16* w;       // n-split packed weights: lin_in, then per block b<3: fc_0, fc_1
   const _Float16* w8;      // the same seven layers in the 8-wave kernel's order (k_field_pre_h8; hi plane only), or null
-  const _Float16* w8x;     // ... with hi and lo planes (k_field_pre_h8x, the f16x3 arithmetic on eight waves), or null
   const float* b;          // biases x16: lin_in, then per block: fc_0, fc_1  (7 x 512)
   unsigned long long* prof;   // DINER_HN_PROF builds: 32 phase counters (shader clocks summed over waves), else unused
   unsigned* tile_counter;     // 8 counters (one per XCD queue), zeroed per launch: see TileQueue
@@ -321,6 +316,7 @@ struct Prof {
 };
 
 // packed weights of one layer with KT k32 blocks: [w 4][t KT][mo 8][hl 2][lane 64][8]
+constexpr size_t kLinInHalfs = (size_t)4 * 2 * 8192, kLayerHalfs = (size_t)4 * 16 * 8192;      // lin_in (KT = 2), a 512-wide layer (KT = 16)
 __device__ __forceinline__ const h8* wfrag(const _Float16* layer, int KT, int wave, int t, int mo, int hl, int lane) {
   return reinterpret_cast<const h8*>(layer) + ((((size_t)wave * KT + t) * 8 + mo) * 2 + hl) * 64 + lane;
 }
@@ -357,7 +353,6 @@ struct NoSide {
 //   * B fragments (hi, lo of one column group, shared) live in one buffer: group g of the next k32 block is re-read
 //     right after its last use in the second half (576 MFMA cycles before the next use);
 //   * the side task gets a slot per quarter-step, so its VALU / VMEM work is spread between the MFMAs.
-// LO = false: plain fp16 operands (hi parts only, one MFMA per product; diner_set_precision(3)).
 #ifndef DINER_HN_EARLYA
 #define DINER_HN_EARLYA 1
 #endif
@@ -366,7 +361,7 @@ struct NoSide {
 // while the conversion runs -- neutral there (61.58 M vs 61.71 M clocks per wave); in the post kernel the same costs 5 % (the
 // loads issued in front of the barrier hold the wave for ~4 k clocks, profiles/r02c_phase_timer_post_kernel.txt), so not there.  (On the fc_1 GEMMs every way of doing the same -- ring started ahead of the gather / no-gather branch, or
 // only in the no-gather arm with its own publish -- made the allocator spill 30-130 registers inside the GEMM: not done.)
-template <int KT, int R, bool LO>
+template <int KT, int R>
 struct ARing {
   typedef const __attribute__((address_space(1))) char* gptr;      // stays a global (not flat) access through the asm
   h8 a[R][8];                            // half-step ring (static indices after unrolling)
@@ -381,7 +376,7 @@ struct ARing {
     asm volatile("" : "+s"(abase));
 #pragma unroll
     for (int i = 2 * pair; i < 2 * pair + 2; ++i)
-      if (LO || (i & 1) == 0) dst[i] = *(const __attribute__((address_space(1))) h8*)(abase + avoff + (i * 1024 - 4096));
+      dst[i] = *(const __attribute__((address_space(1))) h8*)(abase + avoff + (i * 1024 - 4096));
     if (pair == 3) abase += 8192;
 #endif
   }
@@ -448,6 +443,7 @@ __device__ __forceinline__ float resid_hi(unsigned h, float v) {       // v - fl
 }
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 // four accumulator values (rows 4q .. 4q+3 of one row tile, one column) -> dwords [2 part, 2 part + 1] of the B fragments hi / lo
+// (LO = false: hi only, the plain-fp16 operands of the eight-wave kernels)
 template <bool LO, int PART>
 __device__ __forceinline__ void cvt4(const f32x4& x, float scale, u32x4& h, u32x4& l) {
   float v[4];
@@ -482,9 +478,8 @@ __device__ __forceinline__ void cvt4(const f32x4& x, float scale, u32x4& h, u32x
 //     tl's 96 MFMAs -- one f32x4 per quarter-step, written to LDS for the other waves and kept in registers (cv) as this wave's B
 //     operands.  A barrier in front of chunk position 1 is the only one the publish needs (everybody's blocks are in LDS then);
 //     the conversion of 3/4 of a publish and all of its LDS writes run in the MFMAs' shadow instead of in front of the GEMM.
-// LO = false: plain fp16 operands (hi parts only, one MFMA per product; DINER_PRECISION_F16).
-template <int KT, int R, bool LO, bool OWN, class Side>
-__device__ __forceinline__ void gemm(ARing<KT, R, LO>& ring, LdsB B, int wave, const f32x4 (&src)[kSlice][kGroups], float scale,
+template <int KT, int R, bool OWN, class Side>
+__device__ __forceinline__ void gemm(ARing<KT, R>& ring, LdsB B, int wave, const f32x4 (&src)[kSlice][kGroups], float scale,
                                      f32x4 (&acc)[kSlice][kGroups], Side& side) {
   constexpr int NH = 2 * KT;
   static_assert(!OWN || KT == 16, "own-chunk scheme: 512-wide contractions only");
@@ -501,7 +496,7 @@ __device__ __forceinline__ void gemm(ARing<KT, R, LO>& ring, LdsB B, int wave, c
     asm volatile("" : "+v"(bb[g][0]), "+v"(bb[g][1]));
 #else
     bb[g][0] = *LdsB::at(cbp[t >> 2], t & 3, g, 0);
-    if (LO) bb[g][1] = *LdsB::at(cbp[t >> 2], t & 3, g, 1);
+    bb[g][1] = *LdsB::at(cbp[t >> 2], t & 3, g, 1);
 #endif
   };
   cbp[0] = chunk_ptr(0);
@@ -530,11 +525,11 @@ __device__ __forceinline__ void gemm(ARing<KT, R, LO>& ring, LdsB B, int wave, c
     }
     if constexpr (OWN && t + 1 < 4) {    // convert block t + 1 of the own chunk, one f32x4 per quarter-step: unit u of 8
       constexpr int u = half * 4 + g, gu = u >> 1, part = u & 1;
-      cvt4<LO, part>(src[2 * (t + 1) + part][gu], scale, ch, cl);
+      cvt4<true, part>(src[2 * (t + 1) + part][gu], scale, ch, cl);
       if constexpr (part == 1) {         // the pair is complete: to LDS, for the other waves and for this one (in order: no barrier)
         asm volatile("" : "+v"(cbp[0]));
         *LdsB::at(cbp[0], t + 1, gu, 0) = __builtin_bit_cast(h8, ch);
-        if constexpr (LO) *LdsB::at(cbp[0], t + 1, gu, 1) = __builtin_bit_cast(h8, cl);
+        *LdsB::at(cbp[0], t + 1, gu, 1) = __builtin_bit_cast(h8, cl);
       }
     }
     side.template run<h, g>();
@@ -542,12 +537,10 @@ __device__ __forceinline__ void gemm(ARing<KT, R, LO>& ring, LdsB B, int wave, c
     const h8 b0 = bb[g][0], b1 = bb[g][1];
 #pragma unroll
     for (int m = 0; m < 4; ++m) DINER_HN_MFMA(acc[4 * half + m][g], ac[2 * m], b0);
-    if constexpr (LO) {
 #pragma unroll
-      for (int m = 0; m < 4; ++m) DINER_HN_MFMA(acc[4 * half + m][g], ac[2 * m + 1], b0);
+    for (int m = 0; m < 4; ++m) DINER_HN_MFMA(acc[4 * half + m][g], ac[2 * m + 1], b0);
 #pragma unroll
-      for (int m = 0; m < 4; ++m) DINER_HN_MFMA(acc[4 * half + m][g], ac[2 * m], b1);
-    }
+    for (int m = 0; m < 4; ++m) DINER_HN_MFMA(acc[4 * half + m][g], ac[2 * m], b1);
     // Anchor the quarter-step's results here (no code): MFMAs are pure, and without a use in place the optimiser may
     // sink a whole accumulation chain below all of the GEMM's loads (seen in k_field_post_h3n: every fragment spilled).
 #pragma unroll
@@ -556,17 +549,16 @@ __device__ __forceinline__ void gemm(ARing<KT, R, LO>& ring, LdsB B, int wave, c
   side.finish();
 }
 // all B operands from LDS (published before the call): start + run in one go
-template <int KT, int R, bool LO, class Side>
+template <int KT, int R, class Side>
 __device__ __forceinline__ void gemm(const _Float16* __restrict__ layer, LdsB B, int wave, int lane,
                                      f32x4 (&acc)[kSlice][kGroups], Side& side) {
-  ARing<KT, R, LO> ring;
+  ARing<KT, R> ring;
   ring.start(layer, wave, lane);
-  gemm<KT, R, LO, false>(ring, B, wave, acc, 0.0f, acc, side);
+  gemm<KT, R, false>(ring, B, wave, acc, 0.0f, acc, side);
 }
 
 // publish relu(acc) * scale of this wave's 128-feature slice as B operands (its own chunk: k32 blocks 4w .. 4w+3) for all 4 column
 // groups, in front of a GEMM (the GEMMs that carry a gather side task, lin_out)
-template <bool LO>
 __device__ __forceinline__ void publish(LdsB B, int wave, int lane, const f32x4 (&acc)[kSlice][kGroups]) {
   B.opaque();
 #ifdef DINER_HN_NO_PUBLISH
@@ -579,29 +571,29 @@ __device__ __forceinline__ void publish(LdsB B, int wave, int lane, const f32x4 
 #pragma unroll
     for (int g = 0; g < kGroups; ++g) {
       u32x4 h, l;
-      cvt4<LO, 0>(acc[2 * tl][g], kInvScale, h, l);
-      cvt4<LO, 1>(acc[2 * tl + 1][g], kInvScale, h, l);
+      cvt4<true, 0>(acc[2 * tl][g], kInvScale, h, l);
+      cvt4<true, 1>(acc[2 * tl + 1][g], kInvScale, h, l);
       *LdsB::at(cb, tl, g, 0) = __builtin_bit_cast(h8, h);
-      if constexpr (LO) *LdsB::at(cb, tl, g, 1) = __builtin_bit_cast(h8, l);
+      *LdsB::at(cb, tl, g, 1) = __builtin_bit_cast(h8, l);
     }
 }
 
 // relu(src) -> B operands and the GEMM of `layer` on them.  OWN: the own-chunk scheme of gemm (one barrier in front, block 0 of the
 // own chunk converted before it so that the wait overlaps with the conversion, one barrier inside the GEMM); otherwise barrier,
 // publish, barrier, GEMM.  The weight ring is started first (EARLY) -- the barriers wait on LDS traffic only.
-template <int R, bool LO, bool EARLY, bool OWN, bool BIAS_FIRST = true, class Side, class Between>
+template <int R, bool EARLY, bool OWN, bool BIAS_FIRST = true, class Side, class Between>
 __device__ __forceinline__ void publish_gemm(const _Float16* __restrict__ layer, LdsB B, int wave, int lane,
                                              const f32x4 (&src)[kSlice][kGroups], f32x4 (&acc)[kSlice][kGroups], Side& side,
                                              Between&& between, Prof& pf, int ph) {
-  ARing<16, R, LO> ring;
+  ARing<16, R> ring;
   if constexpr (EARLY) ring.start(layer, wave, lane);
   if constexpr (OWN) {
     if constexpr (BIAS_FIRST) between();          // bias of the accumulators the GEMM adds into (its loads fly during the conversion)
     u32x4 c0[kGroups][2];
 #pragma unroll
     for (int g = 0; g < kGroups; ++g) {           // block 0 of the own chunk, converted while the others finish the previous GEMM
-      cvt4<LO, 0>(src[0][g], kInvScale, c0[g][0], c0[g][1]);
-      cvt4<LO, 1>(src[1][g], kInvScale, c0[g][0], c0[g][1]);
+      cvt4<true, 0>(src[0][g], kInvScale, c0[g][0], c0[g][1]);
+      cvt4<true, 1>(src[1][g], kInvScale, c0[g][0], c0[g][1]);
     }
     pf.mark(ph);
     __syncthreads();                              // everybody finished reading the previous B
@@ -613,24 +605,24 @@ __device__ __forceinline__ void publish_gemm(const _Float16* __restrict__ layer,
 #pragma unroll
       for (int g = 0; g < kGroups; ++g) {
         *LdsB::at(cb, 0, g, 0) = __builtin_bit_cast(h8, c0[g][0]);
-        if constexpr (LO) *LdsB::at(cb, 0, g, 1) = __builtin_bit_cast(h8, c0[g][1]);
+        *LdsB::at(cb, 0, g, 1) = __builtin_bit_cast(h8, c0[g][1]);
       }
     }
     if constexpr (!BIAS_FIRST) between();
     if constexpr (!EARLY) ring.start(layer, wave, lane);
     pf.mark(ph + 2);
-    gemm<16, R, LO, true>(ring, B, wave, src, kInvScale, acc, side);
+    gemm<16, R, true>(ring, B, wave, src, kInvScale, acc, side);
     pf.mark(ph + 3);
   } else {
     __syncthreads();                              // everybody finished reading the previous B
     pf.mark(ph);
-    publish<LO>(B, wave, lane, src);
+    publish(B, wave, lane, src);
     pf.mark(ph + 1);
     __syncthreads();
     pf.mark(ph + 2);
     between();                                    // bias of the accumulators the GEMM adds into
     if constexpr (!EARLY) ring.start(layer, wave, lane);
-    gemm<16, R, LO, false>(ring, B, wave, src, kInvScale, acc, side);
+    gemm<16, R, false>(ring, B, wave, src, kInvScale, acc, side);
     pf.mark(ph + 3);
   }
 }
@@ -677,23 +669,6 @@ __device__ __forceinline__ void add_bias(f32x4 (&acc)[kSlice][kGroups], const fl
 #endif
 #ifndef DINER_HN_G0DEPTH        // units in flight for block 0's stand-alone gather (no GEMM buffers live there)
 #define DINER_HN_G0DEPTH 8
-#endif
-// Plain-fp16 instances (LO = false): a half-step is 4 x 4 MFMAs = 256 clocks instead of 768, so the same prefetch distances in half-steps
-// cover a third of the latency, and the lo planes' registers (48 of the weight ring, 16 of the B buffer) are free: deeper rings there.
-#ifndef DINER_HN_RING_F16        // measured (profiles/r04_ab_runs.txt): ring 4 / gather depth 3 is +6.7 % at 800x600, +3.8 % at 1024^2 K=192; 6 / 4 the same, 8 / 4 spills
-#define DINER_HN_RING_F16 4
-#endif
-#ifndef DINER_HN_RING0_F16
-#define DINER_HN_RING0_F16 DINER_HN_RING_F16
-#endif
-#ifndef DINER_HN_GDEPTH_F16
-#define DINER_HN_GDEPTH_F16 3
-#endif
-#ifndef DINER_HN_GDEPTH_H        // GatherSideH (fp16 maps): units between request and blend as a GEMM side task / stand-alone
-#define DINER_HN_GDEPTH_H 2
-#endif
-#ifndef DINER_HN_G0DEPTH_H
-#define DINER_HN_G0DEPTH_H 4
 #endif
 
 // xs[mo][g] += 16 * interp(lin_z[b](latent)) for this wave's feature slice and all four column groups: 32 units
@@ -833,104 +808,6 @@ struct GatherSide {
   }
 };
 
-// The same side task for the plain-fp16 instances (round 4): the taps come from the FP16 copy of the projected maps
-// (DinerScene.latent_proj_f16, written by k_proj_to_f16 in mlp.hip), whose 512 channels are stored in the order this kernel consumes
-// them -- position 128 w + 32 mp + 8 q + 4 (mo & 1) + i holds channel 128 w + 16 mo + 4 q + i (mp = mo / 2) -- so that ONE 16-byte load
-// per lane and tap carries the lane's four rows of TWO row tiles: half the load instructions, half the bytes through the vector-memory
-// path (which, not the matrix pipe, bounds these instances: at one MFMA per product the weight stream alone needs the path's 64 B/clk,
-// profiles/r04_cfg5_f16_*).  16 units (g, mp) of 4 taps; unit U is requested during half-step 2 U (tap G in quarter-step G) and
-// blended D units later, row tile 2 mp during the even half-step, 2 mp + 1 during the odd one: the blend is v_fma_mix_f32 (fp16 tap x
-// fp32 weight + fp32 sum: full rate, one per value as before).
-template <int D, bool SIDE = true>
-struct GatherSideH {
-  typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-  const char* __restrict__ tz;             // fp16 map of this block: (NV, Hf, Wf, 512) halves, 1 KB per texel
-  const TapRec* __restrict__ taps_lds;     // [g 4][col 16]
-  int wave, q, pt;
-  f32x4 (&xs)[kSlice][kGroups];
-  u32x4 r[D + 1][4];
-  u32x4 off4[kGroups];
-  f32x4 w4[kGroups];
-  f32x4 bw, bv;
-
-  __device__ __forceinline__ GatherSideH(const void* tz_, const TapRec* taps_lds_, int wave_, int q_, int pt_, f32x4 (&xs_)[kSlice][kGroups])
-      : tz(reinterpret_cast<const char*>(tz_)), taps_lds(taps_lds_), wave(wave_), q(q_), pt(pt_), xs(xs_) {
-    prefetch<0>();
-  }
-  template <int g>
-  __device__ __forceinline__ void prefetch() {
-    off4[g] = *reinterpret_cast<const u32x4*>(taps_lds[g * 16 + pt].off);
-    w4[g] = *reinterpret_cast<const f32x4*>(taps_lds[g * 16 + pt].w) * kScale;
-  }
-  template <int U, int KTAP>
-  __device__ __forceinline__ void issue_tap() {
-    constexpr int g = U >> 2, mp = U & 3;
-    const unsigned lane_off = (unsigned)(wave * 256 + q * 16);
-    r[U % (D + 1)][KTAP] = *reinterpret_cast<const u32x4*>(tz + (off4[g][KTAP] * 1024u + lane_off) + mp * 64);
-  }
-  static __device__ __forceinline__ float mix_lo(unsigned h, float w, float c) {      // float(low half of h) * w + c
-    float d;
-    asm("v_fma_mix_f32 %0, %1, %2, %3 op_sel_hi:[1,0,0]" : "=v"(d) : "v"(h), "v"(w), "v"(c));
-    return d;
-  }
-  static __device__ __forceinline__ float mix_hi(unsigned h, float w, float c) {      // float(high half of h) * w + c
-    float d;
-    asm("v_fma_mix_f32 %0, %1, %2, %3 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(d) : "v"(h), "v"(w), "v"(c));
-    return d;
-  }
-  // tap K of unit U into row tile 2 mp + HF: the blend is summed on its own and added to the accumulator in ONE step behind tap 3 (the
-  // GEMM this rides on accumulates into the same registers between the quarter-steps)
-  template <int U, int HF, int K>
-  __device__ __forceinline__ void blend_step() {
-    constexpr int g = U >> 2, mo = 2 * (U & 3) + HF;
-    const u32x4& t = r[U % (D + 1)][K];
-    if constexpr (K == 0) {
-      bw = w4[g];
-      asm volatile("" : "+v"(bw));           // (see GatherSide::blend_step)
-      bv = (f32x4){0.0f, 0.0f, 0.0f, 0.0f};
-    }
-    bv[0] = mix_lo(t[2 * HF], bw[K], bv[0]);
-    bv[1] = mix_hi(t[2 * HF], bw[K], bv[1]);
-    bv[2] = mix_lo(t[2 * HF + 1], bw[K], bv[2]);
-    bv[3] = mix_hi(t[2 * HF + 1], bw[K], bv[3]);
-    if constexpr (K == 3) {
-      asm volatile("" : "+a"(xs[mo][g]));      // keep the accumulator file assignment: read, add, write back
-      f32x4 acc = xs[mo][g];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) acc[i] = add1(acc[i], bv[i]);
-      xs[mo][g] = acc;
-      asm volatile("" : "+a"(xs[mo][g]));
-    }
-  }
-  template <int H, int G>
-  __device__ __forceinline__ void run() {
-    constexpr int U = H >> 1, V = U - D;
-    if constexpr (V >= 0 && V < 16) blend_step<(V >= 0 && V < 16 ? V : 0), (H & 1), G>();
-    if constexpr ((H & 1) == 0 && U < 16) issue_tap<(U < 16 ? U : 0), G>();
-    if constexpr (G == 1 && (H & 7) == 7 && H < 31) prefetch<(H < 31 ? (H + 1) >> 3 : 0)>();
-  }
-  __device__ __forceinline__ void finish() {
-    static_for<D>([&](auto I) {
-      constexpr int V = 16 - D + decltype(I)::value;
-      static_for<2>([&](auto HF) {
-        blend_step<V, decltype(HF)::value, 0>();
-        blend_step<V, decltype(HF)::value, 1>();
-        blend_step<V, decltype(HF)::value, 2>();
-        blend_step<V, decltype(HF)::value, 3>();
-      });
-    });
-  }
-  __device__ __forceinline__ void all() {
-    static_for<32>([&](auto H) {
-      run<decltype(H)::value, 0>();
-      run<decltype(H)::value, 1>();
-      run<decltype(H)::value, 2>();
-      run<decltype(H)::value, 3>();
-    });
-    finish();
-  }
-};
-
 // one accumulator block (this wave's 128 features x the 64 columns of the tile) -> a saved activation tensor (see SaveActs), x 1/16;
 // column group g is view g (per-view kernel: rows g P + p) or the g-th 16-point tile of the workgroup's 64 points (post kernel: rows p)
 // bits: the relu decisions of the same values, one dword per lane and row -- the lane's 32 features 16 mo + 4 q + i of the wave's slice at bit
@@ -963,10 +840,9 @@ __device__ __forceinline__ void save_block(float* __restrict__ dst, unsigned* __
   }
 }
 
-template <bool LO, bool SAVE>
+template <bool SAVE>
 __device__ __forceinline__ void field_pre_body(const SceneDev& sc, const Args& a, const SaveActs& sv) {
-  constexpr int kRing = LO ? DINER_HN_RING : DINER_HN_RING_F16, kRing0 = LO ? DINER_HN_RING0 : DINER_HN_RING0_F16;
-  constexpr int kGDepth = LO ? DINER_HN_GDEPTH : DINER_HN_GDEPTH_F16;
+  constexpr int kRing = DINER_HN_RING, kRing0 = DINER_HN_RING0, kGDepth = DINER_HN_GDEPTH;
   extern __shared__ __attribute__((aligned(16))) float smem[];
   h8* B = reinterpret_cast<h8*>(smem);
   TapRec* taps_lds = reinterpret_cast<TapRec*>(reinterpret_cast<char*>(smem) + (size_t)kBHalfs * 2);
@@ -988,8 +864,7 @@ __device__ __forceinline__ void field_pre_body(const SceneDev& sc, const Args& a
   __syncthreads();
   const LdsB Bl = LdsB::make(B, lane);
   const _Float16* w_in = a.w;                                   // [4][2][8][2][64][8]  = 4 * 2 * 16 KB
-  const _Float16* w_blk = a.w + (size_t)4 * 2 * 8192;           // then 6 layers of 4 * 16 * 16 KB
-  constexpr size_t kLayerHalfs = (size_t)4 * 16 * 8192;
+  const _Float16* w_blk = a.w + kLinInHalfs;                    // then 6 layers of 4 * 16 * 16 KB
 
   Prof pf;
   pf.begin();
@@ -1019,7 +894,7 @@ __device__ __forceinline__ void field_pre_body(const SceneDev& sc, const Args& a
           l[j] = (_Float16)(v - (float)hh);
         }
         B[((t * kGroups + wave) * 2 + 0) * 64 + lane] = h;
-        if constexpr (LO) B[((t * kGroups + wave) * 2 + 1) * 64 + lane] = l;
+        B[((t * kGroups + wave) * 2 + 1) * 64 + lane] = l;
       }
       if (q == 0) {
         TapRec r;
@@ -1036,28 +911,20 @@ __device__ __forceinline__ void field_pre_body(const SceneDev& sc, const Args& a
     pf.mark(3);
     f32x4 xs[kSlice][kGroups], ns[kSlice][kGroups];
     set_bias(xs, a.b, wave, q);
-#if defined(DINER_HN_G0EARLY)
-    if constexpr (LO) {      // experiment: block 0's first tap requests in front of the lin_in GEMM (measured, not kept: profiles/r04_ab_runs.txt)
-      NoSide none;
-      GatherSide<DINER_HN_G0DEPTH, false> g0(fa.tz, taps_lds, wave, q, pt, xs);
-      g0.head();
-      gemm<2, 2, LO>(w_in, Bl, wave, lane, xs, none);
-      pf.mark(4);
-      g0.tail();
-      pf.mark(5);
-    } else
-#endif
     {
       NoSide none;
-      gemm<2, 2, LO>(w_in, Bl, wave, lane, xs, none);
+#if defined(DINER_HN_G0EARLY)   // experiment: block 0's first tap requests in front of the lin_in GEMM (measured, not kept: profiles/r04_ab_runs.txt)
+      GatherSide<DINER_HN_G0DEPTH, false> g0(fa.tz, taps_lds, wave, q, pt, xs);
+      g0.head();
+      gemm<2, 2>(w_in, Bl, wave, lane, xs, none);
       pf.mark(4);
-      if constexpr (LO) {
-        GatherSide<DINER_HN_G0DEPTH, false> g0(fa.tz, taps_lds, wave, q, pt, xs);   // lin_z[0]: nothing long enough to hide under yet
-        g0.all();
-      } else {
-        GatherSideH<DINER_HN_G0DEPTH_H, false> g0(fa.tz16, taps_lds, wave, q, pt, xs);
-        g0.all();
-      }
+      g0.tail();
+#else
+      gemm<2, 2>(w_in, Bl, wave, lane, xs, none);
+      pf.mark(4);
+      GatherSide<DINER_HN_G0DEPTH, false> g0(fa.tz, taps_lds, wave, q, pt, xs);     // lin_z[0]: nothing long enough to hide under yet
+      g0.all();
+#endif
       pf.mark(5);
     }
 #pragma nounroll
@@ -1066,7 +933,7 @@ __device__ __forceinline__ void field_pre_body(const SceneDev& sc, const Args& a
       if constexpr (SAVE) save_block<true>(sv.X[b], sv.bX[b], fa.P, tile, wave, lane, xs);
       {
         NoSide none;
-        publish_gemm<kRing0, LO, DINER_HN_EARLYA != 0, DINER_HN_OWN != 0>(
+        publish_gemm<kRing0, DINER_HN_EARLYA != 0, DINER_HN_OWN != 0>(
             w_blk + (size_t)(2 * b) * kLayerHalfs, Bl, wave, lane, xs, ns, none, [&] { set_bias(ns, bias, wave, q); }, pf, 6);
       }
       if constexpr (SAVE) save_block<true>(sv.H[b], sv.bH[b], fa.P, tile, wave, lane, ns);
@@ -1074,23 +941,18 @@ __device__ __forceinline__ void field_pre_body(const SceneDev& sc, const Args& a
       // (folded into the projected map's bias when the weights are packed, mlp.hip)
       const _Float16* w1 = w_blk + (size_t)(2 * b + 1) * kLayerHalfs;
 #if DINER_HN_OWNG
-      if constexpr (LO) {
-        GatherSide<kGDepth> gs(fa.tz + (size_t)(b + 1) * fa.tz_stride, taps_lds, wave, q, pt, xs);
-        publish_gemm<kRing, LO, DINER_HN_EARLY1 != 0, true>(w1, Bl, wave, lane, ns, xs, gs, [&] { pin_acc(xs); }, pf, 10);
-      } else {
-        GatherSideH<DINER_HN_GDEPTH_H> gs(reinterpret_cast<const _Float16*>(fa.tz16) + (size_t)(b + 1) * fa.tz_stride, taps_lds, wave, q, pt, xs);
-        publish_gemm<kRing, LO, DINER_HN_EARLY1 != 0, true>(w1, Bl, wave, lane, ns, xs, gs, [&] { pin_acc(xs); }, pf, 10);
-      }
+      GatherSide<kGDepth> gs(fa.tz + (size_t)(b + 1) * fa.tz_stride, taps_lds, wave, q, pt, xs);
+      publish_gemm<kRing, DINER_HN_EARLY1 != 0, true>(w1, Bl, wave, lane, ns, xs, gs, [&] { pin_acc(xs); }, pf, 10);
 #else
       __syncthreads();
       pf.mark(10);
-      publish<LO>(Bl, wave, lane, ns);
+      publish(Bl, wave, lane, ns);
       pf.mark(11);
       __syncthreads();
       pf.mark(12);
       pin_acc(xs);
       GatherSide<kGDepth> gs(fa.tz + (size_t)(b + 1) * fa.tz_stride, taps_lds, wave, q, pt, xs);
-      gemm<16, kRing, LO>(w1, Bl, wave, lane, xs, gs);
+      gemm<16, kRing>(w1, Bl, wave, lane, xs, gs);
       pf.mark(13);
 #endif
     }
@@ -1098,11 +960,11 @@ __device__ __forceinline__ void field_pre_body(const SceneDev& sc, const Args& a
       const float* bias = a.b + kHidden * 5;
       NoSide none;
       if constexpr (SAVE) save_block<true>(sv.X[2], sv.bX[2], fa.P, tile, wave, lane, xs);
-      publish_gemm<kRing0, LO, DINER_HN_EARLYA != 0, DINER_HN_OWN != 0>(
+      publish_gemm<kRing0, DINER_HN_EARLYA != 0, DINER_HN_OWN != 0>(
           w_blk + (size_t)4 * kLayerHalfs, Bl, wave, lane, xs, ns, none, [&] { set_bias(ns, bias, wave, q); }, pf, 6);
       if constexpr (SAVE) save_block<true>(sv.H[2], sv.bH[2], fa.P, tile, wave, lane, ns);
-      publish_gemm<kRing, LO, DINER_HN_EARLY1 != 0, DINER_HN_OWN != 0>(w_blk + (size_t)5 * kLayerHalfs, Bl, wave, lane, ns, xs, none,
-                                                                [&] { pin_acc(xs); }, pf, 10);
+      publish_gemm<kRing, DINER_HN_EARLY1 != 0, DINER_HN_OWN != 0>(w_blk + (size_t)5 * kLayerHalfs, Bl, wave, lane, ns, xs, none,
+                                                                   [&] { pin_acc(xs); }, pf, 10);
     }
     // view mean = mean over the four column groups; hand-over at scale 1 in accumulator layout (row tile 8 w + mo)
     f32x4* out = reinterpret_cast<f32x4*>(fa.xpre) + (size_t)tile * (kTiles * 64) + lane;
@@ -1113,10 +975,16 @@ __device__ __forceinline__ void field_pre_body(const SceneDev& sc, const Args& a
   }
   pf.end(a.prof, lane);
 }
+// (a template with the one instance <true> only to keep the kernel's name: `k_field_pre_h3n<true>` is what the benchmark line's
+// roofline.kernel, the key into profiles/pmc_latest.json and every committed kernel trace call it; <false> was the plain-fp16 arithmetic on
+// four waves, which has run on k_field_pre_h8 since round 5)
 template <bool LO>
-__global__ __launch_bounds__(256, 1) void k_field_pre_h3n(SceneDev sc, Args a) { field_pre_body<LO, false>(sc, a, SaveActs{}); }
+__global__ __launch_bounds__(256, 1) void k_field_pre_h3n(SceneDev sc, Args a) {
+  static_assert(LO, "f16x3 only");
+  field_pre_body<false>(sc, a, SaveActs{});
+}
 // the same kernel storing the pre-activations of blocks 0-2 (training forward, DINER_TRAIN_FUSED_FWD)
-__global__ __launch_bounds__(256, 1) void k_train_fwd_pre(SceneDev sc, Args a, SaveActs sv) { field_pre_body<true, true>(sc, a, sv); }
+__global__ __launch_bounds__(256, 1) void k_train_fwd_pre(SceneDev sc, Args a, SaveActs sv) { field_pre_body<true>(sc, a, sv); }
 
 // =====================================================================================================================================
 // Round 5: the plain-fp16 per-view kernel with EIGHT waves per workgroup (two per SIMD): k_field_pre_h8.
@@ -1307,9 +1175,24 @@ __device__ __forceinline__ void pin_acc8(f32x4 (&acc)[kS8][kGroups]) {
     for (int g = 0; g < kGroups; ++g) asm volatile("" : "+a"(acc[mo][g]));
 }
 
-// xs[mo][g] += 16 * interp(projected map) from the fp16 maps (see GatherSideH): 8 units U = (g, mp) of 4 taps; ONE 16-byte load per lane and
-// tap carries the lane's four rows of the wave's row tiles 2 mp and 2 mp + 1.  Steps T (the k32 blocks of the GEMM this rides on, or the
-// steps of the stand-alone loop) of four quarters G: unit U is requested during step 2 U (tap G in quarter G) and blended D units
+// fp16 tap x fp32 weight + fp32 sum in one full-rate instruction: the fp16 operand is read in place from either half of a dword
+__device__ __forceinline__ float mix_lo(unsigned h, float w, float c) {      // float(low half of h) * w + c
+  float d;
+  asm("v_fma_mix_f32 %0, %1, %2, %3 op_sel_hi:[1,0,0]" : "=v"(d) : "v"(h), "v"(w), "v"(c));
+  return d;
+}
+__device__ __forceinline__ float mix_hi(unsigned h, float w, float c) {      // float(high half of h) * w + c
+  float d;
+  asm("v_fma_mix_f32 %0, %1, %2, %3 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(d) : "v"(h), "v"(w), "v"(c));
+  return d;
+}
+
+// xs[mo][g] += 16 * interp(projected map) from the FP16 copy of the projected maps (DinerScene.latent_proj_f16, written by k_proj_to_f16 in
+// mlp.hip), whose 512 channels are stored in the order this kernel consumes them: position 128 wp + 32 mp + 8 q + 4 (mo & 1) + i holds
+// channel 128 wp + 16 mo + 4 q + i, where wave pair wp = w / 2 owns 8 row tiles mo and mp = mo / 2.  Per wave 8 units U = (g, mp) of 4 taps;
+// ONE 16-byte load per lane and tap carries the lane's four rows of the wave's row tiles 2 mp and 2 mp + 1: half the load instructions and
+// half the bytes of fp32 taps through the vector-memory path; the blend is v_fma_mix_f32 (mix_lo / mix_hi), one per value.
+// Steps T (the k32 blocks of the GEMM this rides on, or the steps of the stand-alone loop) of four quarters G: unit U is requested during step 2 U (tap G in quarter G) and blended D units
 // later, row tile 2 mp during step 2 (U + D), row tile 2 mp + 1 during the next one.  A column's tap rows (`off4`, needed when group g's
 // units are requested: steps 4 g, 4 g + 2) and blend weights (`w4`, needed from step 4 g + 2 D on) are read from LDS one step ahead of
 // their first use into ONE slot each (the previous group's last use lies behind by then).
@@ -1372,10 +1255,10 @@ struct Gather8 {
       asm volatile("" : "+v"(bw));           // (see GatherSide::blend_step)
       bv = (f32x4){0.0f, 0.0f, 0.0f, 0.0f};
     }
-    bv[0] = GatherSideH<1>::mix_lo(t[2 * HF], bw[K], bv[0]);
-    bv[1] = GatherSideH<1>::mix_hi(t[2 * HF], bw[K], bv[1]);
-    bv[2] = GatherSideH<1>::mix_lo(t[2 * HF + 1], bw[K], bv[2]);
-    bv[3] = GatherSideH<1>::mix_hi(t[2 * HF + 1], bw[K], bv[3]);
+    bv[0] = mix_lo(t[2 * HF], bw[K], bv[0]);
+    bv[1] = mix_hi(t[2 * HF], bw[K], bv[1]);
+    bv[2] = mix_lo(t[2 * HF + 1], bw[K], bv[2]);
+    bv[3] = mix_hi(t[2 * HF + 1], bw[K], bv[3]);
     if constexpr (K == 3) {
 #ifdef DINER_H8_NO_ACCUM        // ablation: the blend without the accumulator update
       asm volatile("" :: "v"(bv));
@@ -1573,352 +1456,6 @@ __global__ __launch_bounds__(512, 1) void k_field_pre_h8(SceneDev sc, Args a) {
   pf.end(a.prof, lane);
 }
 
-// -------------------------------------------------------------------------------------------------------------------------------------
-// The same decomposition for the f16x3 arithmetic (hi and lo planes, three MFMAs per product): k_field_pre_h8x.
-//   * weights [wave 8][k32 block][row tile 4][hi | lo][lane 64][8 halfs]: 8 KB per wave and block, two buffer loads per quarter-step,
-//     ring of R blocks (R = 2: a block is 48 MFMAs = 768 clocks of this wave, about twice that of wall time with two waves per SIMD)
-//   * B operands [k32 16][g 4][hi | lo][lane 64]: 128 KB, ONE buffer (two would not fit): barrier, publish, barrier per layer
-//   * taps: fp32 projected maps (the parity-grade mode keeps fp32 taps), 16 units (g, mo) of 4 taps per wave; the tap buffers live in the
-//     AGPR half of the file (the hidden block's 64 registers are dead while the gather-carrying GEMM runs; the arch half holds ring + B)
-constexpr size_t kLinInHalfs8x = (size_t)8 * 2 * 4 * 2 * 512, kLayerHalfs8x = (size_t)8 * 16 * 4 * 2 * 512;
-constexpr size_t kLdsBytes8x = (size_t)2 * kB8Bytes + kTapsBytes + kFeatTabBytes + kFeatSrcBytes8;      // (one B buffer of hi + lo planes)
-#ifndef DINER_H8X_RING
-#define DINER_H8X_RING 2
-#endif
-#ifndef DINER_H8X_GDEPTH
-#define DINER_H8X_GDEPTH 1
-#endif
-#ifndef DINER_H8X_G0DEPTH
-#define DINER_H8X_G0DEPTH 4
-#endif
-#ifndef DINER_H8X_TAPS_A
-#define DINER_H8X_TAPS_A 0
-#endif
-
-__device__ __forceinline__ lds_h8 bfrag8x(lds_ptr base, int t, int g, int hl) { return (lds_h8)(base + ((t * kGroups + g) * 2 + hl) * 1024); }
-
-template <int KT, int R>
-struct ARing8X {
-  h8 a[R][8];                            // [row tile m][hi | lo] = a[.][2 m + hl]
-  __amdgpu_buffer_rsrc_t rs;
-  unsigned avoff;
-  template <int H>
-  __device__ __forceinline__ void load2(h8 (&dst)[8], int pair) {      // fragments 2 pair, 2 pair + 1 (hi, lo of row tile `pair`) of block H
-#pragma unroll
-    for (int i = 2 * pair; i < 2 * pair + 2; ++i)
-      dst[i] = __builtin_bit_cast(h8, __builtin_amdgcn_raw_buffer_load_b128(rs, avoff, (H * 8 + i) * 1024, 0));
-  }
-  __device__ __forceinline__ void start(const _Float16* __restrict__ layer, int wave, int lane) {
-    rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(reinterpret_cast<const char*>(layer) + (size_t)wave * KT * 8192), 0, KT * 8192, 0x00020000);
-    avoff = lane * 16;
-    static_for<(R - 1 < KT ? R - 1 : KT)>([&](auto H) {
-#pragma unroll
-      for (int pr = 0; pr < 4; ++pr) load2<decltype(H)::value>(a[decltype(H)::value], pr);
-    });
-  }
-};
-
-// acc[mo][g] += W . B in three products (hi hi, lo hi, hi lo): 48 MFMAs per k32 block
-template <int KT, int R, class Side>
-__device__ __forceinline__ void gemm8x(const _Float16* __restrict__ layer, lds_ptr Bb, int wave, int lane, f32x4 (&acc)[kS8][kGroups], Side& side) {
-  ARing8X<KT, R> ring;
-  ring.start(layer, wave, lane);
-  asm volatile("" : "+v"(Bb));
-  h8 bb[kGroups][2];
-#pragma unroll
-  for (int g = 0; g < kGroups; ++g) {
-    bb[g][0] = *bfrag8x(Bb, 0, g, 0);
-    bb[g][1] = *bfrag8x(Bb, 0, g, 1);
-  }
-  static_for<KT * kGroups>([&](auto Q) {
-    constexpr int qi = decltype(Q)::value;
-    constexpr int t = qi >> 2, g = qi & 3;
-    __builtin_amdgcn_sched_barrier(0);
-    if constexpr (t + R - 1 < KT) ring.template load2<(t + R - 1 < KT ? t + R - 1 : 0)>(ring.a[(t + R - 1) % R], g);
-    if constexpr (g > 0 && t + 1 < KT) {
-      bb[g - 1][0] = *bfrag8x(Bb, t + 1, g - 1, 0);
-      bb[g - 1][1] = *bfrag8x(Bb, t + 1, g - 1, 1);
-    }
-    if constexpr (g == 0 && t > 0) {
-      bb[kGroups - 1][0] = *bfrag8x(Bb, t, kGroups - 1, 0);
-      bb[kGroups - 1][1] = *bfrag8x(Bb, t, kGroups - 1, 1);
-    }
-    side.template run<t, g>();
-    h8 (&ac)[8] = ring.a[t % R];
-    const h8 b0 = bb[g][0], b1 = bb[g][1];
-#pragma unroll
-    for (int m = 0; m < kS8; ++m) DINER_HN_MFMA(acc[m][g], ac[2 * m], b0);
-#pragma unroll
-    for (int m = 0; m < kS8; ++m) DINER_HN_MFMA(acc[m][g], ac[2 * m + 1], b0);
-#pragma unroll
-    for (int m = 0; m < kS8; ++m) DINER_HN_MFMA(acc[m][g], ac[2 * m], b1);
-#pragma unroll
-    for (int m = 0; m < kS8; ++m) asm volatile("" : "+a"(acc[m][g]));
-  });
-  side.finish();
-}
-
-__device__ __forceinline__ void publish8x(lds_ptr Bb, int wave, const f32x4 (&acc)[kS8][kGroups]) {
-  lds_ptr mine = Bb + wave * (2 * kGroups * 2 * 1024);
-  asm volatile("" : "+v"(mine));
-#pragma unroll
-  for (int tl = 0; tl < 2; ++tl)
-#pragma unroll
-    for (int g = 0; g < kGroups; ++g) {
-      u32x4 h, l;
-      cvt4<true, 0>(acc[2 * tl][g], kInvScale, h, l);
-      cvt4<true, 1>(acc[2 * tl + 1][g], kInvScale, h, l);
-      *bfrag8x(mine, tl, g, 0) = __builtin_bit_cast(h8, h);
-      *bfrag8x(mine, tl, g, 1) = __builtin_bit_cast(h8, l);
-    }
-}
-
-// xs[mo][g] += 16 * interp(projected map), fp32 maps: 16 units U = (g, mo) of 4 taps (one f32x4 per lane and tap: rows 4q .. 4q+3 of the
-// wave's row tile mo).  Unit U is requested during step U (tap G in quarter G) and blended D units later.  Tap buffers in AGPRs (TA).
-template <int D, bool TA>
-struct Gather8F {
-  static constexpr int kSteps = 16 + D;
-  const float* __restrict__ tz;
-  const TapRec* __restrict__ taps_lds;
-  int pt;
-  unsigned lane_off;
-  f32x4 (&xs)[kS8][kGroups];
-  f32x4 r[D + 1][4];
-  u32x4 off4;
-  f32x4 w4, bw, bv;
-  __device__ __forceinline__ Gather8F(const float* tz_, const TapRec* taps_lds_, int wave, int q, int pt_, f32x4 (&xs_)[kS8][kGroups])
-      : tz(tz_), taps_lds(taps_lds_), pt(pt_), lane_off((unsigned)((16 * wave + q) * 16)), xs(xs_) {
-    off4 = *reinterpret_cast<const u32x4*>(taps_lds[pt].off);
-  }
-  template <int U, int KTAP>
-  __device__ __forceinline__ void issue_tap() {
-    constexpr int mo = U & 3;
-    const char* base = reinterpret_cast<const char*>(tz);
-#ifdef DINER_H8X_G_NOLOAD
-    asm volatile("" : "+v"(r[U % (D + 1)][KTAP]));
-#else
-    r[U % (D + 1)][KTAP] = *reinterpret_cast<const f32x4*>(base + (off4[KTAP] * 2048u + lane_off) + mo * 64);
-#endif
-    if constexpr (TA) asm volatile("" : "+a"(r[U % (D + 1)][KTAP]));
-  }
-  template <int U, int K>
-  __device__ __forceinline__ void blend_step() {
-    constexpr int g = U >> 2, mo = U & 3;
-    f32x4 t;
-    if constexpr (TA) {
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        int ti;
-        asm("v_accvgpr_read_b32 %0, %1" : "=v"(ti) : "a"(r[U % (D + 1)][K][i]));
-        t[i] = __int_as_float(ti);
-      }
-    } else {
-      t = r[U % (D + 1)][K];
-    }
-#ifdef DINER_H8X_NO_BLEND
-    asm volatile("" :: "v"(t));
-    return;
-#endif
-    if constexpr (K == 0) {
-      bw = w4;
-      asm volatile("" : "+v"(bw));           // (see GatherSide::blend_step)
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) bv[i] = K == 0 ? mul1(t[i], bw[0]) : fma1(t[i], bw[K], bv[i]);
-    if constexpr (K == 3) {
-      asm volatile("" : "+a"(xs[mo][g]));
-      f32x4 acc = xs[mo][g];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) acc[i] = add1(acc[i], bv[i]);
-      xs[mo][g] = acc;
-      asm volatile("" : "+a"(xs[mo][g]));
-    }
-  }
-  template <int T, int G>
-  __device__ __forceinline__ void run() {
-    constexpr int V = T - D;
-    if constexpr (V >= 0 && V < 16) blend_step<(V >= 0 && V < 16 ? V : 0), G>();
-    if constexpr (T < 16) issue_tap<(T < 16 ? T : 0), G>();
-    if constexpr (G == 1) {
-      // tap rows of the next group: its first unit is requested in step T + 1 = 4 g'.  This step's requests (quarters 2, 3 still to come) use
-      // the old rows: read into a spare and swap behind quarter 3 -- done by reading in quarter 3 instead (below)
-    }
-    if constexpr (G == 3) {
-      if constexpr ((T & 3) == 3 && (T + 1) / 4 < kGroups) off4 = *reinterpret_cast<const u32x4*>(taps_lds[((T + 1) / 4) * 16 + pt].off);
-    }
-    if constexpr (G == 1) {
-      // blend weights of group gw, first used in step 4 gw + D = T + 1 (this step's blend copied the previous group's in quarter 0)
-      if constexpr (T + 1 >= D && ((T + 1 - D) & 3) == 0 && (T + 1 - D) / 4 < kGroups)
-        w4 = *reinterpret_cast<const f32x4*>(taps_lds[((T + 1 - D) / 4) * 16 + pt].w) * kScale;
-    }
-  }
-  __device__ __forceinline__ void finish() {
-    static_for<D>([&](auto I) {
-      constexpr int T = 16 + decltype(I)::value;
-      run<T, 0>(); run<T, 1>(); run<T, 2>(); run<T, 3>();
-    });
-  }
-  __device__ __forceinline__ void all() {
-    static_for<kSteps>([&](auto I) {
-      constexpr int T = decltype(I)::value;
-      run<T, 0>(); run<T, 1>(); run<T, 2>(); run<T, 3>();
-    });
-  }
-};
-
-__global__ __launch_bounds__(512, 1) void k_field_pre_h8x(SceneDev sc, Args a) {
-  constexpr int R = DINER_H8X_RING;
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  h8* B = reinterpret_cast<h8*>(smem);
-  TapRec* taps_lds = reinterpret_cast<TapRec*>(reinterpret_cast<char*>(smem) + (size_t)2 * kB8Bytes);
-  FeatRec* feat_tab = reinterpret_cast<FeatRec*>(reinterpret_cast<char*>(taps_lds) + kTapsBytes);
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int lane = threadIdx.x & 63;
-  const int q = lane >> 4, pt = lane & 15;
-  const int view = wave & 3, tin = wave >> 2;
-  float* feat_src = reinterpret_cast<float*>(reinterpret_cast<char*>(feat_tab) + kFeatTabBytes) + wave * 64 * kSrcStride;
-  const FieldArgs& fa = a.fa;
-  if (threadIdx.x < 64) {
-    const int sl = threadIdx.x & 15;
-    feat_tab[threadIdx.x] = feat_recipe(16 * (sl >> 2) + 4 * (threadIdx.x >> 4) + (sl & 3), fa.freq_factor);
-  }
-  const long long n_tiles = (fa.P + kPtsPerWave - 1) / kPtsPerWave;
-  __shared__ unsigned s_tile;
-  TileQueue tq;
-  tq.begin();
-  tq.first(a.tile_counter, n_tiles, a.qmap, &s_tile);
-  __syncthreads();
-  lds_ptr Bb = (lds_ptr)(reinterpret_cast<char*>(B)) + lane * 16;
-  const _Float16* w_in = a.w8x;
-  const _Float16* w_blk = a.w8x + kLinInHalfs8x;
-
-  Prof pf;
-  pf.begin();
-  for (long long tile = tq.initial(&s_tile); tile < n_tiles; tile = tq.next(tile, &s_tile)) {
-    tq.request(a.tile_counter, n_tiles, a.qmap);
-    long long p = tile * kPtsPerWave + pt;
-    if (p >= fa.P) p = fa.P - 1;
-    MapDims dims{sc.Wf, sc.Hf, sc.Ws, sc.Hs};
-    asm volatile("" : "+s"(dims.Wf), "+s"(dims.Hf), "+s"(dims.Ws), "+s"(dims.Hs));
-    h8 fin_h, fin_l;
-    Taps taps;
-    {
-      float px, py, pz, dx, dy, dz;
-      load_point(fa, p, px, py, pz, dx, dy, dz);
-      float xc[3], vd[3];
-      world_to_cam(sc.R[view], sc.t[view], px, py, pz, xc[0], xc[1], xc[2]);
-      vd[0] = rot_row(sc.R[view] + 0, dx, dy, dz);
-      vd[1] = rot_row(sc.R[view] + 3, dx, dy, dz);
-      vd[2] = rot_row(sc.R[view] + 6, dx, dy, dz);
-      const float u = project_axis(xc[0], xc[2], sc.focal[view][0], sc.c[view][0], sc.img_w);
-      const float w = project_axis(xc[1], xc[2], sc.focal[view][1], sc.c[view][1], sc.img_h);
-      const int ix = nearest_border(u, dims.Ws), iy = nearest_border(w, dims.Hs);
-      const float dd = __fsub_rn(sc.depth[(size_t)view * dims.Hs * dims.Ws + (size_t)iy * dims.Ws + ix], xc[2]);
-      float* mine = feat_src + lane * kSrcStride;
-      mine[0] = xc[0]; mine[1] = xc[1]; mine[2] = xc[2];
-      mine[3] = vd[0]; mine[4] = vd[1]; mine[5] = vd[2];
-      mine[6] = dd;    mine[7] = 0.0f;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const FeatRec r = feat_tab[q * 16 + 8 * tin + j];
-        const float x = mine[r.src];
-        const float e = sin_posenc(__fmaf_rn(x, r.freq, r.phase));
-        const float v = r.sin ? e : x;
-        const _Float16 hh = (_Float16)v;
-        fin_h[j] = hh;
-        fin_l[j] = (_Float16)(v - (float)hh);
-      }
-      bilinear_taps(dims.Wf, dims.Hf, sc.feature_padding, view, u, w, taps);
-    }
-    pf.mark(0);
-    __syncthreads();                              // previous tile's readers of B / taps are done
-    pf.mark(1);
-    *bfrag8x(Bb, tin, view, 0) = fin_h;
-    *bfrag8x(Bb, tin, view, 1) = fin_l;
-    if (tin == 0 && q == 0) {
-      TapRec r;
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        r.off[k] = (unsigned)(taps.off[k] >> 9);
-        r.w[k] = taps.w[k];
-      }
-      taps_lds[view * 16 + pt] = r;
-    }
-    pf.mark(2);
-    __syncthreads();
-    pf.mark(3);
-    f32x4 xs[kS8][kGroups];
-    set_bias8(xs, a.b, wave, q);
-    pin_acc8(xs);
-    {
-      NoSide8 none;
-      gemm8x<2, 2>(w_in, Bb, wave, lane, xs, none);
-      pf.mark(4);
-      Gather8F<DINER_H8X_G0DEPTH, false> g0(fa.tz, taps_lds, wave, q, pt, xs);
-      g0.all();
-      pf.mark(5);
-    }
-    auto block = [&](int b, auto&& side) {
-      const float* bias = a.b + kHidden * (1 + 2 * b);
-      __syncthreads();                            // everybody finished reading the previous B
-      pf.mark(6);
-      publish8x(Bb, wave, xs);
-      pf.mark(7);
-      __syncthreads();
-      pf.mark(8);
-      {
-        f32x4 ns[kS8][kGroups];
-        set_bias8(ns, bias, wave, q);
-        NoSide8 none;
-        gemm8x<16, R>(w_blk + (size_t)(2 * b) * kLayerHalfs8x, Bb, wave, lane, ns, none);
-        pf.mark(9);
-        __syncthreads();
-        pf.mark(10);
-        publish8x(Bb, wave, ns);
-        pf.mark(11);
-      }
-      __syncthreads();
-      pf.mark(12);
-      pin_acc8(xs);
-      gemm8x<16, R>(w_blk + (size_t)(2 * b + 1) * kLayerHalfs8x, Bb, wave, lane, xs, side);
-      pf.mark(13);
-    };
-#pragma nounroll
-    for (int b = 0; b < 2; ++b) {
-#ifdef DINER_H8X_NO_GATHER      // ablation
-      NoSide8 gs;
-#else
-      Gather8F<DINER_H8X_GDEPTH, DINER_H8X_TAPS_A != 0> gs(fa.tz + (size_t)(b + 1) * fa.tz_stride, taps_lds, wave, q, pt, xs);
-#endif
-      block(b, gs);
-    }
-    {
-      NoSide8 none;
-      block(2, none);
-    }
-    f32x4* out = reinterpret_cast<f32x4*>(fa.xpre) + (size_t)tile * (kTiles * 64) + lane;
-#pragma unroll
-    for (int mo = 0; mo < kS8; ++mo)
-      out[(4 * wave + mo) * 64] = (((xs[mo][0] + xs[mo][1]) + xs[mo][2]) + xs[mo][3]) * (0.25f * kInvScale);
-    pf.mark(14);
-  }
-  pf.end(a.prof, lane);
-}
-
-// layer packing for k_field_pre_h8x: [w 8][t KT][mo 4][hl 2][lane 64][8]: hi / lo of W * scale
-__global__ void k_pack_layer_h8x(const float* __restrict__ W, int rows, int cols, int KT, float scale, _Float16* __restrict__ dst) {
-  const long long total = (long long)8 * KT * 4096;
-  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
-    const int j = i & 7, lane = (i >> 3) & 63, hl = (i >> 9) & 1, mo = (i >> 10) & 3;
-    const int wt = (int)(i >> 12), t = wt % KT, w = wt / KT;
-    const int row = 64 * w + 16 * mo + (lane & 15);
-    const int col = 32 * t + 16 * (j >> 2) + 4 * (lane >> 4) + (j & 3);
-    const float x = (row < rows && col < cols) ? W[(size_t)row * cols + col] * scale : 0.0f;
-    const _Float16 h = (_Float16)x;
-    dst[i] = hl ? (_Float16)(x - (float)h) : h;
-  }
-}
-
 // layer packing for k_field_pre_h8: [w 8][t KT][mo 4][lane 64][8] = W[64 w + 16 mo + (lane & 15)][32 t + 16 (j >> 2) + 4 (lane >> 4) + (j & 3)] * scale
 // (512-wide layers, DINER_H8_FLAGS: position s of wave w's stream is k32 block (2 w + s) & 15 -- the wave's own blocks first, see gemm8)
 __global__ void k_pack_layer_h8(const float* __restrict__ W, int rows, int cols, int KT, float scale, _Float16* __restrict__ dst) {
@@ -1955,7 +1492,7 @@ __device__ __forceinline__ int lane_here() {
 
 // Blocks 3-4 + lin_out + output activations on the view-averaged hidden state, same feature-sliced scheme: a
 // workgroup takes 64 points (four 16-point tiles = the four column groups), wave w owns features [128 w, 128 w + 128).
-template <bool LO, bool SAVE>
+template <bool SAVE>
 __device__ __forceinline__ void field_post_body(const PostArgsN& a, const SaveActs& sv) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   h8* B = reinterpret_cast<h8*>(smem);
@@ -1966,7 +1503,6 @@ __device__ __forceinline__ void field_post_body(const PostArgsN& a, const SaveAc
   const LdsB Bl = LdsB::make(B, lane);
   const long long n_t16 = (pa.P + kPtsPerWave - 1) / kPtsPerWave;
   const long long n_tiles = (n_t16 + 3) / 4;
-  constexpr size_t kLayerHalfs = (size_t)4 * 16 * 8192;
 
   Prof pf;
   pf.begin();
@@ -2024,14 +1560,14 @@ __device__ __forceinline__ void field_post_body(const PostArgsN& a, const SaveAc
     for (int b = 0; b < 2; ++b) {
       const float* bias = bpost + 2 * kHidden * b;
       if constexpr (SAVE) save_block<false>(sv.X[3 + b], sv.bX[3 + b], pa.P, tile, wave, lane_here(), xs);
-      publish_gemm<(LO ? DINER_HN_RING0 : DINER_HN_RING0_F16), LO, DINER_HN_EARLYP != 0, DINER_HN_OWN != 0>(a.w + (size_t)(2 * b) * kLayerHalfs, Bl, wave, lane, xs, ns, none, [&] {
+      publish_gemm<DINER_HN_RING0, DINER_HN_EARLYP != 0, DINER_HN_OWN != 0>(a.w + (size_t)(2 * b) * kLayerHalfs, Bl, wave, lane, xs, ns, none, [&] {
         set_bias(ns, bias, wave, lane_here() >> 4);
         pin_acc(xs);                              // the residual stream stays in registers across the fc_0 GEMM
       }, pf, 0);
       if (b == 0) tq.park(&s_tile2[par]);           // (the request went out at the top of the tile)
       if constexpr (SAVE) save_block<false>(sv.H[3 + b], sv.bH[3 + b], pa.P, tile, wave, lane_here(), ns);
       pin_acc(xs);
-      publish_gemm<(LO ? DINER_HN_RING : DINER_HN_RING_F16), LO, DINER_HN_EARLYP != 0, DINER_HN_OWN != 0, false>(a.w + (size_t)(2 * b + 1) * kLayerHalfs, Bl, wave, lane, ns, xs, none,
+      publish_gemm<DINER_HN_RING, DINER_HN_EARLYP != 0, DINER_HN_OWN != 0, false>(a.w + (size_t)(2 * b + 1) * kLayerHalfs, Bl, wave, lane, ns, xs, none,
                                       [&] { add_bias(xs, bias + kHidden, wave, lane_here() >> 4); }, pf, 4);
     }
 #if DINER_HN_LINOUT_VALU
@@ -2130,7 +1666,7 @@ __device__ __forceinline__ void field_post_body(const PostArgsN& a, const SaveAc
     // (requesting its 32 weight fragments before the publish moves 4 k clocks from here into the publish and the next tile's
     // hand-over load: measured, no net gain)
     __syncthreads();
-    publish<LO>(Bl, wave, lane, xs);
+    publish(Bl, wave, lane, xs);
     __syncthreads();
     tile_next_v = tq.take(tile, &s_tile2[par]);
     if (tile_next_v < n_tiles) request_handover(tile_next_v);
@@ -2151,10 +1687,8 @@ __device__ __forceinline__ void field_post_body(const PostArgsN& a, const SaveAc
         const h8 ah = wo[(t * 2 + 0) * 64], al = wo[(t * 2 + 1) * 64];
         const h8 bh = *LdsB::at(Bo.chunk(t >> 2), t & 3, 0, 0), bl = *LdsB::at(Bo.chunk(t >> 2), t & 3, 0, 1);
         DINER_HN_MFMA(o[t & 3], ah, bh);
-        if constexpr (LO) {
-          DINER_HN_MFMA(o[(t + 1) & 3], al, bh);
-          DINER_HN_MFMA(o[(t + 2) & 3], ah, bl);
-        }
+        DINER_HN_MFMA(o[(t + 1) & 3], al, bh);
+        DINER_HN_MFMA(o[(t + 2) & 3], ah, bl);
       }
       f32x4 res = ((o[0] + o[1]) + (o[2] + o[3])) * kInvScale;
       asm volatile("" : "+v"(res));
@@ -2188,10 +1722,13 @@ __device__ __forceinline__ void field_post_body(const PostArgsN& a, const SaveAc
   }
   pf.end(a.prof, lane);
 }
-template <bool LO>
-__global__ __launch_bounds__(256, 1) void k_field_post_h3n(PostArgsN a) { field_post_body<LO, false>(a, SaveActs{}); }
+template <bool LO>      // (one instance, <true>: see k_field_pre_h3n)
+__global__ __launch_bounds__(256, 1) void k_field_post_h3n(PostArgsN a) {
+  static_assert(LO, "f16x3 only");
+  field_post_body<false>(a, SaveActs{});
+}
 // the same kernel storing the pre-activations of blocks 3-4, the stream entering lin_out and lin_out's raw outputs (training forward)
-__global__ __launch_bounds__(256, 1) void k_train_fwd_post(PostArgsN a, SaveActs sv) { field_post_body<true, true>(a, sv); }
+__global__ __launch_bounds__(256, 1) void k_train_fwd_post(PostArgsN a, SaveActs sv) { field_post_body<true>(a, sv); }
 
 // Round 5: the post kernel of the plain-fp16 mode on eight waves (two per SIMD), the scheme of k_field_pre_h8: wave w owns features
 // [64 w, 64 w + 64) of the 64 points of a tile (four 16-point tiles = the four column groups); two B buffers, one barrier per layer; lin_out
@@ -2430,108 +1967,75 @@ __global__ void k_scale_pad(const float* __restrict__ src, int n, int n_pad, flo
 
 }  // namespace h3n
 
-// w: lin_in + 6 per-view + 4 post layers (n-split fragments); w_out: lin_out fragments; b_pre: 7 x 512 (x16); b_post: 4 x 512
-// (x16) + the lin_out bias at scale 1 (padded to 16).  The caller frees whatever was allocated when this fails.
-static size_t h3n_halfs4() { return (size_t)4 * 2 * 8192 + (size_t)(6 + 4) * 4 * 16 * 8192; }      // lin_in, 6 per-view layers, 4 post layers
-int h3n_alloc(float** w_out, float** w_lin_out, float** b_pre, float** b_post) {
-  using namespace h3n;
-  const size_t halfs4 = h3n_halfs4();
-  const size_t halfs8 = w8::kLinInHalfs8 + 6 * w8::kLayerHalfs8;                    // the per-view layers in the 8-wave kernels' order: hi plane,
-  const size_t halfs8x = w8::kLinInHalfs8x + 6 * w8::kLayerHalfs8x;                 // ... hi + lo planes,
-  const size_t halfs = halfs4 + halfs8 + halfs8x + 4 * w8::kLayerHalfs8;             // and the four post layers (hi plane)
-  DINER_HIP_OK(hipMalloc(w_out, halfs * sizeof(_Float16)));
-  DINER_HIP_OK(hipMalloc(w_lin_out, (size_t)16384 * sizeof(_Float16) + kLinOutWBytes));      // MFMA fragments + the fp32 pack of the vector-ALU lin_out
+// The packed-weight buffer (DinerMlpImpl::hn_w), in _Float16 units: every layer of the network twice, once per kernel family.  This is the
+// one place that says where a plane lives; a kernel gets the start of its lin_in plane and walks on by the per-layer constants.
+//   four-wave order (k_pack_layer_h3n: hi and lo planes -- k_field_pre_h3n / k_field_post_h3n and the training forward):
+//     lin_in | fc_0, fc_1 of the per-view blocks 0-2 | fc_0, fc_1 of the post blocks 3-4
+//   eight-wave order (k_pack_layer_h8: hi plane only -- k_field_pre_h8 / k_field_post_h8), the same three planes
+struct WeightLayout {
+  static constexpr size_t kLinIn4 = h3n::kLinInHalfs, kPerView4 = 6 * h3n::kLayerHalfs, kPost4 = 4 * h3n::kLayerHalfs;
+  static constexpr size_t kLinIn8 = h3n::w8::kLinInHalfs8, kPerView8 = 6 * h3n::w8::kLayerHalfs8, kPost8 = 4 * h3n::w8::kLayerHalfs8;
+  static constexpr size_t oLinIn4 = 0, oPerView4 = oLinIn4 + kLinIn4, oPost4 = oPerView4 + kPerView4;
+  static constexpr size_t oLinIn8 = oPost4 + kPost4, oPerView8 = oLinIn8 + kLinIn8, oPost8 = oPerView8 + kPerView8;
+  static constexpr size_t kTotal = oPost8 + kPost8;
+};
+// the lin_out buffer (hn_w_out): the MFMA fragments [t 16][hl 2][lane 64][8] halfs, behind them the fp32 pack of the vector-ALU lin_out
+constexpr size_t kLinOutFragHalfs = 16 * 2 * 64 * 8;
+
+// w: see WeightLayout; w_lin_out: lin_out fragments + fp32 pack; b_pre: 7 x 512 (x16); b_post: 4 x 512 (x16) + the lin_out bias at
+// scale 1 (padded to 16) + block 2's fc_1 bias (x16).  The caller frees whatever was allocated when this fails.
+int h3n_alloc(_Float16** w, _Float16** w_lin_out, float** b_pre, float** b_post) {
+  DINER_HIP_OK(hipMalloc(w, WeightLayout::kTotal * sizeof(_Float16)));
+  DINER_HIP_OK(hipMalloc(w_lin_out, kLinOutFragHalfs * sizeof(_Float16) + h3n::kLinOutWBytes));
   DINER_HIP_OK(hipMalloc(b_pre, 7 * kHidden * sizeof(float)));
   DINER_HIP_OK(hipMalloc(b_post, (5 * kHidden + 16) * sizeof(float)));
   return 0;
 }
 // train_only: the four-wave layouts, the lin_out packs and the biases (what k_train_fwd_pre / k_train_fwd_post read); the eight-wave
 // layouts keep their old contents
-int h3n_pack(const DinerMlpParams* p, hipStream_t stream, float* w_out_, float* w_lin_out_, float* b_pre_, float* b_post_, bool train_only) {
+int h3n_pack(const DinerMlpParams* p, hipStream_t stream, _Float16* w, _Float16* w_lin_out, float* b_pre, float* b_post, bool train_only) {
   using namespace h3n;
-  float** w_out = &w_out_;
-  float** w_lin_out = &w_lin_out_;
-  float** b_pre = &b_pre_;
-  float** b_post = &b_post_;
-  const size_t halfs4 = h3n_halfs4();
-  const size_t halfs8 = w8::kLinInHalfs8 + 6 * w8::kLayerHalfs8;
-  const size_t halfs8x = w8::kLinInHalfs8x + 6 * w8::kLayerHalfs8x;
+  typedef WeightLayout L;
   auto bias = [&](const float* b, int n, int n_pad, float scale, float* dst) {
     hipLaunchKernelGGL(k_scale_pad, dim3(4), dim3(256), 0, stream, b, n, n_pad, scale, dst);
   };
-  bias(p->lin_in_b, kHidden, kHidden, kScale, *b_pre);
+  bias(p->lin_in_b, kHidden, kHidden, kScale, b_pre);
   for (int b = 0; b < 3; ++b) {
-    bias(p->fc0_b[b], kHidden, kHidden, kScale, *b_pre + kHidden * (1 + 2 * b));
+    bias(p->fc0_b[b], kHidden, kHidden, kScale, b_pre + kHidden * (1 + 2 * b));
     // the fc_1 biases are not added by the per-view kernel: those of blocks 0 and 1 travel in the next block's projected map (see
     // mlp_pack), block 2's is added by the post kernel to the view mean it takes over (the mean of x + b is mean(x) + b)
-    bias(p->fc1_b[b], kHidden, kHidden, 0.0f, *b_pre + kHidden * (2 + 2 * b));
+    bias(p->fc1_b[b], kHidden, kHidden, 0.0f, b_pre + kHidden * (2 + 2 * b));
   }
   for (int b = 3; b < 5; ++b) {
-    bias(p->fc0_b[b], kHidden, kHidden, kScale, *b_post + 2 * kHidden * (b - 3));
-    bias(p->fc1_b[b], kHidden, kHidden, kScale, *b_post + 2 * kHidden * (b - 3) + kHidden);
+    bias(p->fc0_b[b], kHidden, kHidden, kScale, b_post + 2 * kHidden * (b - 3));
+    bias(p->fc1_b[b], kHidden, kHidden, kScale, b_post + 2 * kHidden * (b - 3) + kHidden);
   }
-  bias(p->lin_out_b, 4, 16, 1.0f, *b_post + 4 * kHidden);
-  bias(p->fc1_b[2], kHidden, kHidden, kScale, *b_post + 4 * kHidden + 16);
-  hipLaunchKernelGGL(k_pack_lin_out_h3n, dim3(64), dim3(256), 0, stream, p->lin_out_w, 4, kHidden, kScale,
-                     (_Float16*)*w_lin_out);
+  bias(p->lin_out_b, 4, 16, 1.0f, b_post + 4 * kHidden);
+  bias(p->fc1_b[2], kHidden, kHidden, kScale, b_post + 4 * kHidden + 16);
+  hipLaunchKernelGGL(k_pack_lin_out_h3n, dim3(64), dim3(256), 0, stream, p->lin_out_w, 4, kHidden, kScale, w_lin_out);
   hipLaunchKernelGGL(k_pack_lin_out_valu, dim3(8), dim3(256), 0, stream, p->lin_out_w, 4, kHidden, kInvScale,
-                     reinterpret_cast<float*>(reinterpret_cast<char*>(*w_lin_out) + 32768));
-  _Float16* wp = (_Float16*)*w_out;
-  hipLaunchKernelGGL(k_pack_layer_h3n, dim3(256), dim3(256), 0, stream, p->lin_in_w, kHidden, kDIn, 2, kScale, wp);
-  wp += (size_t)4 * 2 * 8192;
-  for (int b = 0; b < 3; ++b) {
-    hipLaunchKernelGGL(k_pack_layer_h3n, dim3(512), dim3(256), 0, stream, p->fc0_w[b], kHidden, kHidden, 16, kScale, wp);
-    wp += (size_t)4 * 16 * 8192;
-    hipLaunchKernelGGL(k_pack_layer_h3n, dim3(512), dim3(256), 0, stream, p->fc1_w[b], kHidden, kHidden, 16, kScale, wp);
-    wp += (size_t)4 * 16 * 8192;
-  }
-  for (int b = 3; b < 5; ++b) {
-    hipLaunchKernelGGL(k_pack_layer_h3n, dim3(512), dim3(256), 0, stream, p->fc0_w[b], kHidden, kHidden, 16, kScale, wp);
-    wp += (size_t)4 * 16 * 8192;
-    hipLaunchKernelGGL(k_pack_layer_h3n, dim3(512), dim3(256), 0, stream, p->fc1_w[b], kHidden, kHidden, 16, kScale, wp);
-    wp += (size_t)4 * 16 * 8192;
-  }
-  if (train_only) {
-    DINER_LAUNCH_OK();
-    return 0;
-  }
-  {
-    _Float16* w8p = (_Float16*)*w_out + halfs4;
-    hipLaunchKernelGGL(w8::k_pack_layer_h8, dim3(64), dim3(256), 0, stream, p->lin_in_w, kHidden, kDIn, 2, kScale, w8p);
-    w8p += w8::kLinInHalfs8;
-    for (int b = 0; b < 3; ++b) {
-      hipLaunchKernelGGL(w8::k_pack_layer_h8, dim3(512), dim3(256), 0, stream, p->fc0_w[b], kHidden, kHidden, 16, kScale, w8p);
-      w8p += w8::kLayerHalfs8;
-      hipLaunchKernelGGL(w8::k_pack_layer_h8, dim3(512), dim3(256), 0, stream, p->fc1_w[b], kHidden, kHidden, 16, kScale, w8p);
-      w8p += w8::kLayerHalfs8;
-    }
-  }
-  {
-    _Float16* wx = (_Float16*)*w_out + halfs4 + halfs8;
-    hipLaunchKernelGGL(w8::k_pack_layer_h8x, dim3(64), dim3(256), 0, stream, p->lin_in_w, kHidden, kDIn, 2, kScale, wx);
-    wx += w8::kLinInHalfs8x;
-    for (int b = 0; b < 3; ++b) {
-      hipLaunchKernelGGL(w8::k_pack_layer_h8x, dim3(512), dim3(256), 0, stream, p->fc0_w[b], kHidden, kHidden, 16, kScale, wx);
-      wx += w8::kLayerHalfs8x;
-      hipLaunchKernelGGL(w8::k_pack_layer_h8x, dim3(512), dim3(256), 0, stream, p->fc1_w[b], kHidden, kHidden, 16, kScale, wx);
-      wx += w8::kLayerHalfs8x;
-    }
-  }
-  {
-    _Float16* wq = (_Float16*)*w_out + halfs4 + halfs8 + halfs8x;
-    for (int b = 3; b < 5; ++b) {
-      hipLaunchKernelGGL(w8::k_pack_layer_h8, dim3(512), dim3(256), 0, stream, p->fc0_w[b], kHidden, kHidden, 16, kScale, wq);
-      wq += w8::kLayerHalfs8;
-      hipLaunchKernelGGL(w8::k_pack_layer_h8, dim3(512), dim3(256), 0, stream, p->fc1_w[b], kHidden, kHidden, 16, kScale, wq);
-      wq += w8::kLayerHalfs8;
-    }
+                     reinterpret_cast<float*>(w_lin_out + kLinOutFragHalfs));
+  // fc_0, fc_1 of blocks [b0, b1) with `kernel`, one layer of `layer_halfs` behind the other from dst on
+  auto blocks = [&](void (*kernel)(const float*, int, int, int, float, _Float16*), int b0, int b1, size_t layer_halfs, _Float16* dst) {
+    for (int b = b0; b < b1; ++b)
+      for (const float* W : {p->fc0_w[b], p->fc1_w[b]}) {
+        hipLaunchKernelGGL(kernel, dim3(512), dim3(256), 0, stream, W, kHidden, kHidden, 16, kScale, dst);
+        dst += layer_halfs;
+      }
+  };
+  hipLaunchKernelGGL(k_pack_layer_h3n, dim3(256), dim3(256), 0, stream, p->lin_in_w, kHidden, kDIn, 2, kScale, w + L::oLinIn4);
+  blocks(k_pack_layer_h3n, 0, 3, kLayerHalfs, w + L::oPerView4);
+  blocks(k_pack_layer_h3n, 3, 5, kLayerHalfs, w + L::oPost4);
+  if (!train_only) {
+    hipLaunchKernelGGL(w8::k_pack_layer_h8, dim3(64), dim3(256), 0, stream, p->lin_in_w, kHidden, kDIn, 2, kScale, w + L::oLinIn8);
+    blocks(w8::k_pack_layer_h8, 0, 3, w8::kLayerHalfs8, w + L::oPerView8);
+    blocks(w8::k_pack_layer_h8, 3, 5, w8::kLayerHalfs8, w + L::oPost8);
   }
   DINER_LAUNCH_OK();
   return 0;
 }
 int h3n_set_attributes() {
   DINER_HIP_OK(hipFuncSetAttribute((const void*)h3n::w8::k_field_post_h8, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h3n::w8::kLdsBytesPost8));
-  DINER_HIP_OK(hipFuncSetAttribute((const void*)h3n::w8::k_field_pre_h8x, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h3n::w8::kLdsBytes8x));
   DINER_HIP_OK(hipFuncSetAttribute((const void*)h3n::w8::k_field_pre_h8, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h3n::w8::kLdsBytes8));
   DINER_HIP_OK(hipFuncSetAttribute((const void*)h3n::k_train_fwd_pre, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h3n::kLdsBytes));
   DINER_HIP_OK(hipFuncSetAttribute((const void*)h3n::k_train_fwd_post, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h3n::kLdsBytesPost));
@@ -2539,22 +2043,12 @@ int h3n_set_attributes() {
                                    (int)h3n::kLdsBytes));
   DINER_HIP_OK(hipFuncSetAttribute((const void*)h3n::k_field_post_h3n<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                    (int)h3n::kLdsBytes));
-  DINER_HIP_OK(hipFuncSetAttribute((const void*)h3n::k_field_pre_h3n<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)h3n::kLdsBytes));
-  DINER_HIP_OK(hipFuncSetAttribute((const void*)h3n::k_field_post_h3n<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)h3n::kLdsBytes));
   return 0;
 }
-// split = true: f16x3 split products (hi and lo parts, three MFMAs per product); false: plain fp16 operands
-void h3n_launch_pre(const SceneDev& sc, const FieldArgs& fa, const float* w, const float* b, int grid, bool split,
+// split = true: f16x3 split products (hi and lo parts, three MFMAs per product) on four waves; false: plain fp16 operands on eight
+void h3n_launch_pre(const SceneDev& sc, const FieldArgs& fa, const _Float16* w, const float* b, int grid, bool split,
                     unsigned* tile_counter, hipStream_t stream, const SaveActs* sv) {
-  const _Float16* w8p = (const _Float16*)w + ((size_t)4 * 2 * 8192 + (size_t)(6 + 4) * 4 * 16 * 8192);
-  // DINER_F16_W8=0: the plain-fp16 mode on the 4-wave kernel (A/B measurement aid)
-  static const bool use_w8 = [] { const char* e = getenv("DINER_F16_W8"); return !(e && *e == '0'); }();
-  const _Float16* w8xp = w8p + (h3n::w8::kLinInHalfs8 + 6 * h3n::w8::kLayerHalfs8);
-  // DINER_F16X3_W8=1: the f16x3 mode on the eight-wave kernel (round 5 experiment; default off until measured)
-  static const bool use_w8x = [] { const char* e = getenv("DINER_F16X3_W8"); return e && *e == '1'; }();
-  h3n::Args a{fa, (const _Float16*)w, w8p, w8xp, b, nullptr, tile_counter,
+  h3n::Args a{fa, w + WeightLayout::oLinIn4, w + WeightLayout::oLinIn8, b, nullptr, tile_counter,
               h3n::QueueMap::make((fa.P + kPtsPerWave - 1) / kPtsPerWave, fa.K, fa.rays != nullptr && fa.xyz == nullptr && fa.direct_feat == nullptr)};
 #ifdef DINER_HN_PROF
   static unsigned long long* prof = nullptr;
@@ -2564,10 +2058,8 @@ void h3n_launch_pre(const SceneDev& sc, const FieldArgs& fa, const float* w, con
 #endif
   if (sv) {          // training forward: the f16x3 kernel storing the pre-activations
     hipLaunchKernelGGL(h3n::k_train_fwd_pre, dim3(grid), dim3(256), h3n::kLdsBytes, stream, sc, a, *sv);
-  } else if (split && use_w8x) hipLaunchKernelGGL(h3n::w8::k_field_pre_h8x, dim3(grid), dim3(512), h3n::w8::kLdsBytes8x, stream, sc, a);
-  else if (split) hipLaunchKernelGGL(h3n::k_field_pre_h3n<true>, dim3(grid), dim3(256), h3n::kLdsBytes, stream, sc, a);
-  else if (use_w8) hipLaunchKernelGGL(h3n::w8::k_field_pre_h8, dim3(grid), dim3(512), h3n::w8::kLdsBytes8, stream, sc, a);
-  else hipLaunchKernelGGL(h3n::k_field_pre_h3n<false>, dim3(grid), dim3(256), h3n::kLdsBytes, stream, sc, a);
+  } else if (split) hipLaunchKernelGGL(h3n::k_field_pre_h3n<true>, dim3(grid), dim3(256), h3n::kLdsBytes, stream, sc, a);
+  else hipLaunchKernelGGL(h3n::w8::k_field_pre_h8, dim3(grid), dim3(512), h3n::w8::kLdsBytes8, stream, sc, a);
 #ifdef DINER_HN_PROF
   unsigned long long h[32];
   static const char* fnames[4] = {"  load_point", "  project + depth tap", "  features", "  bilinear taps"};
@@ -2584,17 +2076,11 @@ void h3n_launch_pre(const SceneDev& sc, const FieldArgs& fa, const float* w, con
 #endif
 }
 
-// w: the n-split pack (post layers follow the per-view ones); w_lin_out: the lin_out fragments
-void h3n_launch_post(const PostArgs& pa, const float* w, const float* w_lin_out, int grid, bool split, unsigned* tile_counter,
+// w: see WeightLayout; w_lin_out: the lin_out fragments + fp32 pack
+void h3n_launch_post(const PostArgs& pa, const _Float16* w, const _Float16* w_lin_out, int grid, bool split, unsigned* tile_counter,
                      hipStream_t stream, const SaveActs* sv) {
-  const _Float16* wn = (const _Float16*)w + (size_t)4 * 2 * 8192 + (size_t)6 * 4 * 16 * 8192;
-  const _Float16* wo = (const _Float16*)w_lin_out;
   const long long n_t16 = (pa.P + kPtsPerWave - 1) / kPtsPerWave;
-  const _Float16* w8post = (const _Float16*)w + ((size_t)4 * 2 * 8192 + (size_t)(6 + 4) * 4 * 16 * 8192) + (h3n::w8::kLinInHalfs8 + 6 * h3n::w8::kLayerHalfs8) +
-                           (h3n::w8::kLinInHalfs8x + 6 * h3n::w8::kLayerHalfs8x);
-  // DINER_F16_W8=0 / DINER_F16_POST_W8=0: the plain-fp16 post kernel on four waves (A/B measurement aids)
-  static const bool use_w8 = [] { const char* e = getenv("DINER_F16_W8"); const char* f = getenv("DINER_F16_POST_W8"); return !(e && *e == '0') && !(f && *f == '0'); }();
-  h3n::PostArgsN a{pa, wn, w8post, wo, nullptr, tile_counter, h3n::QueueMap::make((n_t16 + 3) / 4, 0, false)};
+  h3n::PostArgsN a{pa, w + WeightLayout::oPost4, w + WeightLayout::oPost8, w_lin_out, nullptr, tile_counter, h3n::QueueMap::make((n_t16 + 3) / 4, 0, false)};
 #ifdef DINER_HN_PROF
   static unsigned long long* prof = nullptr;
   if (!prof) hipMalloc(&prof, 32 * sizeof(unsigned long long));
@@ -2604,8 +2090,7 @@ void h3n_launch_post(const PostArgs& pa, const float* w, const float* w_lin_out,
   if (sv) {
     hipLaunchKernelGGL(h3n::k_train_fwd_post, dim3(grid), dim3(256), h3n::kLdsBytesPost, stream, a, *sv);
   } else if (split) hipLaunchKernelGGL(h3n::k_field_post_h3n<true>, dim3(grid), dim3(256), h3n::kLdsBytesPost, stream, a);
-  else if (use_w8) hipLaunchKernelGGL(h3n::w8::k_field_post_h8, dim3(grid), dim3(512), h3n::w8::kLdsBytesPost8, stream, a);
-  else hipLaunchKernelGGL(h3n::k_field_post_h3n<false>, dim3(grid), dim3(256), h3n::kLdsBytesPost, stream, a);
+  else hipLaunchKernelGGL(h3n::w8::k_field_post_h8, dim3(grid), dim3(512), h3n::w8::kLdsBytesPost8, stream, a);
 #ifdef DINER_HN_PROF
   unsigned long long h[32];
   hipStreamSynchronize(stream);
