@@ -81,6 +81,24 @@ struct RayCams {
   RayCam cam[kMaxRayCams];
 };
 
+// one ray of camera c at pixel (row i, column j): [origin, world direction, near, far] -- the arithmetic both ray kernels share, so
+// that a pixel's row is the same bits whichever of them writes it
+__device__ __forceinline__ void write_ray(const RayCam& c, int i, int j, float* __restrict__ o) {
+  const float x = __fdiv_rn(__fsub_rn((float)j + 0.5f, c.cx), c.fx);       // cam_geometry.py:25-31
+  const float y = __fdiv_rn(__fsub_rn((float)i + 0.5f, c.cy), c.fy);
+  const float nrm = __fsqrt_rn(__fadd_rn(__fadd_rn(__fmul_rn(x, x), __fmul_rn(y, y)), 1.0f));
+  const float dx = __fdiv_rn(x, nrm), dy = __fdiv_rn(y, nrm), dz = __fdiv_rn(1.0f, nrm);
+  o[0] = c.o[0];
+  o[1] = c.o[1];
+  o[2] = c.o[2];
+  // d_w = R^T d_cam (:37-38)
+  o[3] = __fmaf_rn(c.R[6], dz, __fmaf_rn(c.R[3], dy, __fmul_rn(c.R[0], dx)));
+  o[4] = __fmaf_rn(c.R[7], dz, __fmaf_rn(c.R[4], dy, __fmul_rn(c.R[1], dx)));
+  o[5] = __fmaf_rn(c.R[8], dz, __fmaf_rn(c.R[5], dy, __fmul_rn(c.R[2], dx)));
+  o[6] = c.zn;
+  o[7] = c.zf;
+}
+
 // rays [ray0, ray0 + n) of each camera's row-major (H, W) list: [origin, world direction, near, far]
 __global__ void k_gen_rays(RayCams cams, int B, int W, long long ray0, long long n, float* __restrict__ out) {
   const long long total = (long long)B * n;
@@ -89,21 +107,20 @@ __global__ void k_gen_rays(RayCams cams, int B, int W, long long ray0, long long
     const int b = (int)(idx / n);
     const long long r = ray0 + (idx - (long long)b * n);
     const int i = (int)(r / W), j = (int)(r - (long long)i * W);
-    const RayCam& c = cams.cam[b];
-    const float x = __fdiv_rn(__fsub_rn((float)j + 0.5f, c.cx), c.fx);       // cam_geometry.py:25-31
-    const float y = __fdiv_rn(__fsub_rn((float)i + 0.5f, c.cy), c.fy);
-    const float nrm = __fsqrt_rn(__fadd_rn(__fadd_rn(__fmul_rn(x, x), __fmul_rn(y, y)), 1.0f));
-    const float dx = __fdiv_rn(x, nrm), dy = __fdiv_rn(y, nrm), dz = __fdiv_rn(1.0f, nrm);
-    float* o = out + idx * 8;
-    o[0] = c.o[0];
-    o[1] = c.o[1];
-    o[2] = c.o[2];
-    // d_w = R^T d_cam (:37-38)
-    o[3] = __fmaf_rn(c.R[6], dz, __fmaf_rn(c.R[3], dy, __fmul_rn(c.R[0], dx)));
-    o[4] = __fmaf_rn(c.R[7], dz, __fmaf_rn(c.R[4], dy, __fmul_rn(c.R[1], dx)));
-    o[5] = __fmaf_rn(c.R[8], dz, __fmaf_rn(c.R[5], dy, __fmul_rn(c.R[2], dx)));
-    o[6] = c.zn;
-    o[7] = c.zf;
+    write_ray(cams.cam[b], i, j, out + idx * 8);
+  }
+}
+
+// rays at listed pixels: pix (B, n) row-major pixel indices of each camera's (H, W) image -> out (B, n, 8).  An index outside
+// [0, W H) is clamped (the caller's error; nothing is read or written out of bounds).
+__global__ void k_gen_rays_at(RayCams cams, int B, int W, int HW, const int* __restrict__ pix, long long n, float* __restrict__ out) {
+  const long long total = (long long)B * n;
+  for (long long idx = blockIdx.x * (long long)blockDim.x + threadIdx.x; idx < total;
+       idx += (long long)gridDim.x * blockDim.x) {
+    const int b = (int)(idx / n);
+    const int r = min(max(pix[idx], 0), HW - 1);
+    const int i = r / W, j = r - i * W;
+    write_ray(cams.cam[b], i, j, out + idx * 8);
   }
 }
 
@@ -176,15 +193,8 @@ extern "C" int diner_depth2normal_f32(const float* dmap, const float* K, int N, 
   return 0;
 }
 
-extern "C" int diner_gen_rays_f32(const float* extrinsics, const float* intrinsics, const float* z_near,
-                                  const float* z_far, int B, int W, int H, long long ray0, long long n_rays, float* out,
-                                  void* stream) {
-  DINER_CHECK_ARG(extrinsics && intrinsics && z_near && z_far && (out || B == 0 || n_rays == 0), "gen_rays: null pointer argument");
-  DINER_CHECK_ARG(B >= 0 && B <= kMaxRayCams, "gen_rays: %d cameras, at most %d per call", B, kMaxRayCams);
-  DINER_CHECK_ARG(W > 0 && H > 0, "gen_rays: bad image size %d x %d", W, H);
-  DINER_CHECK_ARG(ray0 >= 0 && n_rays >= 0 && ray0 + n_rays <= (long long)W * H,
-                  "gen_rays: ray range [%lld, %lld) outside the %d x %d image", ray0, ray0 + n_rays, W, H);
-  if (B == 0 || n_rays == 0) return 0;
+// kernel-argument cameras from the host arrays of the C ABI
+static RayCams make_ray_cams(const float* extrinsics, const float* intrinsics, const float* z_near, const float* z_far, int B) {
   RayCams cams;
   for (int b = 0; b < B; ++b) {
     const float* E = extrinsics + 16 * b;
@@ -201,9 +211,37 @@ extern "C" int diner_gen_rays_f32(const float* extrinsics, const float* intrinsi
     c.zn = z_near[b];
     c.zf = z_far[b];
   }
+  return cams;
+}
+
+extern "C" int diner_gen_rays_f32(const float* extrinsics, const float* intrinsics, const float* z_near,
+                                  const float* z_far, int B, int W, int H, long long ray0, long long n_rays, float* out,
+                                  void* stream) {
+  DINER_CHECK_ARG(extrinsics && intrinsics && z_near && z_far && (out || B == 0 || n_rays == 0), "gen_rays: null pointer argument");
+  DINER_CHECK_ARG(B >= 0 && B <= kMaxRayCams, "gen_rays: %d cameras, at most %d per call", B, kMaxRayCams);
+  DINER_CHECK_ARG(W > 0 && H > 0, "gen_rays: bad image size %d x %d", W, H);
+  DINER_CHECK_ARG(ray0 >= 0 && n_rays >= 0 && ray0 + n_rays <= (long long)W * H,
+                  "gen_rays: ray range [%lld, %lld) outside the %d x %d image", ray0, ray0 + n_rays, W, H);
+  if (B == 0 || n_rays == 0) return 0;
+  const RayCams cams = make_ray_cams(extrinsics, intrinsics, z_near, z_far, B);
   const long long total = (long long)B * n_rays;
   const int blocks = (int)((total + 255) / 256 > 16384 ? 16384 : (total + 255) / 256);
   hipLaunchKernelGGL(k_gen_rays, dim3(blocks), dim3(256), 0, (hipStream_t)stream, cams, B, W, ray0, n_rays, out);
+  DINER_LAUNCH_OK();
+  return 0;
+}
+
+extern "C" int diner_gen_rays_at_f32(const float* extrinsics, const float* intrinsics, const float* z_near, const float* z_far,
+                                     int B, int W, int H, const int* pix, long long n, float* out, void* stream) {
+  DINER_CHECK_ARG(extrinsics && intrinsics && z_near && z_far && ((pix && out) || B == 0 || n == 0), "gen_rays_at: null pointer argument");
+  DINER_CHECK_ARG(B >= 0 && B <= kMaxRayCams, "gen_rays_at: %d cameras, at most %d per call", B, kMaxRayCams);
+  DINER_CHECK_ARG(W > 0 && H > 0 && (long long)W * H <= 0x7fffffffLL, "gen_rays_at: bad image size %d x %d", W, H);
+  DINER_CHECK_ARG(n >= 0 && n <= 0x7fffffffLL, "gen_rays_at: %lld pixels per camera, need 0 <= n < 2^31", n);
+  if (B == 0 || n == 0) return 0;
+  const RayCams cams = make_ray_cams(extrinsics, intrinsics, z_near, z_far, B);
+  const long long total = (long long)B * n;
+  const int blocks = (int)((total + 255) / 256 > 16384 ? 16384 : (total + 255) / 256);
+  hipLaunchKernelGGL(k_gen_rays_at, dim3(blocks), dim3(256), 0, (hipStream_t)stream, cams, B, W, W * H, pix, n, out);
   DINER_LAUNCH_OK();
   return 0;
 }

@@ -593,6 +593,33 @@ def gen_rays(extrinsics, intrinsics, W, H, z_near, z_far, device, ray0=0, n_rays
     return out
 
 
+def gen_rays_at(extrinsics, intrinsics, W, H, z_near, z_far, pix):
+    """gen_rays at listed pixels: pix (B, n) int32 on a HIP device (row-major pixel indices y * W + x of each camera's image)
+    -> (B, n, 8); a row is bit-identical to the row gen_rays writes for that pixel.  Indices outside [0, W H) are clamped.  Camera
+    tensors may live anywhere (they are read on the host; host tensors keep the call free of synchronisation)."""
+    if not pix.is_cuda:
+        raise RuntimeError("diner_amd: gen_rays_at generates on a HIP device; there is no CPU fallback")
+    if pix.dtype != torch.int32:
+        raise TypeError(f"diner_amd: gen_rays_at expects int32 pixel indices, got {pix.dtype}")
+    E = extrinsics.detach().to("cpu", torch.float32).contiguous()
+    Km = intrinsics.detach().to("cpu", torch.float32).contiguous()
+    B = E.shape[0]
+    zn = torch.as_tensor(z_near, dtype=torch.float32).detach().to("cpu").reshape(-1).expand(B).contiguous()
+    zf = torch.as_tensor(z_far, dtype=torch.float32).detach().to("cpu").reshape(-1).expand(B).contiguous()
+    if tuple(E.shape) != (B, 4, 4) or tuple(Km.shape) != (B, 3, 3) or pix.dim() != 2 or pix.shape[0] != B:
+        raise ValueError(f"diner_amd: gen_rays_at expects (B,4,4) extrinsics, (B,3,3) intrinsics and (B,n) pixels, got {tuple(E.shape)}, "
+                         f"{tuple(Km.shape)}, {tuple(pix.shape)}")
+    pix = pix.contiguous()
+    n = int(pix.shape[1])
+    out = torch.empty(B, n, 8, device=pix.device, dtype=torch.float32)
+    with torch.cuda.device(pix.device):
+        for b0 in range(0, B, 16):
+            b1 = min(B, b0 + 16)
+            _lib.check(lib.diner_gen_rays_at_f32(E[b0:b1].data_ptr(), Km[b0:b1].data_ptr(), zn[b0:b1].data_ptr(), zf[b0:b1].data_ptr(),
+                                                 b1 - b0, int(W), int(H), _ptr(pix[b0:b1]), n, _ptr(out[b0:b1]), _stream()))
+    return out
+
+
 # FLOPs of the two field kernels per sample point (SURVEY.md section 8d): NV views x (lin_in + 3 x (lin_z, fc_0, fc_1))
 # before the view mean, 2 x (fc_0, fc_1) + lin_out after it.
 FLOP_PRE_PER_POINT_REFERENCE = 2 * 4 * (55 * 512 + 9 * 512 * 512)     # as the reference computes it (SURVEY 8d)

@@ -299,3 +299,59 @@ def metric_pair(kind, H, W, seed):
         p.reshape(-1)[idx] += np.where(p.reshape(-1)[idx] == 255, -1, 1)
         return p.astype(np.uint8), g
     raise ValueError(f"metric_pair: unknown kind {kind!r}")
+
+
+# ---- inputs of the training-objective tests (G25, tools/make_golden_objective.py) ----------------------------------------------
+# (kind, SB, s, n_downsampling, w_antibias, B, seed) of every case G25 pins; objective_case() regenerates pred / gt (numpy only).
+# s = 0: the random-pixel mode (no patch, no anti-bias term).
+OBJECTIVE_CASES = (
+    ("patch", 4, 64, 3, 1.0, 4096, 1), ("patch", 4, 64, 3, 5.0, 4096, 1), ("patch", 2, 32, 2, 1.0, 1024, 2),
+    ("patch", 1, 64, 0, 1.0, 4096, 3), ("zero_cells", 2, 32, 3, 1.0, 1024, 4), ("random", 4, 0, 0, 0.0, 128, 5),
+)
+
+
+def objective_case(kind, SB, s, n_downsampling, B, seed):
+    """Seeded (pred, gt) float32 (SB, B, 3) in [0, 1].  Uniform draws combined by exactly rounded float64 operations only, so the bytes
+    are the same on every host.  "patch" / "random": pred = 0.7 gt + 0.3 noise + a per-object, per-channel offset; "zero_cells": the
+    same with pred == gt on every other 2^n x 2^n cell of the s x s patch (a checkerboard), which makes those cells' mean difference
+    exactly zero."""
+    import numpy as np
+    rs = np.random.RandomState(seed)
+    gt = rs.random_sample((SB, B, 3))
+    noise = rs.random_sample((SB, B, 3))
+    off = (rs.random_sample((SB, 1, 3)) - 0.5) * 0.125
+    pred = np.clip(0.7 * gt + 0.3 * noise + off, 0.0, 1.0).astype(np.float32)
+    gt = gt.astype(np.float32)
+    if kind == "zero_cells":
+        c = 1 << n_downsampling
+        yy, xx = np.mgrid[0:s, 0:s]
+        same = (((yy // c) + (xx // c)) % 2 == 0).reshape(-1)
+        pred[:, same] = gt[:, same]
+    elif kind not in ("patch", "random"):
+        raise ValueError(f"objective_case: unknown kind {kind!r}")
+    return pred, gt
+
+
+# (H, W, s, seed) of the foreground masks G25 pins for the patch sampler; each has 6 objects
+PATCH_CASES = ((48, 56, 16, 11), (40, 40, 32, 12), (33, 47, 15, 13))
+
+
+def patch_case(H, W, s, seed):
+    """Seeded (fg (6, H, W) float32, u (6,) float32) for the patch sampler.  The weights are multiples of 2^-16 (their double sums
+    are exact in any order): object 0 a disc of fractional weights, 1 all zero, 2 non-zero only inside the border the sampler ignores
+    (its padded mask is all zero), 3 a binary box, 4 the disc mirrored, 5 fractional weights everywhere.  u covers 0, the largest
+    float32 below 1 and interior values."""
+    import numpy as np
+    rs = np.random.RandomState(seed)
+    yy, xx = np.mgrid[0:H, 0:W]
+    fg = np.zeros((6, H, W), np.float32)
+    frac = (rs.randint(0, 65536, (H, W)) / 65536.0).astype(np.float32)
+    fg[0] = np.where((yy - H / 2) ** 2 + (xx - W / 2) ** 2 < (0.45 * min(H, W)) ** 2, frac, 0)
+    pad = (s + 1) // 2
+    border = (yy < pad) | (yy >= H - pad) | (xx < pad) | (xx >= W - pad)
+    fg[2] = np.where(border, frac, 0)
+    fg[3, H // 4:H - H // 4, W // 4:W - W // 4] = 1.0
+    fg[4] = fg[0, ::-1, ::-1]
+    fg[5] = frac
+    u = np.array([0.37, 0.5, 0.25, 0.99999994, 0.0, 0.81], np.float32)
+    return fg, u

@@ -438,6 +438,38 @@ int diner_image_metrics_u8(const unsigned char* pred, const unsigned char* gt, i
                            void* workspace, double* out, void* stream);
 int diner_image_metrics_f32(const float* pred, const float* gt, int N, int H, int W, void* workspace, double* out, void* stream);
 
+/* ---- the training objective (DINER.calc_losses around renderer.forward, reference src/models/diner.py:217-290) -------------------
+ * New symbols without an ABI bump; enqueue-only on `stream`, no allocation, no host synchronisation, no floating-point atomics (the
+ * outputs are bit-identical from run to run); bad arguments return DINER_E_INVALID before any device work.
+ *
+ * diner_sample_patch (diner.py:233-247): fg (SB,H,W) fp32 foreground weights (>= 0; a value that is not > 0 counts as 0), patch side s,
+ *   u (SB) uniform numbers in [0, 1) or NULL -> Philox4x32-10 keyed by (seed, step, object).  With pad = (s + 1) / 2 the weights of the
+ *   first and last pad rows and columns count as 0; the centre is the first pixel in row-major order whose inclusive prefix sum of
+ *   weights (double; per-thread runs of consecutive pixels, then the threads in order) exceeds u * total.
+ *   pix_idcs (SB, s*s) int32: the row-major block of pixels (cx - pad + j, cy - pad + i), i the slow index, as y * W + x;
+ *   centres (SB,2) int32 (x, y); flags (SB) int32: 1 for an object whose padded mask is all zero (it gets the image centre
+ *   (W / 2, H / 2)), else 0.  s + 1 > min(H, W) is refused.
+ * diner_gen_rays_at_f32: diner_gen_rays_f32 at listed pixels: pix (B, n) int32 device (y * W + x) -> out (B, n, 8); a row is
+ *   bit-identical to the row diner_gen_rays_f32 writes for that pixel.  Indices outside [0, W H) are clamped.  B <= 16 per call.
+ * diner_objective_f32: losses (3) double = {rgb_fine, antibias, w_mse rgb_fine + w_antibias antibias} and d_pred (SB,B,3) fp32 = the
+ *   gradient of losses[2] with respect to pred (SB,B,3).  Ground truth: gt (SB,B,3), or gt == NULL and images (SB,3,H,W) with
+ *   pix (SB,B) int32 (gathered in the kernel, indices clamped; H, W unused with gt).
+ *   rgb_fine = mean (p - g)^2 over SB B 3 values (MSELoss).  With a patch (s > 0, B == s*s, s a multiple of 2^n_downsampling, s <= 1024)
+ *   D[o, ch, cell] = the mean of p - g over the 2^n x 2^n pixels of a cell of the patch viewed as (SB,3,s,s) (diner.py:281-282) and
+ *   antibias = mean |D| (AntibiasLoss with L1Loss), gradient sign(D) / (4^n SB 3 (s / 2^n)^2) per pixel, sign(0) = 0.  s == 0 is the
+ *   random-pixel mode (diner.py:229-230): antibias = 0 and w_antibias must be 0.  p - g rounds to fp32, every sum is double (partial
+ *   sums per workgroup in `workspace`, diner_objective_workspace_bytes(SB, B, s, n_downsampling) bytes -- 0 for sizes the entry
+ *   refuses -- added in a fixed order by a finalising launch).  w_mse = 1 is DINER's objective; w_mse = 0, w_antibias = 1 is
+ *   AntibiasLoss alone. */
+int diner_sample_patch(const float* fg, int SB, int H, int W, int s, const float* u, uint64_t seed, long long step, int* pix_idcs,
+                       int* centres, int* flags, void* stream);
+int diner_gen_rays_at_f32(const float* extrinsics, const float* intrinsics, const float* z_near, const float* z_far, int B,
+                          int W, int H, const int* pix, long long n, float* out, void* stream);
+size_t diner_objective_workspace_bytes(int SB, int B, int s, int n_downsampling);
+int diner_objective_f32(const float* pred, const float* gt, const float* images, const int* pix, int SB, int B, int H, int W, int s,
+                        int n_downsampling, double w_mse, double w_antibias, void* workspace, double* losses, float* d_pred,
+                        void* stream);
+
 /* ---- measurement aid (bench.py): per-kernel durations of the two field kernels ------------------
  * With profiling enabled every field call brackets k_field_pre / k_field_post with HIP events on the
  * launch stream; diner_profile_collect waits for them, returns the summed durations (ms), the number

@@ -11,6 +11,7 @@
 #   l512-prof [rows]           phase timer of lin512_body (needs libdiner_hip_l512prof.so: build_variant('l512prof', ['DINER_L512_PROF']))
 #   bench [bench args]         bench.py (default --gpus 1 --steps 20 --warmup 5 --full) -> bench_line.json in the output folder + a digest on stdout
 #   profile <tag> [bench args] rocprofv3 stats + PMC passes of the bench (tools/profile_round.sh)
+#   objective-time [args]      tools/time_objective.py: calc_losses against the torch expression of the objective, alternating (stdout; keep it as profiles/objective_step_ab.txt)
 #   smoke                      __graft_entry__.smoke()
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}" || exit 1
 mkdir -p gpurun_out
@@ -59,6 +60,8 @@ print("roofline", l["roofline"]["frac"], l["roofline"]["avg_launch_ms"])
 PY
     ;;
   profile) bash tools/profile_round.sh "$@" ;;
+  objective-time)
+    timeout 900 python tools/time_objective.py "$@" 2>&1 | grep -v amdgpu.ids ;;
   smoke) python __graft_entry__.py smoke ;;
   *) echo "unknown job '$job' (see the header of tools/job.sh)"; exit 2 ;;
 esac
