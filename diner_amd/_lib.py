@@ -58,6 +58,16 @@ SIGNATURES = {
                                             C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "diner_field_from_points_f32": (C.c_int, [C.POINTER(DinerScene), C.c_void_p, C.c_void_p, C.c_void_p,
                                               C.c_longlong, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "diner_scene_proj_views_bytes": (C.c_size_t, [C.POINTER(DinerScene)]),
+    "diner_scene_prepare_views_f32": (C.c_int, [C.POINTER(DinerScene), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "diner_field_views_workspace_bytes": (C.c_size_t, [C.c_longlong]),
+    "diner_field_from_rays_views_f32": (C.c_int, [C.POINTER(DinerScene), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                                  C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "diner_field_from_points_views_f32": (C.c_int, [C.POINTER(DinerScene), C.c_void_p, C.c_void_p, C.c_void_p,
+                                                    C.c_longlong, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "diner_render_views_f32": (C.c_int, [C.POINTER(DinerScene), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                         C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p]),
     "diner_mlp_forward_workspace_bytes": (C.c_size_t, [C.c_longlong]),
     "diner_mlp_forward_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p]),
     "diner_composite_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,

@@ -69,6 +69,33 @@ int make_scene_dev(const DinerScene* s, SceneDevWide* out) {
   return fill_scene_dev(s, out);
 }
 
+int make_group_scene_dev(const DinerScene* s, int g, SceneDev* out, int* n_live) {
+  DINER_CHECK_ARG(s != nullptr && s->nv >= 1 && s->nv <= kMaxViewsWide, "scene: nv outside [1,%d]", kMaxViewsWide);
+  const int v0 = kMaxViews * g;
+  DINER_CHECK_ARG(g >= 0 && v0 < s->nv, "scene: view group %d of a scene with %d views", g, s->nv);
+  const int live = s->nv - v0 < kMaxViews ? s->nv - v0 : kMaxViews;
+  DinerScene grp = *s;
+  grp.nv = live;
+  grp.poses_host = s->poses_host + 16 * v0;
+  grp.focal_host = s->focal_host + 2 * v0;
+  grp.c_host = s->c_host + 2 * v0;
+  const size_t hw_f = (size_t)s->Hf * s->Wf, hw_s = (size_t)s->Hs * s->Ws;
+  if (s->latent_cl) grp.latent_cl = s->latent_cl + (size_t)v0 * hw_f * s->C;
+  if (s->depth) grp.depth = s->depth + (size_t)v0 * hw_s;
+  if (s->depth_std) grp.depth_std = s->depth_std + (size_t)v0 * hw_s;
+  if (s->normals) grp.normals = s->normals + (size_t)v0 * 3 * hw_s;
+  int rc = fill_scene_dev(&grp, out);
+  if (rc) return rc;
+  for (int v = live; v < kMaxViews; ++v) {      // dead columns: the group's first camera
+    memcpy(out->R[v], out->R[0], sizeof(out->R[0]));
+    memcpy(out->t[v], out->t[0], sizeof(out->t[0]));
+    memcpy(out->focal[v], out->focal[0], sizeof(out->focal[0]));
+    memcpy(out->c[v], out->c[0], sizeof(out->c[0]));
+  }
+  *n_live = live;
+  return 0;
+}
+
 int check_mlp_config(const DinerMlpParams* p, const char* who, bool poscode) {
   DINER_CHECK_ARG(p && p->lin_in_w && p->lin_in_b && p->lin_out_w && p->lin_out_b && p->fc0_w && p->fc0_b && p->fc1_w &&
                       p->fc1_b && p->lin_z_w && p->lin_z_b, "%s: parameter pointers missing", who);

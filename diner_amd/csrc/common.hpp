@@ -70,6 +70,10 @@ using SceneDevWide = SceneDevT<kMaxViewsWide>;
 // SceneDev: 1 <= nv <= 4 (5..16 views: DINER_E_UNSUPPORTED, the entry is built for four); SceneDevWide: 1 <= nv <= 16.
 int make_scene_dev(const DinerScene* s, SceneDev* out);
 int make_scene_dev(const DinerScene* s, SceneDevWide* out);
+// Group g (views 4 g .. 4 g + n_live - 1, n_live <= 4) of a scene with 1 .. 16 views as the four-camera kernel argument of the view-group
+// field kernels: the map pointers start at the group's first view, the camera slots of a partial group's dead columns repeat its first
+// view.  The caller has checked nv and the host camera arrays.
+int make_group_scene_dev(const DinerScene* s, int g, SceneDev* out, int* n_live);
 // The refusal of an entry built for at most four source views, for entries that do not build a SceneDev (host-only, before any
 // device work): 0, DINER_E_UNSUPPORTED for 5..16 views, DINER_E_INVALID outside [1, 16].
 int check_fused_views(int nv, const char* who);

@@ -160,6 +160,47 @@ __device__ __forceinline__ void view_mean_store(float* exch, const f32x4 (&x)[kT
 #undef DINER_ROUND
 }
 
+// One group of up to four source views of a scene with any number of them (the view-group instances k_field_views_f32 / k_field_views_h3n):
+// the mean over the views is linear, so an NV-view scene is ceil(NV / 4) launches of the four-view per-view body, each adding
+// scale * (sum over its live views) into the same hand-over.  Column group w of a launch is view 4 g + w of the scene; the columns
+// w >= n_live of a partial group recompute view 0 of the group (valid addresses, nothing new) and are left out of the sum by selection.
+struct ViewGroup {
+  int n_live;          // live views of this group, 1 .. 4
+  int first;           // != 0: this launch writes the hand-over, else it adds to what the earlier groups left
+  float scale;         // 1 / NV (the f16x3 kernel: kInvScale / NV, its accumulators hold 16 x the activations)
+};
+
+// view_mean_store for a view group: the sum runs over the live views only (wave-uniform selection: an inf / NaN of a dead column never
+// enters it, one of a live column always does), and a later group adds its share to the hand-over of the earlier ones.
+__device__ __forceinline__ void view_group_store(float* exch, const f32x4 (&x)[kTiles], const ViewGroup& vg, f32x4* __restrict__ out_tile,
+                                                 int wave, int lane) {
+  f32x4* e = reinterpret_cast<f32x4*>(exch);
+  int n_live = vg.n_live, first = vg.first;      // re-read from the kernel arguments here: nothing of the group lives across the GEMMs
+  float scale = vg.scale;
+  asm volatile("" : "+s"(n_live), "+s"(first), "+s"(scale));
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    __builtin_amdgcn_s_waitcnt(0xc07f);       // lgkmcnt(0): my reads of the previous round are done
+    __builtin_amdgcn_s_barrier();
+#pragma unroll
+    for (int j = 0; j < 8; ++j) e[(wave * 8 + j) * 64 + lane] = x[8 * r + j];
+    __builtin_amdgcn_s_waitcnt(0xc07f);
+    __builtin_amdgcn_s_barrier();
+#pragma unroll
+    for (int jj = 0; jj < 2; ++jj) {
+      const int j = 2 * wave + jj;
+      f32x4 s = e[(0 * 8 + j) * 64 + lane];
+      if (n_live > 1) s += e[(1 * 8 + j) * 64 + lane];
+      if (n_live > 2) s += e[(2 * 8 + j) * 64 + lane];
+      if (n_live > 3) s += e[(3 * 8 + j) * 64 + lane];
+      s *= scale;
+      f32x4* o = out_tile + (8 * r + j) * 64 + lane;
+      if (!first) s += *o;
+      *o = s;
+    }
+  }
+}
+
 // bilinear taps of one (point, view): float offsets into a channels-last (.., 512) map + blend weights
 struct Taps {
   size_t off[4];

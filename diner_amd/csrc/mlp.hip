@@ -88,7 +88,7 @@ int h3n_alloc(_Float16** w, _Float16** w_out, float** b_pre, float** b_post);
 int h3n_pack(const DinerMlpParams* p, hipStream_t stream, _Float16* w, _Float16* w_out, float* b_pre, float* b_post, bool train_only);
 int h3n_set_attributes();
 void h3n_launch_pre(const SceneDev& sc, const FieldArgs& fa, const _Float16* w, const float* b, int grid, bool split,
-                    unsigned* tile_counter, hipStream_t stream, const SaveActs* sv = nullptr);
+                    unsigned* tile_counter, hipStream_t stream, const SaveActs* sv = nullptr, const ViewGroup* vg = nullptr);
 void h3n_launch_post(const PostArgs& pa, const _Float16* w, const _Float16* w_out, int grid, bool split, unsigned* tile_counter,
                      hipStream_t stream, const SaveActs* sv = nullptr);
 
@@ -457,6 +457,56 @@ __global__ __launch_bounds__(256, 1) void k_field_pre(SceneDev sc, FieldArgs a) 
   ws.drain();   // the last (unused) stage DMAs must land before the LDS is released
 }
 
+// The view-group instance of k_field_pre: one group of up to four views of a scene with 1..3 or 5..16 of them, one launch per group
+// (launch_field_views; ViewGroup in field_common.hpp).  A dead column of a partial group recomputes the group's first view: valid
+// addresses, finite values, and view_group_store leaves it out of the sum.  (A kernel of its own, not a template parameter of
+// k_field_pre's body: as a template the shipped instance came out with another register allocation.)
+__global__ __launch_bounds__(256, 1) void k_field_views_f32(SceneDev sc, FieldArgs a, ViewGroup vg) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  const int q = lane >> 4, pt = lane & 15;
+  const int v = wave < vg.n_live ? wave : 0;            // one wave per source view of the group
+  const long long n_tiles = (a.P + kPtsPerWave - 1) / kPtsPerWave;
+  if (a.gate && *a.gate == 0) return;                   // fp32 fall-back pass of an fp16-operand call: nothing overflowed
+
+  WeightStream ws;
+  ws.base = a.w_pre;
+  ws.lds = smem;
+  ws.n_stages = kPreStages;
+  ws.wave = wave;
+  ws.lane = lane;
+  ws.start();
+
+  for (long long tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+    long long p = tile * kPtsPerWave + pt;
+    if (p >= a.P) p = a.P - 1;                          // tail lanes shadow the last point; stores are whole tiles
+                                                        // into a workspace padded to a multiple of 16 points
+    Taps taps;
+    float feat[16];
+    field_frontend(sc, a, v, q, p, taps, feat);
+
+    f32x4 x[kTiles], net[kTiles];
+    // ---- lin_in: x = W_in f + b_in                                             (resnetfc.py:141)
+    set_bias(x, a.b_pre, q);
+    stage_mma<0>(ws, feat, x);
+    stage_mma<1>(ws, feat, x);
+    stage_mma<2>(ws, feat, x);
+    stage_mma<3>(ws, feat, x);
+    // ---- blocks 0..2 (per view)                                                 (:145-157, :61-69)
+    for (int b = 0; b < 3; ++b) {
+      const float* bias = a.b_pre + kHidden * (1 + 2 * b);
+      set_bias(net, bias, q);
+      layer_fc0_hoisted(ws, a.tz + (size_t)b * a.tz_stride, taps, q, x, net);   // x += lin_z[b](latent); net = fc_0(relu(x))
+      add_bias(x, bias + kHidden, q);
+      layer_from_acc(ws, net, x);                                                // x += fc_1(relu(net))
+    }
+    // ---- (1 / NV) x the sum over the group's live views (= waves), written to or added into the hand-over in accumulator layout
+    view_group_store(smem + kRing * kStageFloats, x, vg, reinterpret_cast<f32x4*>(a.xpre) + (size_t)tile * (kTiles * 64), wave, lane);
+  }
+  ws.drain();   // the last (unused) stage DMAs must land before the LDS is released
+}
+
 struct HoistArgs {
   const float* src;    // (rows, 512) channels-last latent pixels (or explicit latent rows)
   float* dst;          // (3, rows, 512): lin_z[b](src) + bias
@@ -638,6 +688,7 @@ static int prepare_device() {
   if (!g_dev.attrs[dev]) {
     DINER_HIP_OK(hipFuncSetAttribute((const void*)k_field_pre, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kFp32LdsBytes));
     DINER_HIP_OK(hipFuncSetAttribute((const void*)k_field_post, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kFp32LdsBytes));
+    DINER_HIP_OK(hipFuncSetAttribute((const void*)k_field_views_f32, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kFp32LdsBytes));
     DINER_HIP_OK(hipFuncSetAttribute((const void*)k_hoist_linz, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kFp32LdsBytes));
     int rc = h3n_set_attributes();
     if (rc) return rc;
@@ -741,6 +792,105 @@ static int launch_field(const SceneDev* sc, const DinerMlpImpl* m, FieldArgs fa,
   }
   hipLaunchKernelGGL(k_field_pre, dim3(grid_pre), dim3(256), kFp32LdsBytes, stream, *sc, fa);
   DINER_LAUNCH_OK();
+  if (timed && !use_hn) DINER_HIP_OK(hipEventRecord(e1, stream));
+  hipLaunchKernelGGL(k_field_post, dim3(grid_post), dim3(256), kFp32LdsBytes, stream, pa);
+  DINER_LAUNCH_OK();
+  if (timed) {
+    if (!use_hn) DINER_HIP_OK(hipEventRecord(e2, stream));
+    std::lock_guard<std::mutex> lock(g_timer.mu);
+    g_timer.ev.push_back(e0);
+    g_timer.ev.push_back(e1);
+    g_timer.ev.push_back(e2);
+    g_timer.points.push_back(fa.P);
+  }
+  return 0;
+}
+
+// The field of a scene with any number of source views, 1 .. DINER_MAX_VIEWS, on the view-group instances of the per-view kernels: one
+// launch per group of up to four views on the stream (the launches are ordered, and each reads, adds to and writes the 2 KB-per-point
+// hand-over by tile index), then the unchanged post kernel.  fa.tz / fa.tz_stride: the scene's projected maps (3, NV, Hf, Wf, 512); a
+// group's maps start 4 g Hf Wf 512 floats further on, the plane stride stays NV Hf Wf 512.  The 32-bit tap offsets of the fp16-operand
+// kernel span ONE group's maps.  The gated exact pass behind an f16x3 call recomputes the launch over all groups.  Tile counters: the
+// workspace's flag block holds 64 ints -- [0] the range flag, [16, 24) the post kernel's queues, [8, 16) and [24, 48) those of groups 0 .. 3.
+static int launch_field_views(const DinerScene* scene, const DinerMlpImpl* m, FieldArgs fa, float* out, void* workspace, int precision,
+                              hipStream_t stream) {
+  const int nv = scene->nv, n_groups = (nv + kMaxViews - 1) / kMaxViews;
+  const int cus = prepare_device();
+  if (cus < 0) return cus;
+  DINER_CHECK_ARG(!m->train_only, "field: this handle was last packed with diner_mlp_update(DINER_MLP_UPDATE_TRAIN_ONLY) -- only the "
+                  "layouts of the fused training forward are current; update it without the flag (or create one) for inference");
+  bool fits = false;
+  {
+    int rcf = mlp_fits(m, &fits);
+    if (rcf) return rcf;
+  }
+  const bool use_hn = precision == DINER_PRECISION_F16X3 && fits;
+  const size_t group_floats = (size_t)(nv < kMaxViews ? nv : kMaxViews) * scene->Hf * scene->Wf * kLatent;
+  if (use_hn && group_floats * sizeof(float) >= ((size_t)1 << 32)) {
+    set_error("field: the projected feature maps of one group of four views are %.1f GiB; the fp16-operand kernels address a group with "
+              "32-bit offsets (< 4 GiB) -- use DINER_PRECISION_FP32 for this scene", (double)(group_floats * sizeof(float)) / (1u << 30));
+    return DINER_E_UNSUPPORTED;
+  }
+  SceneDev sd[kMaxViewsWide / kMaxViews];
+  ViewGroup vg[kMaxViewsWide / kMaxViews];
+  for (int g = 0; g < n_groups; ++g) {
+    int rc = make_group_scene_dev(scene, g, &sd[g], &vg[g].n_live);
+    if (rc) return rc;
+    vg[g].first = g == 0;
+  }
+  fa.w_pre = m->w_pre;
+  fa.b_pre = m->b_pre;
+  fa.xpre = (float*)workspace;
+  fa.freq_factor = m->freq_factor;
+  fa.gate = nullptr;
+  int* flag = reinterpret_cast<int*>((char*)workspace + xpre_bytes(fa.P, nv));
+  const long long n_t16 = (fa.P + kPtsPerWave - 1) / kPtsPerWave;
+  const int grid_pre = (int)(n_t16 < cus ? n_t16 : cus);
+  const long long n_tiles = (n_t16 + 3) / 4;
+  const int grid_post = (int)(n_tiles < cus ? n_tiles : cus);
+  const float* tz = fa.tz;
+  const size_t tz_group = (size_t)kMaxViews * scene->Hf * scene->Wf * kLatent;
+  hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr;
+  bool timed;
+  {
+    std::lock_guard<std::mutex> lock(g_timer.mu);
+    timed = g_timer.enabled;
+  }
+  if (timed) {
+    DINER_HIP_OK(hipEventCreate(&e0));
+    DINER_HIP_OK(hipEventCreate(&e1));
+    DINER_HIP_OK(hipEventCreate(&e2));
+  }
+  PostArgs pa{(const float*)workspace, m->w_post, m->b_post, out, fa.P, nv, 0, nullptr, nullptr, m->fallback_dev};
+  if (use_hn) {
+    static_assert(kFlagBytes >= 48 * sizeof(int), "range flag + the tile counters of four groups and the post kernel");
+    DINER_HIP_OK(hipMemsetAsync(flag, 0, 48 * sizeof(int), stream));
+    if (timed) DINER_HIP_OK(hipEventRecord(e0, stream));
+    for (int g = 0; g < n_groups; ++g) {
+      fa.tz = tz + (size_t)g * tz_group;
+      vg[g].scale = (1.0f / 16.0f) / (float)nv;
+      h3n_launch_pre(sd[g], fa, m->hn_w, m->hn_b_pre, grid_pre, true, reinterpret_cast<unsigned*>(flag) + (g == 0 ? 8 : 16 + 8 * g), stream,
+                     nullptr, &vg[g]);
+      DINER_LAUNCH_OK();
+    }
+    if (timed) DINER_HIP_OK(hipEventRecord(e1, stream));
+    PostArgs pn = pa;
+    pn.b_post = m->hn_b_post;
+    pn.overflow = flag;
+    h3n_launch_post(pn, m->hn_w, m->hn_w_out, grid_post, true, reinterpret_cast<unsigned*>(flag) + 16, stream);
+    DINER_LAUNCH_OK();
+    if (timed) DINER_HIP_OK(hipEventRecord(e2, stream));
+    fa.gate = flag;                 // the exact kernels below only run when the flag was raised
+    pa.gate = flag;
+  } else if (timed) {
+    DINER_HIP_OK(hipEventRecord(e0, stream));
+  }
+  for (int g = 0; g < n_groups; ++g) {
+    fa.tz = tz + (size_t)g * tz_group;
+    vg[g].scale = 1.0f / (float)nv;
+    hipLaunchKernelGGL(k_field_views_f32, dim3(grid_pre), dim3(256), kFp32LdsBytes, stream, sd[g], fa, vg[g]);
+    DINER_LAUNCH_OK();
+  }
   if (timed && !use_hn) DINER_HIP_OK(hipEventRecord(e1, stream));
   hipLaunchKernelGGL(k_field_post, dim3(grid_post), dim3(256), kFp32LdsBytes, stream, pa);
   DINER_LAUNCH_OK();
@@ -1151,6 +1301,103 @@ extern "C" int diner_render_f32(const DinerScene* scene, const DinerMlp* mlp, co
                                 float* field_ws, void* workspace, void* stream) {
   DINER_CHECK_ARG(field_ws, "render: field scratch missing");
   int rc = diner_field_from_rays_f32(scene, mlp, rays, z, NR, K, precision, field_ws, workspace, stream);
+  if (rc) return rc;
+  return diner_composite_f32(field_ws, z, rays, NR, K, white_bkgd, rgb_out, depth_out, weights_out, stream);
+}
+
+// ---- scenes with any number of source views, 1 .. DINER_MAX_VIEWS, on the fused kernels (view groups) -----------------------------------
+static int check_views_nv(const DinerScene* scene, const char* who) {
+  DINER_CHECK_ARG(scene, "%s: scene is null", who);
+  DINER_CHECK_ARG(scene->nv >= 1 && scene->nv <= kMaxViewsWide, "%s: nv=%d outside [1,%d]", who, scene->nv, kMaxViewsWide);
+  return 0;
+}
+
+static int check_field_scene_views(const DinerScene* scene, const DinerMlp* mlp, int precision) {
+  DINER_CHECK_ARG(scene->poses_host && scene->focal_host && scene->c_host, "scene: poses_host/focal_host/c_host (host arrays) missing");
+  DINER_CHECK_ARG(scene->img_w > 0 && scene->img_h > 0, "scene: image_shape must be positive");
+  DINER_CHECK_ARG(scene->proj_stamp == mlp->impl.stamp,
+                  "field: scene->latent_proj was prepared with another packed-weights handle (proj_stamp %llu, this handle %llu): "
+                  "the projected maps carry that handle's lin_z / fc_1 biases -- call diner_scene_prepare_views_f32 with this handle and "
+                  "store diner_mlp_stamp() in scene->proj_stamp", (unsigned long long)scene->proj_stamp,
+                  (unsigned long long)mlp->impl.stamp);
+  DINER_CHECK_ARG(scene->C == kLatent, "field: latent size %d != %d", scene->C, kLatent);
+  DINER_CHECK_ARG(scene->depth, "field: depth map missing");
+  DINER_CHECK_ARG(scene->latent_proj, "field: scene->latent_proj is null -- call diner_scene_prepare_views_f32 once per "
+                                      "(scene, MLP weights) first");
+  DINER_CHECK_ARG(scene->Hf > 0 && scene->Wf > 0 && scene->Hs > 0 && scene->Ws > 0, "field: bad map sizes");
+  DINER_CHECK_ARG(precision == DINER_PRECISION_FP32 || precision == DINER_PRECISION_F16X3 || precision == DINER_PRECISION_F16,
+                  "field: precision must be DINER_PRECISION_FP32 (0), _F16X3 (1) or _F16 (3), got %d (2 is retired)", precision);
+  if (precision == DINER_PRECISION_F16) {
+    set_error("field: DINER_PRECISION_F16 (plain fp16 operands) is built for four source views, this scene has %d -- use "
+              "DINER_PRECISION_F16X3 (f16x3) or DINER_PRECISION_FP32 (fp32), which take 1 to %d views", scene->nv, kMaxViewsWide);
+    return DINER_E_UNSUPPORTED;
+  }
+  return 0;
+}
+
+extern "C" size_t diner_scene_proj_views_bytes(const DinerScene* scene) {
+  if (!scene || scene->nv < 1 || scene->nv > kMaxViewsWide || scene->Hf <= 0 || scene->Wf <= 0) return 0;
+  return (size_t)3 * scene->nv * scene->Hf * scene->Wf * kLatent * sizeof(float);
+}
+
+extern "C" int diner_scene_prepare_views_f32(const DinerScene* scene, const DinerMlp* mlp, float* latent_proj_out, void* stream) {
+  int rc = check_views_nv(scene, "scene_prepare_views");
+  if (rc) return rc;
+  DINER_CHECK_ARG(mlp && latent_proj_out, "scene_prepare_views: null pointer argument");
+  DINER_CHECK_ARG(scene->latent_cl && scene->C == kLatent && scene->Hf > 0 && scene->Wf > 0,
+                  "scene_prepare_views: channels-last latent (NV,Hf,Wf,%d) missing", kLatent);
+  return launch_hoist(&mlp->impl, scene->latent_cl, (long long)scene->nv * scene->Hf * scene->Wf, latent_proj_out, (hipStream_t)stream);
+}
+
+extern "C" size_t diner_field_views_workspace_bytes(long long n_points) { return diner_field_workspace_bytes(n_points); }
+
+extern "C" int diner_field_from_rays_views_f32(const DinerScene* scene, const DinerMlp* mlp, const float* rays, const float* z, int NR,
+                                               int K, int precision, float* field_out, void* workspace, void* stream) {
+  int rc = check_views_nv(scene, "field_from_rays_views");
+  if (rc) return rc;
+  if (scene->nv == kMaxViews) return diner_field_from_rays_f32(scene, mlp, rays, z, NR, K, precision, field_out, workspace, stream);
+  DINER_CHECK_ARG(mlp && rays && z && field_out && workspace, "field_from_rays_views: null pointer argument");
+  DINER_CHECK_ARG(NR > 0 && K > 0, "field_from_rays_views: bad sizes NR=%d K=%d", NR, K);
+  rc = check_field_scene_views(scene, mlp, precision);
+  if (rc) return rc;
+  FieldArgs fa;
+  memset(&fa, 0, sizeof(fa));
+  fa.rays = rays;
+  fa.z = z;
+  fa.K = K;
+  fa.P = (long long)NR * K;
+  fa.tz = scene->latent_proj;
+  fa.tz_stride = (size_t)scene->nv * scene->Hf * scene->Wf * kLatent;
+  return launch_field_views(scene, &mlp->impl, fa, field_out, workspace, precision, (hipStream_t)stream);
+}
+
+extern "C" int diner_field_from_points_views_f32(const DinerScene* scene, const DinerMlp* mlp, const float* xyz, const float* viewdirs,
+                                                 long long P, int precision, float* field_out, void* workspace, void* stream) {
+  int rc = check_views_nv(scene, "field_from_points_views");
+  if (rc) return rc;
+  if (scene->nv == kMaxViews) return diner_field_from_points_f32(scene, mlp, xyz, viewdirs, P, precision, field_out, workspace, stream);
+  DINER_CHECK_ARG(mlp && xyz && viewdirs && field_out && workspace, "field_from_points_views: null pointer argument");
+  DINER_CHECK_ARG(P > 0, "field_from_points_views: P must be positive");
+  rc = check_field_scene_views(scene, mlp, precision);
+  if (rc) return rc;
+  FieldArgs fa;
+  memset(&fa, 0, sizeof(fa));
+  fa.xyz = xyz;
+  fa.viewdirs = viewdirs;
+  fa.K = 1;
+  fa.P = P;
+  fa.tz = scene->latent_proj;
+  fa.tz_stride = (size_t)scene->nv * scene->Hf * scene->Wf * kLatent;
+  return launch_field_views(scene, &mlp->impl, fa, field_out, workspace, precision, (hipStream_t)stream);
+}
+
+extern "C" int diner_render_views_f32(const DinerScene* scene, const DinerMlp* mlp, const float* rays, const float* z, int NR, int K,
+                                      int white_bkgd, int precision, float* rgb_out, float* depth_out, float* weights_out,
+                                      float* field_ws, void* workspace, void* stream) {
+  int rc = check_views_nv(scene, "render_views");
+  if (rc) return rc;
+  DINER_CHECK_ARG(field_ws, "render_views: field scratch missing");
+  rc = diner_field_from_rays_views_f32(scene, mlp, rays, z, NR, K, precision, field_ws, workspace, stream);
   if (rc) return rc;
   return diner_composite_f32(field_ws, z, rays, NR, K, white_bkgd, rgb_out, depth_out, weights_out, stream);
 }

@@ -840,8 +840,12 @@ __device__ __forceinline__ void save_block(float* __restrict__ dst, unsigned* __
   }
 }
 
-template <bool SAVE>
-__device__ __forceinline__ void field_pre_body(const SceneDev& sc, const Args& a, const SaveActs& sv) {
+// GROUP: the view-group instance (k_field_views_h3n, see ViewGroup in field_common.hpp) -- column group w is view w of ONE group of up to
+// four views; a dead column (w >= n_live) recomputes the group's first view and is left out of the sum, which is written to (first group) or
+// added into (later groups) the hand-over
+template <bool SAVE, bool GROUP = false>
+__device__ __forceinline__ void field_pre_body(const SceneDev& sc, const Args& a, const SaveActs& sv, const ViewGroup& vg = ViewGroup{}) {
+  static_assert(!(SAVE && GROUP), "the training forward runs four views");
   constexpr int kRing = DINER_HN_RING, kRing0 = DINER_HN_RING0, kGDepth = DINER_HN_GDEPTH;
   extern __shared__ __attribute__((aligned(16))) float smem[];
   h8* B = reinterpret_cast<h8*>(smem);
@@ -878,7 +882,7 @@ __device__ __forceinline__ void field_pre_body(const SceneDev& sc, const Args& a
     // do not survive the GEMMs in registers and come back from scratch in every tile (seven reloads in front of the projection).
     MapDims dims{sc.Wf, sc.Hf, sc.Ws, sc.Hs};
     asm volatile("" : "+s"(dims.Wf), "+s"(dims.Hf), "+s"(dims.Ws), "+s"(dims.Hs));
-    frontend_h3n(sc, dims, fa, /*view=*/wave, q, lane, p, feat_tab, feat_src, taps, feat);
+    frontend_h3n(sc, dims, fa, /*view=*/GROUP ? (wave < vg.n_live ? wave : 0) : wave, q, lane, p, feat_tab, feat_src, taps, feat);
     pf.mark(0);
     __syncthreads();                              // previous tile's readers of B / taps are done
     pf.mark(1);
@@ -968,9 +972,27 @@ __device__ __forceinline__ void field_pre_body(const SceneDev& sc, const Args& a
     }
     // view mean = mean over the four column groups; hand-over at scale 1 in accumulator layout (row tile 8 w + mo)
     f32x4* out = reinterpret_cast<f32x4*>(fa.xpre) + (size_t)tile * (kTiles * 64) + lane;
+    if constexpr (GROUP) {
+      // the sum over the LIVE views in the four-view order ((v0 + v1) + v2) + v3, by wave-uniform selection (never a multiplication with
+      // zero: an inf / NaN of a dead column must not reach the result, one of a live column must); scale = 1 / (16 NV)
+      int n_live = vg.n_live, first = vg.first;
+      float scale = vg.scale;
+      asm volatile("" : "+s"(n_live), "+s"(first), "+s"(scale));      // per-tile scalars, as the map sizes above
 #pragma unroll
-    for (int mo = 0; mo < kSlice; ++mo)
-      out[(8 * wave + mo) * 64] = (((xs[mo][0] + xs[mo][1]) + xs[mo][2]) + xs[mo][3]) * (0.25f * kInvScale);
+      for (int mo = 0; mo < kSlice; ++mo) {
+        f32x4 s = xs[mo][0];
+        if (n_live > 1) s += xs[mo][1];
+        if (n_live > 2) s += xs[mo][2];
+        if (n_live > 3) s += xs[mo][3];
+        s *= scale;
+        if (!first) s += out[(8 * wave + mo) * 64];
+        out[(8 * wave + mo) * 64] = s;
+      }
+    } else {
+#pragma unroll
+      for (int mo = 0; mo < kSlice; ++mo)
+        out[(8 * wave + mo) * 64] = (((xs[mo][0] + xs[mo][1]) + xs[mo][2]) + xs[mo][3]) * (0.25f * kInvScale);
+    }
     pf.mark(14);
   }
   pf.end(a.prof, lane);
@@ -983,6 +1005,8 @@ __global__ __launch_bounds__(256, 1) void k_field_pre_h3n(SceneDev sc, Args a) {
   static_assert(LO, "f16x3 only");
   field_pre_body<false>(sc, a, SaveActs{});
 }
+// the view-group instance: one group of up to four views of a scene with 1..3 or 5..16 of them (mlp.hip, launch_field_views)
+__global__ __launch_bounds__(256, 1) void k_field_views_h3n(SceneDev sc, Args a, ViewGroup vg) { field_pre_body<false, true>(sc, a, SaveActs{}, vg); }
 // the same kernel storing the pre-activations of blocks 0-2 (training forward, DINER_TRAIN_FUSED_FWD)
 __global__ __launch_bounds__(256, 1) void k_train_fwd_pre(SceneDev sc, Args a, SaveActs sv) { field_pre_body<true>(sc, a, sv); }
 
@@ -2038,6 +2062,7 @@ int h3n_set_attributes() {
   DINER_HIP_OK(hipFuncSetAttribute((const void*)h3n::w8::k_field_post_h8, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h3n::w8::kLdsBytesPost8));
   DINER_HIP_OK(hipFuncSetAttribute((const void*)h3n::w8::k_field_pre_h8, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h3n::w8::kLdsBytes8));
   DINER_HIP_OK(hipFuncSetAttribute((const void*)h3n::k_train_fwd_pre, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h3n::kLdsBytes));
+  DINER_HIP_OK(hipFuncSetAttribute((const void*)h3n::k_field_views_h3n, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h3n::kLdsBytes));
   DINER_HIP_OK(hipFuncSetAttribute((const void*)h3n::k_train_fwd_post, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h3n::kLdsBytesPost));
   DINER_HIP_OK(hipFuncSetAttribute((const void*)h3n::k_field_pre_h3n<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                    (int)h3n::kLdsBytes));
@@ -2045,9 +2070,10 @@ int h3n_set_attributes() {
                                    (int)h3n::kLdsBytes));
   return 0;
 }
-// split = true: f16x3 split products (hi and lo parts, three MFMAs per product) on four waves; false: plain fp16 operands on eight
+// split = true: f16x3 split products (hi and lo parts, three MFMAs per product) on four waves; false: plain fp16 operands on eight;
+// vg (f16x3 only): the view-group instance for one group of the scene's views
 void h3n_launch_pre(const SceneDev& sc, const FieldArgs& fa, const _Float16* w, const float* b, int grid, bool split,
-                    unsigned* tile_counter, hipStream_t stream, const SaveActs* sv) {
+                    unsigned* tile_counter, hipStream_t stream, const SaveActs* sv, const ViewGroup* vg) {
   h3n::Args a{fa, w + WeightLayout::oLinIn4, w + WeightLayout::oLinIn8, b, nullptr, tile_counter,
               h3n::QueueMap::make((fa.P + kPtsPerWave - 1) / kPtsPerWave, fa.K, fa.rays != nullptr && fa.xyz == nullptr && fa.direct_feat == nullptr)};
 #ifdef DINER_HN_PROF
@@ -2056,7 +2082,9 @@ void h3n_launch_pre(const SceneDev& sc, const FieldArgs& fa, const _Float16* w, 
   hipMemsetAsync(prof, 0, 32 * sizeof(unsigned long long), stream);
   a.prof = prof;
 #endif
-  if (sv) {          // training forward: the f16x3 kernel storing the pre-activations
+  if (vg) {          // one group of views (f16x3)
+    hipLaunchKernelGGL(h3n::k_field_views_h3n, dim3(grid), dim3(256), h3n::kLdsBytes, stream, sc, a, *vg);
+  } else if (sv) {   // training forward: the f16x3 kernel storing the pre-activations
     hipLaunchKernelGGL(h3n::k_train_fwd_pre, dim3(grid), dim3(256), h3n::kLdsBytes, stream, sc, a, *sv);
   } else if (split) hipLaunchKernelGGL(h3n::k_field_pre_h3n<true>, dim3(grid), dim3(256), h3n::kLdsBytes, stream, sc, a);
   else hipLaunchKernelGGL(h3n::w8::k_field_pre_h8, dim3(grid), dim3(512), h3n::w8::kLdsBytes8, stream, sc, a);

@@ -80,7 +80,7 @@ class HipScene:
         nv = int(poses.shape[0])
         if not 1 <= nv <= _lib.MAX_VIEWS:          # before any device work: the library takes 1 .. DINER_MAX_VIEWS source views
             raise ValueError(f"diner_amd: a scene has 1 to {_lib.MAX_VIEWS} source views (got {nv}); four run on the fused kernels, "
-                             f"any other number on the generic exact-fp32 path")
+                             f"any other number on the same kernels in groups of four (or on the generic exact-fp32 path)")
         dev = None
         for t in (latent, depths, depths_std, normals):
             if t is not None:
@@ -134,7 +134,8 @@ class HipScene:
 
     def prepare(self, mlp, force=False, f16=False):
         """Hoist lin_z[0..2] out of the sample loop: project the channels-last latent once (k_hoist_linz).
-        Re-run when the MLP handle changes (the handle itself is rebuilt whenever a parameter changes).
+        Re-run when the MLP handle changes (the handle itself is rebuilt whenever a parameter changes).  Any view count: a scene with
+        other than four views goes through the *_views entries (the maps of all NV views, gathered from group by group).
         f16: also (re)build the fp16 copy of the projected maps that PRECISION_F16 gathers from (+50 % memory, made only when that mode
         is used; one conversion pass per preparation)."""
         if self.latent_cl is None:
@@ -142,10 +143,12 @@ class HipScene:
         fresh = force or self._prepared_for is not mlp or self.latent_proj is None
         if fresh:
             with torch.cuda.device(self.device):
+                four = self.nv == 4
                 if self.latent_proj is None:
-                    nbytes = lib.diner_scene_proj_bytes(self.ref)
+                    nbytes = (lib.diner_scene_proj_bytes if four else lib.diner_scene_proj_views_bytes)(self.ref)
                     self.latent_proj = torch.empty(nbytes // 4, dtype=torch.float32, device=self.device)
-                _lib.check(lib.diner_scene_prepare_f32(self.ref, mlp.handle, _ptr(self.latent_proj), _stream()))
+                _lib.check((lib.diner_scene_prepare_f32 if four else lib.diner_scene_prepare_views_f32)(
+                    self.ref, mlp.handle, _ptr(self.latent_proj), _stream()))
             self.struct.latent_proj = self.latent_proj.data_ptr()
             self.struct.proj_stamp = lib.diner_mlp_stamp(mlp.handle)      # the library refuses these maps with any other handle
             self._prepared_for = mlp
@@ -264,6 +267,13 @@ def fused_shape(d_in, d_latent, d_hidden, d_out, n_blocks, combine_layer, nv=4, 
     configs/train_dtu.yaml:39-50); anything else takes the generic slow path (GenericMlp)."""
     return (d_in, d_latent, d_hidden, d_out, n_blocks, combine_layer, nv, int(num_freqs), bool(include_input)) == \
         (55, 512, 512, 4, 5, 3, 4, 6, True) and not beta > 0
+
+
+def fused_shape_any_views(d_in, d_latent, d_hidden, d_out, n_blocks, combine_layer, nv=4, num_freqs=6, include_input=True, beta=0.0):
+    """fused_shape without the view count: the shipped configuration with 1 <= nv <= 16 source views, which the field entries render on
+    the fused kernels -- four views directly, any other number in groups of four (the *_views entries of the C ABI)."""
+    return fused_shape(d_in, d_latent, d_hidden, d_out, n_blocks, combine_layer, 4, num_freqs, include_input, beta) and \
+        1 <= int(nv) <= _lib.MAX_VIEWS
 
 
 class GenericMlp:
@@ -449,17 +459,19 @@ def field_from_rays(scene: HipScene, mlp: HipMlp, rays, z, precision=None):
     rays, z = _f32c(rays), _f32c(z)
     NR, K = z.shape
     prec = _precision_for(scene, precision)
-    scene.prepare(mlp, f16=prec == PRECISION_F16)
+    four = scene.nv == 4              # any other view count: the same kernels over groups of four views
+    scene.prepare(mlp, f16=four and prec == PRECISION_F16)
     out = torch.empty(NR, K, 4, device=rays.device, dtype=torch.float32)
     if NR == 0:
         return out
     rays_per = max(1, MAX_POINTS_PER_LAUNCH // K)
+    entry = lib.diner_field_from_rays_f32 if four else lib.diner_field_from_rays_views_f32
     with torch.cuda.device(rays.device):
-        ws = _workspace(lib.diner_field_workspace_bytes(min(NR, rays_per) * K), rays.device)
+        ws = _workspace((lib.diner_field_workspace_bytes if four else lib.diner_field_views_workspace_bytes)(min(NR, rays_per) * K), rays.device)
         for r0 in range(0, NR, rays_per):
             r1 = min(NR, r0 + rays_per)
-            _lib.check(lib.diner_field_from_rays_f32(scene.ref, mlp.handle, _ptr(rays[r0:r1]), _ptr(z[r0:r1]),
-                                                     r1 - r0, K, prec, _ptr(out[r0:r1]), _ptr(ws), _stream()))
+            _lib.check(entry(scene.ref, mlp.handle, _ptr(rays[r0:r1]), _ptr(z[r0:r1]),
+                             r1 - r0, K, prec, _ptr(out[r0:r1]), _ptr(ws), _stream()))
     return out
 
 
@@ -469,17 +481,19 @@ def field_from_points(scene: HipScene, mlp: HipMlp, xyz, viewdirs, precision=Non
     xyz, viewdirs = _f32c(xyz), _f32c(viewdirs)
     P = xyz.shape[0]
     prec = _precision_for(scene, precision)
-    scene.prepare(mlp, f16=prec == PRECISION_F16)
+    four = scene.nv == 4
+    scene.prepare(mlp, f16=four and prec == PRECISION_F16)
     out = torch.empty(P, 4, device=xyz.device, dtype=torch.float32)
     if P == 0:
         return out
     step = MAX_POINTS_PER_LAUNCH
+    entry = lib.diner_field_from_points_f32 if four else lib.diner_field_from_points_views_f32
     with torch.cuda.device(xyz.device):
-        ws = _workspace(lib.diner_field_workspace_bytes(min(P, step)), xyz.device)
+        ws = _workspace((lib.diner_field_workspace_bytes if four else lib.diner_field_views_workspace_bytes)(min(P, step)), xyz.device)
         for p0 in range(0, P, step):
             p1 = min(P, p0 + step)
-            _lib.check(lib.diner_field_from_points_f32(scene.ref, mlp.handle, _ptr(xyz[p0:p1]), _ptr(viewdirs[p0:p1]),
-                                                       p1 - p0, prec, _ptr(out[p0:p1]), _ptr(ws), _stream()))
+            _lib.check(entry(scene.ref, mlp.handle, _ptr(xyz[p0:p1]), _ptr(viewdirs[p0:p1]),
+                             p1 - p0, prec, _ptr(out[p0:p1]), _ptr(ws), _stream()))
     return out
 
 
@@ -516,7 +530,8 @@ def composite(field, z, rays, white_bkgd, want_weights=True):
 
 
 def render(scene: HipScene, mlp: HipMlp, rays, z, white_bkgd, want_weights=False, precision=None):
-    """field + composite (NeRFRendererDGS.composite): -> weights | None, rgb, depth."""
+    """field + composite (NeRFRendererDGS.composite): -> weights | None, rgb, depth.  A HipMlp takes a scene of any view count (four on
+    the fused kernels directly, any other number in groups of four); a GenericMlp renders on the generic exact-fp32 path."""
     if isinstance(mlp, GenericMlp):        # a configuration outside the fused kernels: exact fp32, one GEMM launch per layer
         NR, K = z.shape
         field = field_generic(scene, mlp, rays=rays, z=z).view(NR, K, 4)
@@ -668,16 +683,18 @@ def get_precision():
 
 def _precision_for(scene, precision):
     """Mode passed to the library for one call.  A scene whose projected maps exceed the 32-bit addressing of the
-    fp16-operand kernels (>= 4 GiB per map: images beyond ~2700 x 2700) is rendered by the exact kernels."""
+    fp16-operand kernels (>= 4 GiB per map of one group of up to four views: images beyond ~2700 x 2700, for any number of views) is
+    rendered by the exact kernels."""
     prec = get_precision() if precision is None else (PRECISION_NAMES[precision.lower()] if isinstance(precision, str)
                                                       else int(precision))
     if prec not in (PRECISION_FP32, PRECISION_F16X3, PRECISION_F16):
         raise ValueError(f"diner_amd: unknown precision {precision!r}")
-    if prec != PRECISION_FP32 and scene.nv * scene.Hf * scene.Wf * 2048 >= (1 << 32):
+    group_bytes = min(scene.nv, 4) * scene.Hf * scene.Wf * 2048
+    if prec != PRECISION_FP32 and group_bytes >= (1 << 32):
         global _warned_big_map
         if not _warned_big_map:       # not silent: the exact kernels are ~3x slower than the f16x3 ones
             import warnings
-            warnings.warn(f"diner_amd: one projected feature map of this scene is {scene.nv * scene.Hf * scene.Wf * 2048 / 2 ** 30:.1f} GiB; the "
+            warnings.warn(f"diner_amd: one projected feature map of this scene is {group_bytes / 2 ** 30:.1f} GiB per group of four views; the "
                           f"fp16-operand kernels address it with 32-bit offsets (< 4 GiB), so this scene is rendered by the exact-fp32 "
                           f"kernels (~3x slower)", RuntimeWarning, stacklevel=3)
             _warned_big_map = True

@@ -29,8 +29,8 @@ extern "C" {
 #define DINER_ABI_VERSION 6   /* the *_long_f32 entry points were added without a bump: new symbols, no v6 contract changed */
 
 /* Source views a scene may have (DinerScene.nv).  The fused field / training kernels are built for exactly 4 (every shipped config);
- * the sampler, diner_index_f32 and the generic path (diner_field_inputs_generic_*) take 1 .. DINER_MAX_VIEWS.  Added without an ABI bump:
- * no struct or signature changed. */
+ * the sampler, diner_index_f32, the generic path (diner_field_inputs_generic_*) and the *_views_f32 field entries (the fused kernels over
+ * groups of four views) take 1 .. DINER_MAX_VIEWS.  Added without an ABI bump: no struct or signature changed. */
 #define DINER_MAX_VIEWS 16
 
 #define DINER_E_INVALID     (-1)  /* bad argument (null pointer, size, unsupported configuration) */
@@ -61,8 +61,8 @@ typedef struct DinerScene {
   float img_w, img_h;       /* PixelNeRF.image_shape = [W, H] (pixelnerf.py:50-51)                         */
   float feature_padding;    /* SpatialEncoder.feature_padding (image_encoder.py:59), 32 in the shipped configs */
   int32_t nv, C, Hf, Wf, Hs, Ws; /* nv: source views, 1 .. DINER_MAX_VIEWS.  Entries built for the fused kernels (field, scene preparation,
-                               shipped-shape training, diner_train_inputs_f32) return DINER_E_UNSUPPORTED for 5 .. 16 views; every entry
-                               returns DINER_E_INVALID outside [1, DINER_MAX_VIEWS] */
+                               shipped-shape training, diner_train_inputs_f32) return DINER_E_UNSUPPORTED for 5 .. 16 views (the
+                               *_views_f32 field entries take them); every entry returns DINER_E_INVALID outside [1, DINER_MAX_VIEWS] */
   uint64_t proj_stamp;      /* diner_mlp_stamp() of the handle that wrote latent_proj (set by the caller after
                                diner_scene_prepare_f32).  The field entry points return DINER_E_INVALID when it is not the
                                stamp of the handle they are called with: maps prepared with another (or an older) handle carry
@@ -208,6 +208,28 @@ int diner_field_from_rays_f32(const DinerScene* scene, const DinerMlp* mlp, cons
 /* Same, explicit points / view directions (P,3): PixelNeRF.forward(xyz, viewdirs) (pixelnerf.py:55). */
 int diner_field_from_points_f32(const DinerScene* scene, const DinerMlp* mlp, const float* xyz, const float* viewdirs,
                                 long long P, int precision, float* field_out, void* workspace, void* stream);
+
+/* ---- the same for scenes with ANY number of source views, 1 .. DINER_MAX_VIEWS (pixelnerf.py:67 takes any) -------------------------
+ * The mean over the views (resnetfc.py:148-151) is linear: an NV-view scene runs as ceil(NV / 4) launches of the four-view per-view
+ * kernel over groups of four cameras, each adding (1 / NV) x the sum over its live views into the same 2 KB-per-point hand-over, and one
+ * unchanged post kernel.  A partial group's spare columns recompute one of its own views and are left out of the sum.  Arguments,
+ * workspace size and results as the four-view namesakes above; NV = 4 IS the four-view entry (same bits).  New symbols, no ABI bump.
+ *   diner_scene_proj_views_bytes    3 NV Hf Wf 512 4 bytes for 1 <= NV <= DINER_MAX_VIEWS, else 0
+ *   diner_scene_prepare_views_f32   diner_scene_prepare_f32 for any such NV (set scene->latent_proj / proj_stamp as there)
+ *   precision                       DINER_PRECISION_F16X3 (gated exact-fp32 repeat over all groups behind it, as above) or _FP32;
+ *                                   DINER_PRECISION_F16 with NV != 4 is DINER_E_UNSUPPORTED (the plain-fp16 kernels are four-view)
+ *   f16x3 limit                     the 32-bit tap offsets span ONE group's maps: min(NV, 4) Hf Wf 2 KB below 4 GiB, else DINER_E_UNSUPPORTED
+ * Validation before any device work: NV outside [1, DINER_MAX_VIEWS] is DINER_E_INVALID; then handle, stamp and configuration. */
+size_t diner_scene_proj_views_bytes(const DinerScene* scene);
+int diner_scene_prepare_views_f32(const DinerScene* scene, const DinerMlp* mlp, float* latent_proj_out, void* stream);
+size_t diner_field_views_workspace_bytes(long long n_points);
+int diner_field_from_rays_views_f32(const DinerScene* scene, const DinerMlp* mlp, const float* rays, const float* z,
+                                    int NR, int K, int precision, float* field_out, void* workspace, void* stream);
+int diner_field_from_points_views_f32(const DinerScene* scene, const DinerMlp* mlp, const float* xyz, const float* viewdirs,
+                                      long long P, int precision, float* field_out, void* workspace, void* stream);
+int diner_render_views_f32(const DinerScene* scene, const DinerMlp* mlp, const float* rays, const float* z, int NR, int K,
+                           int white_bkgd, int precision, float* rgb_out, float* depth_out, float* weights_out,
+                           float* field_ws, void* workspace, void* stream);
 
 /* ---- a7 alone: ResnetFC.forward(zx, combine_dim) on an explicit (NV, B, d_latent+d_in) matrix --
  * workspace: diner_mlp_forward_workspace_bytes(B) bytes. */

@@ -6,6 +6,8 @@ import_obj plugin seam), attributes (`poses`, `focal`, `c`, `image_shape`, `enco
 bilinear feature gather + ResnetFC on fp32 MFMA, diner_amd/csrc/mlp.hip) through diner_field_from_points_f32.
 `encode` is per-image setup and stays in torch ops, as in the reference.  In grad mode `forward` switches to the training
 path of diner_amd/train.py (HIP forward that keeps activations + HIP backward)."""
+import os
+
 import torch
 
 from diner_amd import ops
@@ -77,15 +79,26 @@ class PixelNeRF(torch.nn.Module):
 
     def hip_mlp(self):
         """Packed ResnetFC weights (fused kernels) or the generic-path parameter block; either carries the positional encoding that
-        feeds the MLP (the fused field kernels evaluate it in registers)."""
+        feeds the MLP (the fused field kernels evaluate it in registers).  The packed handle whenever the shape is the shipped one apart
+        from the view count: no-grad forward / NeRFRendererDGS.forward / composite / predict_image then run view-grouped."""
         pc = self.poscode
-        return self.mlp_fine.hip_mlp(num_freqs=pc.num_freqs, freq_factor=pc.freq_factor, include_input=pc.include_input, nv=self._nv())
+        return self.mlp_fine.hip_mlp(num_freqs=pc.num_freqs, freq_factor=pc.freq_factor, include_input=pc.include_input, nv=self._nv(),
+                                     view_grouped=self.is_view_grouped())
 
     def is_generic(self):
-        """A configuration outside the fused field kernels (another d_hidden / n_blocks / combine_layer / positional encoding / number of
-        views / latent width): rendered on the generic slow path, exact fp32."""
+        """A configuration outside the four-view kernels: trains on the generic path."""
         pc = self.poscode
         return not self.mlp_fine.is_fused_shape(self._nv(), pc.num_freqs, pc.include_input)
+
+    def is_view_grouped(self):
+        """The shipped shape with a view count other than four (1..3, 5..16): no-grad calls render on the fused kernels over groups of
+        four views (the *_views entries).  Not with plain-fp16 operands as the default precision (DINER_AMD_PRECISION=f16: those
+        kernels are four-view only, such scenes stay on the generic path), nor with DINER_AMD_VIEW_GROUPS=0 (timing aid: the generic
+        route of the same build, tools/time_many_views.py --generic)."""
+        pc = self.poscode
+        nv = self._nv()
+        return (nv != 4 and self.mlp_fine.is_fused_shape_any_views(nv, pc.num_freqs, pc.include_input)
+                and ops.get_precision() != ops.PRECISION_F16 and os.environ.get("DINER_AMD_VIEW_GROUPS", "1") != "0")
 
     def _nv(self):
         """Source views of the encoded scene (the shipped 4 before any encode)."""

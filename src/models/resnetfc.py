@@ -67,13 +67,21 @@ class ResnetFC(nn.Module):
         return hasattr(self, "lin_in") and ops.fused_shape(self.d_in, self.d_latent, self.d_hidden, self.d_out, self.n_blocks,
                                                            self.combine_layer, nv, num_freqs, include_input, self.beta)
 
-    def hip_mlp(self, num_freqs=6, freq_factor=6.28, include_input=True, nv=4):
+    def is_fused_shape_any_views(self, nv=4, num_freqs=6, include_input=True):
+        """The shipped configuration apart from the view count (1 <= nv <= 16): what the field entries render on the fused kernels, four
+        views at a time (ops.fused_shape_any_views)."""
+        return hasattr(self, "lin_in") and ops.fused_shape_any_views(self.d_in, self.d_latent, self.d_hidden, self.d_out, self.n_blocks,
+                                                                     self.combine_layer, nv, num_freqs, include_input, self.beta)
+
+    def hip_mlp(self, num_freqs=6, freq_factor=6.28, include_input=True, nv=4, view_grouped=False):
         """HipMlp handle (fused kernels) or GenericMlp (any other configuration) for the current parameter values, re-made when any
         parameter changed.  The keyword arguments describe the positional encoding of the inputs (PixelNeRF passes its own;
-        irrelevant for forward() on an explicit matrix) and the number of source views."""
+        irrelevant for forward() on an explicit matrix) and the number of source views.  view_grouped (PixelNeRF's field calls): the
+        packed handle also for the shipped shape with another view count, which ops.field_from_rays / field_from_points / render run
+        in groups of four views; without it nv != 4 is the generic path (forward() on an explicit matrix)."""
         self._check_supported()
         sd = {k: v for k, v in self.state_dict().items()}
-        fused = self.is_fused_shape(nv, num_freqs, include_input)
+        fused = self.is_fused_shape(nv, num_freqs, include_input) or (view_grouped and self.is_fused_shape_any_views(nv, num_freqs, include_input))
         key = (tuple((k, v.data_ptr(), v._version, str(v.device)) for k, v in sorted(sd.items())),
                int(num_freqs), float(freq_factor), bool(include_input), fused)
         if self._hip is None or key != self._hip_key:

@@ -12,6 +12,7 @@
 #   bench [bench args]         bench.py (default --gpus 1 --steps 20 --warmup 5 --full) -> bench_line.json in the output folder + a digest on stdout
 #   profile <tag> [bench args] rocprofv3 stats + PMC passes of the bench (tools/profile_round.sh)
 #   objective-time [args]      tools/time_objective.py: calc_losses against the torch expression of the objective, alternating (stdout; keep it as profiles/objective_step_ab.txt)
+#   many-views-time [args]     tools/time_many_views.py --both: NV = 1, 2, 3, 4, 6, 8, 16 on the view-grouped and the forced-generic route, alternating (stdout; keep it under profiles/)
 #   smoke                      __graft_entry__.smoke()
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}" || exit 1
 mkdir -p gpurun_out
@@ -62,6 +63,8 @@ PY
   profile) bash tools/profile_round.sh "$@" ;;
   objective-time)
     timeout 900 python tools/time_objective.py "$@" 2>&1 | grep -v amdgpu.ids ;;
+  many-views-time)
+    timeout 1100 python tools/time_many_views.py --both --nvs 1,2,3,4,6,8,16 "$@" 2>&1 | grep -v amdgpu.ids ;;
   smoke) python __graft_entry__.py smoke ;;
   *) echo "unknown job '$job' (see the header of tools/job.sh)"; exit 2 ;;
 esac

@@ -1,10 +1,13 @@
-"""Frame time of renders with 4 to 16 source views through the drop-in modules (the reference's PixelNeRF takes any number of
-views, pixelnerf.py:67; here four run on the fused kernels and any other number on the generic exact-fp32 path).
+"""Frame time of renders with 1 to 16 source views through the drop-in modules (the reference's PixelNeRF takes any number of
+views, pixelnerf.py:67; here four run on the fused kernels, any other number on the same kernels over groups of four views, and
+-- with --generic -- on the generic exact-fp32 path, so that both routes can be timed from one build).
 
-    python tools/time_many_views.py [--frames 3] [--warmup 1] [--size 256] [--ray-batch 16384] [--no-prof]
+    python tools/time_many_views.py [--frames 3] [--warmup 1] [--size 256] [--ray-batch 16384] [--no-prof] [--generic] [--nvs 4,6,8,16]
+    python tools/time_many_views.py --both        # every view count on both routes, alternating, ratios to the four-view frame
 
 One size x size frame of the seeded synthetic scene (make_scene(nv=NV), seed 0) at K = 128, n_candidates = 1000, n_gaussian = 48 through
-PixelNeRF / NeRFRendererDGS and diner_amd.render.predict_image, with NV = 4, 6, 8 and 16, each in a child process of its own.  Unless
+PixelNeRF / NeRFRendererDGS and diner_amd.render.predict_image, with NV = 4, 6, 8 and 16 (--nvs), each in a child process of its own;
+`path` of a run is fused4 (four views), grouped (view groups) or generic.  Unless
 --no-prof, every child runs under `rocprofv3 --kernel-trace --stats` and its kernel time is split into the sampler, the generic inputs,
 the GEMMs of the generic MLP, the fused field kernels and the rest.  Timed with device events around each frame; median of --frames frames
 after --warmup.  Prints one JSON line."""
@@ -23,7 +26,7 @@ sys.path.insert(0, ROOT)
 NVS = (4, 6, 8, 16)
 K, N_CAND, G = 128, 1000, 48
 GROUPS = (("sampler", ("k_sample_depthguided",)), ("inputs", ("k_generic_inputs",)), ("gemm", ("k_gemm",)),
-          ("fused", ("k_field_pre", "k_field_post")))
+          ("fused", ("k_field_pre", "k_field_post", "k_field_views")))
 
 
 def child(args):
@@ -51,7 +54,9 @@ def child(args):
                 times.append(ev0.elapsed_time(ev1))
             assert torch.isfinite(rgb).all() and torch.isfinite(depth).all()
     ms = sorted(times)[len(times) // 2]
-    print(json.dumps(dict(nv=args.nv, path="generic" if nerf.is_generic() else "fused", ms=round(ms, 2), frames=sorted(times),
+    path = "fused4" if not nerf.is_generic() else ("grouped" if nerf.is_view_grouped() else "generic")
+    assert (path == "generic") == isinstance(nerf.hip_mlp(), ops.GenericMlp)
+    print(json.dumps(dict(nv=args.nv, path=path, ms=round(ms, 2), frames=sorted(times),
                           rays_per_s=round(W * H / (ms * 1e-3)))), flush=True)
 
 
@@ -79,11 +84,20 @@ def main():
     ap.add_argument("--ray-batch", type=int, default=16384)
     ap.add_argument("--no-prof", action="store_true")
     ap.add_argument("--timeout", type=int, default=600, help="seconds per child")
+    ap.add_argument("--generic", action="store_true", help="force the generic exact-fp32 route for view counts other than four")
+    ap.add_argument("--both", action="store_true", help="each view count on the view-grouped and on the forced-generic route, alternating")
+    ap.add_argument("--nvs", default=",".join(str(n) for n in NVS), help="view counts, comma-separated")
     args = ap.parse_args()
+    if args.generic:
+        os.environ["DINER_AMD_VIEW_GROUPS"] = "0"          # PixelNeRF.is_view_grouped() (inherited by the children)
     if args.nv:
         return child(args)
-    res = dict(tool="time_many_views", size=args.size, K=K, n_cand=N_CAND, G=G, frames=args.frames, ray_batch=args.ray_batch, runs={})
-    for nv in NVS:
+    nvs = tuple(int(n) for n in args.nvs.split(","))
+    if args.both:
+        return both(args, nvs)
+    res = dict(tool="time_many_views", size=args.size, K=K, n_cand=N_CAND, G=G, frames=args.frames, ray_batch=args.ray_batch,
+               forced_generic=bool(args.generic), runs={})
+    for nv in nvs:
         cmd = [sys.executable, os.path.abspath(__file__), "--nv", str(nv), "--frames", str(args.frames), "--warmup", str(args.warmup),
                "--size", str(args.size), "--ray-batch", str(args.ray_batch)]
         with tempfile.TemporaryDirectory() as tmp:
@@ -104,8 +118,39 @@ def main():
                                      f"{sorted(glob.glob(os.path.join(tmp, '**'), recursive=True))[:20]}\n{p.stderr[-1500:]}\n")
         res["runs"][f"nv{nv}"] = run
         print(f"NV={nv}: {run}", file=sys.stderr, flush=True)
-    base = res["runs"]["nv4"]["ms"]
-    res["ratio_vs_nv4"] = {k: round(v["ms"] / base, 2) for k, v in res["runs"].items()}
+    if "nv4" in res["runs"]:
+        base = res["runs"]["nv4"]["ms"]
+        res["ratio_vs_nv4"] = {k: round(v["ms"] / base, 2) for k, v in res["runs"].items()}
+    print(json.dumps(res), flush=True)
+
+
+def both(args, nvs):
+    """Every view count on the view-grouped route and on the forced-generic route, one child each, alternating (no profiler): frame
+    times, the ratio of the two and the ratio of either to the four-view fused frame of the same run."""
+    res = dict(tool="time_many_views", mode="both", size=args.size, K=K, n_cand=N_CAND, G=G, frames=args.frames, ray_batch=args.ray_batch, runs={})
+    for nv in nvs:
+        for route in ("grouped", "generic"):
+            if nv == 4 and route == "generic":
+                continue
+            env = dict(os.environ, DINER_AMD_VIEW_GROUPS="0" if route == "generic" else "1")
+            cmd = [sys.executable, os.path.abspath(__file__), "--nv", str(nv), "--frames", str(args.frames), "--warmup", str(args.warmup),
+                   "--size", str(args.size), "--ray-batch", str(args.ray_batch)]
+            p = subprocess.run(cmd, capture_output=True, text=True, timeout=args.timeout, env=env)
+            if p.returncode != 0:
+                sys.stderr.write(p.stdout[-2000:] + p.stderr[-4000:])
+                raise SystemExit(f"NV={nv} {route}: child exited with {p.returncode}")
+            run = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
+            assert run["path"] == ("fused4" if nv == 4 else route), run
+            res["runs"][f"nv{nv}_{run['path']}"] = run
+            print(f"NV={nv} {route}: {run}", file=sys.stderr, flush=True)
+    base = res["runs"].get("nv4_fused4", {}).get("ms")
+    res["table"] = {}
+    for nv in nvs:
+        a, b = res["runs"].get(f"nv{nv}_grouped"), res["runs"].get(f"nv{nv}_generic")
+        if a and b:
+            res["table"][f"nv{nv}"] = dict(grouped_ms=a["ms"], generic_ms=b["ms"], generic_over_grouped=round(b["ms"] / a["ms"], 2),
+                                           grouped_over_nv4=round(a["ms"] / base, 2) if base else None,
+                                           generic_over_nv4=round(b["ms"] / base, 2) if base else None)
     print(json.dumps(res), flush=True)
 
 
