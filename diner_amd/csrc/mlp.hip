@@ -1305,6 +1305,25 @@ extern "C" int diner_render_f32(const DinerScene* scene, const DinerMlp* mlp, co
   return diner_composite_f32(field_ws, z, rays, NR, K, white_bkgd, rgb_out, depth_out, weights_out, stream);
 }
 
+// diner_render_f32 with the opacity / depth-spread outputs of diner_composite_aux_f32 (nerf_renderer.py:359); the compositor's argument
+// checks run here first, so that a refusal costs no field launch
+static int check_render_aux(const float* rgb_out, const float* depth_out, int NR, int K, const char* who) {
+  DINER_CHECK_ARG(rgb_out && depth_out, "%s: null output pointer", who);
+  DINER_CHECK_ARG(NR > 0 && K > 0 && K <= 1024, "%s: bad sizes NR=%d K=%d (K <= 1024)", who, NR, K);
+  return 0;
+}
+
+extern "C" int diner_render_aux_f32(const DinerScene* scene, const DinerMlp* mlp, const float* rays, const float* z, int NR,
+                                    int K, int white_bkgd, int precision, float* rgb_out, float* depth_out, float* weights_out,
+                                    float* field_ws, void* workspace, float* alpha_out, float* depth_var_out, void* stream) {
+  int rc = check_render_aux(rgb_out, depth_out, NR, K, "render_aux");
+  if (rc) return rc;
+  DINER_CHECK_ARG(field_ws, "render_aux: field scratch missing");
+  rc = diner_field_from_rays_f32(scene, mlp, rays, z, NR, K, precision, field_ws, workspace, stream);
+  if (rc) return rc;
+  return diner_composite_aux_f32(field_ws, z, rays, NR, K, white_bkgd, rgb_out, depth_out, weights_out, alpha_out, depth_var_out, stream);
+}
+
 // ---- scenes with any number of source views, 1 .. DINER_MAX_VIEWS, on the fused kernels (view groups) -----------------------------------
 static int check_views_nv(const DinerScene* scene, const char* who) {
   DINER_CHECK_ARG(scene, "%s: scene is null", who);
@@ -1400,4 +1419,17 @@ extern "C" int diner_render_views_f32(const DinerScene* scene, const DinerMlp* m
   rc = diner_field_from_rays_views_f32(scene, mlp, rays, z, NR, K, precision, field_ws, workspace, stream);
   if (rc) return rc;
   return diner_composite_f32(field_ws, z, rays, NR, K, white_bkgd, rgb_out, depth_out, weights_out, stream);
+}
+
+extern "C" int diner_render_views_aux_f32(const DinerScene* scene, const DinerMlp* mlp, const float* rays, const float* z, int NR, int K,
+                                          int white_bkgd, int precision, float* rgb_out, float* depth_out, float* weights_out,
+                                          float* field_ws, void* workspace, float* alpha_out, float* depth_var_out, void* stream) {
+  int rc = check_render_aux(rgb_out, depth_out, NR, K, "render_views_aux");
+  if (rc) return rc;
+  rc = check_views_nv(scene, "render_views_aux");
+  if (rc) return rc;
+  DINER_CHECK_ARG(field_ws, "render_views_aux: field scratch missing");
+  rc = diner_field_from_rays_views_f32(scene, mlp, rays, z, NR, K, precision, field_ws, workspace, stream);
+  if (rc) return rc;
+  return diner_composite_aux_f32(field_ws, z, rays, NR, K, white_bkgd, rgb_out, depth_out, weights_out, alpha_out, depth_var_out, stream);
 }

@@ -1191,16 +1191,20 @@ __global__ __launch_bounds__(256) void k_lin_out_bwd(const float* __restrict__ x
 //   T_k = prod_{j<k} t_j; w_k = a_k T_k; rgb = sum w c (+ 1 - sum w); depth = sum w z.
 // One thread per ray (K <= 1024; no per-K storage beyond d_field itself): G_k = g_rgb.c_k + g_depth z_k - [white] sum(g_rgb); dL/da_k = G_k T_k - S_k / t_k with
 // S_k = sum_{m>k} G_m w_m; dL/dsigma_k = dL/da_k * delta_k (1 - a_k) * [sigma_k > 0]; dL/dc_k = w_k g_rgb.
+// kAlpha: the ray's opacity alpha = sum w_k (nerf_renderer.py:359, diner_composite_aux_f32) carries a gradient g_alpha (NR) as well, which
+// adds g_alpha to every G_k of its ray; the <false> instance is the arithmetic of before (g_alpha is not read).
 constexpr int kCompBwdMaxK = 1024;
+template <bool kAlpha>
 __global__ void k_composite_bwd(const float* __restrict__ field, const float* __restrict__ z, const float* __restrict__ rays,
                                 int NR, int K, int white, const float* __restrict__ g_rgb, const float* __restrict__ g_depth,
-                                float* __restrict__ d_field) {
+                                const float* __restrict__ g_alpha, float* __restrict__ d_field) {
   const int r = blockIdx.x * blockDim.x + threadIdx.x;
   if (r >= NR) return;
   const float far = rays[(size_t)r * 8 + 7];
   const float gr = g_rgb[3 * r], gg = g_rgb[3 * r + 1], gb = g_rgb[3 * r + 2];
   const float gd = g_depth ? g_depth[r] : 0.0f;
   const float gw = white ? (gr + gg + gb) : 0.0f;
+  const float ga = kAlpha ? g_alpha[r] : 0.0f;
   const float* f = field + (size_t)r * K * 4;
   const float* zr = z + (size_t)r * K;
   float* df = d_field + (size_t)r * K * 4;
@@ -1222,7 +1226,8 @@ __global__ void k_composite_bwd(const float* __restrict__ field, const float* __
     const float a = 1.0f - expf(-delta * fmaxf(sg, 0.0f));
     const float t = 1.0f - a + 1e-10f;
     const float Tk = df[4 * k + 3];
-    const float G = gr * f[4 * k] + gg * f[4 * k + 1] + gb * f[4 * k + 2] + gd * zr[k] - gw;
+    float G = gr * f[4 * k] + gg * f[4 * k + 1] + gb * f[4 * k + 2] + gd * zr[k] - gw;
+    if (kAlpha) G += ga;
     const float da = G * Tk - S / t;
     df[4 * k + 3] = sg > 0.0f ? da * delta * (1.0f - a) : 0.0f;
     S += G * a * Tk;
@@ -1394,8 +1399,24 @@ extern "C" int diner_composite_bwd_f32(const float* field, const float* z, const
                                        const float* g_rgb, const float* g_depth, float* d_field, void* stream) {
   DINER_CHECK_ARG(field && z && rays && g_rgb && d_field, "composite_bwd: null pointer argument");
   DINER_CHECK_ARG(NR > 0 && K > 0 && K <= kCompBwdMaxK, "composite_bwd: bad sizes NR=%d K=%d (K <= %d)", NR, K, kCompBwdMaxK);
-  hipLaunchKernelGGL(k_composite_bwd, dim3((NR + 63) / 64), dim3(64), 0, (hipStream_t)stream, field, z, rays, NR, K,
-                     white_bkgd, g_rgb, g_depth, d_field);
+  hipLaunchKernelGGL(k_composite_bwd<false>, dim3((NR + 63) / 64), dim3(64), 0, (hipStream_t)stream, field, z, rays, NR, K,
+                     white_bkgd, g_rgb, g_depth, (const float*)nullptr, d_field);
+  DINER_LAUNCH_OK();
+  return 0;
+}
+
+// adjoint of diner_composite_aux_f32: the above plus the gradient of the ray's opacity (nerf_renderer.py:359); depth_var has none
+extern "C" int diner_composite_aux_bwd_f32(const float* field, const float* z, const float* rays, int NR, int K, int white_bkgd,
+                                           const float* g_rgb, const float* g_depth, const float* g_alpha, float* d_field,
+                                           void* stream) {
+  DINER_CHECK_ARG(field && z && rays && g_rgb && d_field, "composite_aux_bwd: null pointer argument");
+  DINER_CHECK_ARG(NR > 0 && K > 0 && K <= kCompBwdMaxK, "composite_aux_bwd: bad sizes NR=%d K=%d (K <= %d)", NR, K, kCompBwdMaxK);
+  if (g_alpha)
+    hipLaunchKernelGGL(k_composite_bwd<true>, dim3((NR + 63) / 64), dim3(64), 0, (hipStream_t)stream, field, z, rays, NR, K,
+                       white_bkgd, g_rgb, g_depth, g_alpha, d_field);
+  else
+    hipLaunchKernelGGL(k_composite_bwd<false>, dim3((NR + 63) / 64), dim3(64), 0, (hipStream_t)stream, field, z, rays, NR, K,
+                       white_bkgd, g_rgb, g_depth, (const float*)nullptr, d_field);
   DINER_LAUNCH_OK();
   return 0;
 }

@@ -23,6 +23,7 @@ PRED_SUFFIX = "-pred.png"
 GT_SUFFIX = "-gt.png"
 REF_SUFFIX = "-ref.png"
 DEPTH_SUFFIX = "-depth.png"
+ALPHA_SUFFIX = "-alpha.png"
 AVERAGE_SCORE_FILENAME = "average_scores.json"
 REPORT_DETAIL_FILENAME = "detailed_report.json"
 EXAMPLE_PLOT_FILENAME = "examples.png"
@@ -44,13 +45,14 @@ def _hip_device(device):
 
 
 @torch.no_grad()
-def write_prediction_folder(nerf, renderer, batches, outdir, znear, zfar, ray_batch_size=8192):
+def write_prediction_folder(nerf, renderer, batches, outdir, znear, zfar, ray_batch_size=8192, write_alpha=False):
     """Render every target view of `batches` (collated sample dicts of diner_amd.datasets) with `nerf` / `renderer` and write
     <sample_name>{-pred,-depth,-ref,-gt}.png into `outdir`: the render and its colour-mapped depth, the source views side by side and
     the target, each quantised as save_image does.  Returns {"sample_name": [...], "l1", "l2", "psnr", "ssim": float64 (N,)} -- the
-    scores of the renders against their targets, computed on the device from the fp32 tensors (not from the files)."""
+    scores of the renders against their targets, computed on the device from the fp32 tensors (not from the files).  write_alpha: also
+    <sample_name>-alpha.png, the render's opacity (the matte) as an 8-bit grey image, quantised like the others."""
     from .datasets import encode_args
-    from .imageio import depth_to_uint8, to_uint8
+    from .imageio import depth_to_uint8, gray_to_uint8, to_uint8
     from .metrics import KEYS, image_metrics
     from .render import predict_image
     os.makedirs(outdir, exist_ok=True)
@@ -60,14 +62,16 @@ def write_prediction_folder(nerf, renderer, batches, outdir, znear, zfar, ray_ba
         nerf.encode(**encode_args(batch, dev))
         gt = batch["target_rgb"].to(dev)
         H, W = gt.shape[-2:]
-        rgb, depth = predict_image(nerf, renderer, batch["target_extrinsics"].to(dev), batch["target_intrinsics"].to(dev), W, H,
-                                   znear, zfar, ray_batch_size=ray_batch_size)
+        rgb, depth, *alpha = predict_image(nerf, renderer, batch["target_extrinsics"].to(dev), batch["target_intrinsics"].to(dev), W, H,
+                                           znear, zfar, ray_batch_size=ray_batch_size, return_alpha=write_alpha)
         src = batch["src_rgbs"].to(dev)
         for i, stem in enumerate(batch["sample_name"]):
             write_png(os.path.join(outdir, stem + PRED_SUFFIX), to_uint8(rgb[i]))
             write_png(os.path.join(outdir, stem + DEPTH_SUFFIX), depth_to_uint8(depth[i]))
             write_png(os.path.join(outdir, stem + REF_SUFFIX), to_uint8(torch.cat(src[i].unbind(0), dim=-1)))
             write_png(os.path.join(outdir, stem + GT_SUFFIX), to_uint8(gt[i]))
+            if write_alpha:
+                write_png(os.path.join(outdir, stem + ALPHA_SUFFIX), gray_to_uint8(alpha[0][i]))
             names.append(stem)
         s = image_metrics(rgb, gt)
         for k in KEYS:

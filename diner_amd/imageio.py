@@ -41,6 +41,12 @@ def to_uint8(img):
     return out
 
 
+def gray_to_uint8(img):
+    """One-channel image (H,W) or (1,H,W) float32 in [0,1] (an opacity map) -> (H,W) uint8, through to_uint8's quantisation kernel."""
+    g = img.reshape(1, img.shape[-2], img.shape[-1])
+    return to_uint8(g.expand(3, -1, -1))[..., 0].contiguous()
+
+
 def _key_to_float(k):
     b = k if k >= 0 else k ^ 0x7fffffff
     return struct.unpack("<f", struct.pack("<i", b))[0]

@@ -124,7 +124,7 @@ def photometric(pred, gt, s=0, n_downsampling=3, w_antibias=0.0, w_mse=1.0):
 
 
 def calc_losses(nerf, renderer, batch, *, znear, zfar, ray_batch_size=128, w_vgg=0., vgg_spatch=64, w_antibias=0.,
-                antibias_downsampling=3, vgg_fn=None, seed=None, u=None, step=0, info=None):
+                antibias_downsampling=3, vgg_fn=None, seed=None, u=None, step=0, info=None, w_alpha=0.):
     """DINER.calc_losses (diner.py:217-290) for the drop-in modules: encode the batch's source views, pick the rays of the step, ONE
     renderer.forward, the objective.  -> {rgb_fine, vgg_fine, antibias, total}; total.backward() reaches the MLP parameters and
     encoder.latent.
@@ -137,7 +137,10 @@ def calc_losses(nerf, renderer, batch, *, znear, zfar, ray_batch_size=128, w_vgg
     keyed by (seed, step, object); seed None draws one from torch's global CPU generator.  batch["target_extrinsics"] /
     ["target_intrinsics"] are read on the host (keep them there to avoid the copy's wait).  info: an optional dict that receives the pixel
     indices of the step (`pix`), the sampler's per-object flag (`empty_mask`: 1 where the padded mask was all zero and the image centre
-    was taken) the float64 losses (`losses_f64`) and the rendered colours (`pred`)."""
+    was taken) the float64 losses (`losses_f64`) and the rendered colours (`pred`).
+    w_alpha > 0 (not in the reference) supervises the ray's opacity: adds w_alpha * mean((alpha - batch["target_alpha"] at the step's
+    pixels)^2), returned as losses["alpha"]; the opacity is a differentiable output of the compositor node
+    (renderer.forward(want_alpha=True)).  With w_alpha == 0 nothing changes."""
     target = batch["target_rgb"]
     SB, _, H, W = target.shape
     if w_vgg > 0 and vgg_fn is None:
@@ -158,7 +161,8 @@ def calc_losses(nerf, renderer, batch, *, znear, zfar, ray_batch_size=128, w_vgg
         s, flags = 0, None
         pix = torch.randint(0, H * W, (SB, int(ray_batch_size)), device=target.device, dtype=torch.int32)
     rays = gen_rays_at(batch["target_extrinsics"], batch["target_intrinsics"], W, H, znear, zfar, pix)
-    pred = renderer.forward(nerf, rays).fine.rgb
+    fine = renderer.forward(nerf, rays, want_alpha=True).fine if w_alpha > 0 else renderer.forward(nerf, rays).fine
+    pred = fine.rgb
     ph = photometric(pred, (target, pix), s, antibias_downsampling, w_antibias if patch else 0.0)
     total, loss_vgg = ph.total, 0.
     if w_vgg > 0:
@@ -167,4 +171,9 @@ def calc_losses(nerf, renderer, batch, *, znear, zfar, ray_batch_size=128, w_vgg
         total = total + w_vgg * loss_vgg
     if info is not None:        # pix (SB,B) int32; empty_mask (SB) int32 on the device (None without a patch): 1 where the image centre was taken
         info.update(pix=pix, empty_mask=flags, losses_f64=ph.losses_f64, pred=pred)
-    return dict(rgb_fine=ph.rgb_fine, vgg_fine=loss_vgg, antibias=ph.antibias if w_antibias > 0 else 0., total=total)
+    losses = dict(rgb_fine=ph.rgb_fine, vgg_fine=loss_vgg, antibias=ph.antibias if w_antibias > 0 else 0., total=total)
+    if w_alpha > 0:
+        gt_alpha = _f32c(batch["target_alpha"][:, 0]).to(target.device).view(SB, H * W).gather(1, pix.long())
+        losses["alpha"] = (fine.alpha - gt_alpha).square().mean()
+        losses["total"] = total + w_alpha * losses["alpha"]
+    return losses

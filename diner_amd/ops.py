@@ -513,31 +513,40 @@ def mlp_forward(mlp: HipMlp, zx):
     return out
 
 
-def composite(field, z, rays, white_bkgd, want_weights=True):
-    """(NR,K,4),(NR,K),(NR,8) -> weights (NR,K) | None, rgb (NR,3), depth (NR); K <= 1024 (the bounded kernel for K <= 256)."""
+def composite(field, z, rays, white_bkgd, want_weights=True, want_aux=False):
+    """(NR,K,4),(NR,K),(NR,8) -> weights (NR,K) | None, rgb (NR,3), depth (NR); K <= 1024 (the bounded kernel for K <= 256).
+    want_aux: -> weights | None, rgb, depth, alpha (NR), depth_var (NR): the ray's opacity sum_k w_k (pix_alpha of
+    nerf_renderer.py:359) and the spread sum_k w_k (z_k - depth)^2 of its samples around `depth`, from the same launch
+    (diner_composite_aux_f32); weights, rgb and depth are those of the default call bit for bit."""
     _require_hip(field, z, rays)
     field, z, rays = _f32c(field), _f32c(z), _f32c(rays)
     NR, K = z.shape
     rgb = torch.empty(NR, 3, device=z.device, dtype=torch.float32)
     depth = torch.empty(NR, device=z.device, dtype=torch.float32)
     w = torch.empty(NR, K, device=z.device, dtype=torch.float32) if want_weights else None
-    if NR == 0:
-        return w, rgb, depth
-    with torch.cuda.device(z.device):
-        _lib.check(lib.diner_composite_long_f32(_ptr(field), _ptr(z), _ptr(rays), NR, K, int(bool(white_bkgd)),
-                                                _ptr(rgb), _ptr(depth), _ptr(w), _stream()))
-    return w, rgb, depth
+    alpha = torch.empty(NR, device=z.device, dtype=torch.float32) if want_aux else None
+    var = torch.empty(NR, device=z.device, dtype=torch.float32) if want_aux else None
+    if NR > 0:
+        with torch.cuda.device(z.device):
+            if want_aux:
+                _lib.check(lib.diner_composite_aux_f32(_ptr(field), _ptr(z), _ptr(rays), NR, K, int(bool(white_bkgd)),
+                                                       _ptr(rgb), _ptr(depth), _ptr(w), _ptr(alpha), _ptr(var), _stream()))
+            else:
+                _lib.check(lib.diner_composite_long_f32(_ptr(field), _ptr(z), _ptr(rays), NR, K, int(bool(white_bkgd)),
+                                                        _ptr(rgb), _ptr(depth), _ptr(w), _stream()))
+    return (w, rgb, depth, alpha, var) if want_aux else (w, rgb, depth)
 
 
-def render(scene: HipScene, mlp: HipMlp, rays, z, white_bkgd, want_weights=False, precision=None):
-    """field + composite (NeRFRendererDGS.composite): -> weights | None, rgb, depth.  A HipMlp takes a scene of any view count (four on
-    the fused kernels directly, any other number in groups of four); a GenericMlp renders on the generic exact-fp32 path."""
+def render(scene: HipScene, mlp: HipMlp, rays, z, white_bkgd, want_weights=False, precision=None, want_aux=False):
+    """field + composite (NeRFRendererDGS.composite): -> weights | None, rgb, depth [, alpha, depth_var with want_aux, see composite].
+    A HipMlp takes a scene of any view count (four on the fused kernels directly, any other number in groups of four); a GenericMlp
+    renders on the generic exact-fp32 path."""
     if isinstance(mlp, GenericMlp):        # a configuration outside the fused kernels: exact fp32, one GEMM launch per layer
         NR, K = z.shape
         field = field_generic(scene, mlp, rays=rays, z=z).view(NR, K, 4)
     else:
         field = field_from_rays(scene, mlp, rays, z, precision=precision)
-    return composite(field, z, rays, white_bkgd, want_weights)
+    return composite(field, z, rays, white_bkgd, want_weights, want_aux)
 
 
 def posenc(x, num_freqs, freq_factor, include_input=True):

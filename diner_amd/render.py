@@ -60,9 +60,10 @@ def gather_tiles(local, n_total, rank, world, group=None, force=False):
 
 @torch.no_grad()
 def predict_image(nerf, renderer, target_extrinsics, target_intrinsics, W, H, znear, zfar, ray_batch_size=8192,
-                  rank=0, world=1, group=None, seed=None):
+                  rank=0, world=1, group=None, seed=None, return_alpha=False):
     """Render the (SB) target views described by target_extrinsics (SB,4,4) / target_intrinsics (SB,3,3) of the
-    scene last passed to nerf.encode().  Returns rgb (SB,3,H,W), depth (SB,1,H,W) on rank 0 (None elsewhere).
+    scene last passed to nerf.encode().  Returns rgb (SB,3,H,W), depth (SB,1,H,W) on rank 0 (None elsewhere); with return_alpha also
+    the opacity map alpha (SB,1,H,W) (renderer.forward(want_alpha=True): one more channel in the gathered tiles, 20 B/ray).
     Same ray order (row-major pixels, centres at +0.5) and output layout as diner.py:79-92.  Noise injected with
     diner_amd.noise.inject for the whole (SB, H*W, .) ray list is handed to every batch as the matching slice (parity
     tests); without injection the sampler draws in-kernel Philox noise keyed by (`seed`, position of the ray in the frame):
@@ -95,11 +96,15 @@ def predict_image(nerf, renderer, target_extrinsics, target_intrinsics, W, H, zn
         rb = rays[:, r0 - base:r1 - base].contiguous()
         ctx = contextlib.nullcontext() if inj is None else _noise.inject(*(None if t is None else t[:, r0:r1] for t in inj))
         with ctx, _noise.keyed(seed, r0):
-            out = renderer.forward(model=nerf, rays=rb)
-        tiles.append(torch.cat((out.fine.rgb, out.fine.depth.unsqueeze(-1)), dim=-1))      # (SB, b, 4)
-    local = torch.cat(tiles, dim=1) if tiles else torch.zeros(SB, 0, 4, device=dev)
-    full = gather_tiles(local.permute(1, 0, 2).reshape(hi - lo, SB * 4), H * W, rank, world, group)
+            out = renderer.forward(model=nerf, rays=rb, want_alpha=True) if return_alpha else renderer.forward(model=nerf, rays=rb)
+        parts = (out.fine.rgb, out.fine.depth.unsqueeze(-1)) + ((out.fine.alpha.unsqueeze(-1),) if return_alpha else ())
+        tiles.append(torch.cat(parts, dim=-1))                                              # (SB, b, C)
+    C = 5 if return_alpha else 4
+    local = torch.cat(tiles, dim=1) if tiles else torch.zeros(SB, 0, C, device=dev)
+    full = gather_tiles(local.permute(1, 0, 2).reshape(hi - lo, SB * C), H * W, rank, world, group)
     if full is None:
-        return None, None
-    full = full.view(H, W, SB, 4).permute(2, 3, 0, 1)                                       # (SB,4,H,W)
+        return (None, None, None) if return_alpha else (None, None)
+    full = full.view(H, W, SB, C).permute(2, 3, 0, 1)                                       # (SB,C,H,W)
+    if return_alpha:
+        return full[:, :3].contiguous(), full[:, 3:4].contiguous(), full[:, 4:5].contiguous()
     return full[:, :3].contiguous(), full[:, 3:4].contiguous()

@@ -417,6 +417,33 @@ class CompositeFunction(torch.autograd.Function):
         return d_field, None, None, None
 
 
+class CompositeAuxFunction(torch.autograd.Function):
+    """CompositeFunction with the ray's opacity as a third differentiable output: -> rgb (NR,3), depth (NR), alpha (NR) = sum_k w_k
+    (pix_alpha of nerf_renderer.py:359), from the aux compositor instance; the backward is diner_composite_aux_bwd_f32."""
+
+    @staticmethod
+    def forward(ctx, field, z, rays, white_bkgd):
+        from . import ops
+        field, z, rays = _f32c(field.detach()), _f32c(z.detach()), _f32c(rays.detach())
+        _, rgb, depth, alpha, _ = ops.composite(field, z, rays, white_bkgd, want_weights=False, want_aux=True)
+        ctx.save_for_backward(field, z, rays)
+        ctx.white = bool(white_bkgd)
+        return rgb, depth, alpha
+
+    @staticmethod
+    def backward(ctx, g_rgb, g_depth, g_alpha):
+        field, z, rays = ctx.saved_tensors
+        NR, K = z.shape
+        d_field = torch.empty_like(field)
+        with torch.cuda.device(field.device):
+            g_rgb = _f32c(g_rgb) if g_rgb is not None else torch.zeros(NR, 3, device=field.device)
+            gd = _f32c(g_depth) if g_depth is not None else None
+            ga = _f32c(g_alpha) if g_alpha is not None else None
+            _lib.check(lib.diner_composite_aux_bwd_f32(_ptr(field), _ptr(z), _ptr(rays), NR, K, int(ctx.white), _ptr(g_rgb),
+                                                       _ptr(gd), _ptr(ga), _ptr(d_field), _stream()))
+        return d_field, None, None, None
+
+
 class _ObjectSlabs(torch.autograd.Function):
     """latent (SB, NV, C, Hf, Wf) -> its SB per-object slabs as separate autograd inputs of the per-object field nodes.  Plain indexing
     (`latent[sb]`) makes autograd build each object's gradient as a zero-filled tensor of the WHOLE latent with one slab copied in and then
@@ -557,5 +584,8 @@ def field_train(scene: HipScene, xyz, viewdirs, latent, params, freq_factor=6.28
     return FieldFunction.apply(scene, xyz, viewdirs, latent, float(freq_factor), *params)
 
 
-def composite_train(field, z, rays, white_bkgd):
+def composite_train(field, z, rays, white_bkgd, want_alpha=False):
+    """-> rgb, depth [, alpha with want_alpha: the ray's opacity, differentiable like the other two]."""
+    if want_alpha:
+        return CompositeAuxFunction.apply(field, z, rays, white_bkgd)
     return CompositeFunction.apply(field, z, rays, white_bkgd)

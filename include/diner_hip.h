@@ -243,11 +243,33 @@ int diner_mlp_forward_f32(const DinerMlp* mlp, const float* zx, long long B, flo
 int diner_composite_f32(const float* field, const float* z, const float* rays, int NR, int K, int white_bkgd,
                         float* rgb_out, float* depth_out, float* weights_out, void* stream);
 
+/* a9 with the ray's opacity and depth spread as two more per-ray outputs; new symbol, no ABI bump.  The reference computes the opacity,
+ * pix_alpha = weights.sum(-1) (nerf_renderer.py:359), uses it for the white background and never returns it.
+ *   alpha_out      (NR) or NULL: sum_k w_k, the value the white background is blended with
+ *   depth_var_out  (NR) or NULL: max(0, sum_k w_k (z_k - depth)^2) around the unnormalised depth = sum_k w_k z_k written to depth_out, in the
+ *                  centred two-pass form; the sum can be negative only where a weight is (a sample beyond `far`, :301), and reads 0 there.
+ *                  An inference diagnostic: it has no adjoint (diner_composite_aux_bwd_f32 takes no gradient for it).
+ * rgb, depth and weights are those of diner_composite_long_f32 bit for bit.  Limits: K <= 1024 (4 samples per lane up to 256, 16 above);
+ * NULL rgb_out / depth_out or sizes outside are DINER_E_INVALID before any device work. */
+int diner_composite_aux_f32(const float* field, const float* z, const float* rays, int NR, int K, int white_bkgd,
+                            float* rgb_out, float* depth_out, float* weights_out, float* alpha_out, float* depth_var_out,
+                            void* stream);
+
 /* ---- a10: NeRFRendererDGS.composite / forward (nerf_renderer.py:286-365, :399-424) -----------
  * field + composite in one call; `field_ws` is (NR*K,4) scratch the caller provides. */
 int diner_render_f32(const DinerScene* scene, const DinerMlp* mlp, const float* rays, const float* z, int NR, int K,
                      int white_bkgd, int precision, float* rgb_out, float* depth_out, float* weights_out,
                      float* field_ws, void* workspace, void* stream);
+
+/* diner_render_f32 / diner_render_views_f32 with the opacity and depth-spread outputs of diner_composite_aux_f32 (pix_alpha of
+ * nerf_renderer.py:359; either pointer may be NULL): the same field code as their namesakes, then the aux compositor, hence K <= 1024.
+ * The compositor's argument checks (NULL rgb_out / depth_out, NR, K) come first: DINER_E_INVALID before any device work. */
+int diner_render_aux_f32(const DinerScene* scene, const DinerMlp* mlp, const float* rays, const float* z, int NR, int K,
+                         int white_bkgd, int precision, float* rgb_out, float* depth_out, float* weights_out,
+                         float* field_ws, void* workspace, float* alpha_out, float* depth_var_out, void* stream);
+int diner_render_views_aux_f32(const DinerScene* scene, const DinerMlp* mlp, const float* rays, const float* z, int NR, int K,
+                               int white_bkgd, int precision, float* rgb_out, float* depth_out, float* weights_out,
+                               float* field_ws, void* workspace, float* alpha_out, float* depth_var_out, void* stream);
 
 /* ---- stage-level entries that back the reference's small public methods ---------------------- */
 /* PositionalEncoding.forward (positional_encoding.py:33-53): x (N,d_in) -> (N, d_in*(2F+include_input)) */
@@ -337,6 +359,11 @@ int diner_field_act_f32(const float* raw, const float* dout, long long P, int ld
  *   K <= 1024 (the range of diner_composite_long_f32; K <= 256 before the long entries). */
 int diner_composite_bwd_f32(const float* field, const float* z, const float* rays, int NR, int K, int white_bkgd,
                             const float* g_rgb, const float* g_depth, float* d_field, void* stream);
+/* adjoint of diner_composite_aux_f32: the same, plus g_alpha (NR) or NULL, the gradient of the ray's opacity alpha = sum_k w_k
+ * (nerf_renderer.py:359), which adds g_alpha to every sample's G_k.  depth_var carries no gradient.  With g_alpha NULL the result is that
+ * of diner_composite_bwd_f32 bit for bit.  New symbol, no ABI bump. */
+int diner_composite_aux_bwd_f32(const float* field, const float* z, const float* rays, int NR, int K, int white_bkgd,
+                                const float* g_rgb, const float* g_depth, const float* g_alpha, float* d_field, void* stream);
 
 /* (n, HW, C) channels-last -> (n, C, HW): the latent gradient of diner_field_train_backward_f32 / diner_scatter_latent_grad_f32 in the
  * layout of the encoder's feature map (SpatialEncoder.latent, image_encoder.py:82-95), through LDS tiles. */

@@ -45,8 +45,9 @@ class NeRFRendererDGS(torch.nn.Module):
         if not (hasattr(model, "hip_scene") and hasattr(model, "hip_mlp")):
             raise TypeError("diner_amd: `model` must be src.models.pixelnerf.PixelNeRF of this package")
 
-    def _render_train_batch(self, model, rays, z, want_weights):
-        """The SB objects of a training step at once (ABI v6): rays (SB,NR,8), z (SB,NR,K) -> weights | None, rgb (SB,NR,3), depth (SB,NR).
+    def _render_train_batch(self, model, rays, z, want_weights, want_alpha=False):
+        """The SB objects of a training step at once (ABI v6): rays (SB,NR,8), z (SB,NR,K) -> weights | None, rgb (SB,NR,3), depth (SB,NR)
+        [, alpha (SB,NR) with want_alpha: the opacity, a third output of the compositor node].
         One field node for all objects (diner_amd.train.field_train_batch: the layer products of the backward run once over SB x NR x K x NV
         rows), one compositor node over the SB x NR rays."""
         from diner_amd import train
@@ -62,8 +63,14 @@ class NeRFRendererDGS(torch.nn.Module):
             field = train.field_train_batch(scenes, xyz, dirs, model.encoder.latent, train.mlp_params(model.mlp_fine),
                                             model.poscode.freq_factor).view(SB * NR, K, 4)
         zf, rf = z.reshape(SB * NR, K), r.reshape(SB * NR, 8)
-        rgb, depth = train.composite_train(field, zf, rf, self.white_bkgd)
+        alpha = None
+        if want_alpha:
+            rgb, depth, alpha = train.composite_train(field, zf, rf, self.white_bkgd, want_alpha=True)
+        else:
+            rgb, depth = train.composite_train(field, zf, rf, self.white_bkgd)
         w = ops.composite(field.detach(), zf, rf, self.white_bkgd, want_weights=True)[0].view(SB, NR, K) if want_weights else None
+        if want_alpha:
+            return w, rgb.view(SB, NR, 3), depth.view(SB, NR), alpha.view(SB, NR)
         return w, rgb.view(SB, NR, 3), depth.view(SB, NR)
 
     def sample_coarse(self, rays, n_coarse=None):
@@ -121,8 +128,11 @@ class NeRFRendererDGS(torch.nn.Module):
                    for sb in range(SB)]
         return tuple(torch.stack([r[i] for r in res]) for i in range(3))
 
-    def forward(self, model, rays, want_weights=False):
-        """rays (SB,B,8) -> DotMap(fine=DotMap(rgb (SB,B,3), depth (SB,B) [, weights (SB,B,K)]))   (:399-430)."""
+    def forward(self, model, rays, want_weights=False, want_alpha=False):
+        """rays (SB,B,8) -> DotMap(fine=DotMap(rgb (SB,B,3), depth (SB,B) [, weights (SB,B,K)]))   (:399-430).
+        want_alpha (not in the reference, which computes the opacity at :359 and drops it): fine gains alpha (SB,B) = sum_k w_k -- in grad
+        mode an output of the compositor's autograd node -- and, without grad, depth_var (SB,B), the spread of the ray's samples around
+        its depth (a diagnostic without a gradient)."""
         assert len(rays.shape) == 3
         self._check_model(model)
         model._check_poscode()
@@ -140,20 +150,30 @@ class NeRFRendererDGS(torch.nn.Module):
                 seed, r0 = _key(sb)
                 zs.append(ops.sample_depthguided_long(model.hip_scene(sb), rays[sb], self.n_samples, self.n_depth_candidates,
                                                       self.n_gaussian, 0.05, noise=nz, seed=seed, ray_index0=r0))
-            w, rgb, depth = self._render_train_batch(model, rays, torch.stack(zs), want_weights)
-            return DotMap(fine=self._format_outputs(w, rgb, depth, want_weights=want_weights))
+            w, rgb, depth, *aux = self._render_train_batch(model, rays, torch.stack(zs), want_weights, want_alpha)
+            out = self._format_outputs(w, rgb, depth, want_weights=want_weights)
+            if want_alpha:
+                out.alpha = aux[0]
+            return DotMap(fine=out)
+        alphas, dvars = [], []
         for sb in range(SB):
             scene = model.hip_scene(sb)
             nz = None if inj is None else tuple(None if t is None else t[sb] for t in inj)
             seed, r0 = _key(sb)
             z = ops.sample_depthguided_long(scene, rays[sb], self.n_samples, self.n_depth_candidates, self.n_gaussian,
                                             0.05, noise=nz, seed=seed, ray_index0=r0)
-            w, rgb, depth = ops.render(scene, mlp, rays[sb], z, self.white_bkgd, want_weights=want_weights)
+            w, rgb, depth, *aux = ops.render(scene, mlp, rays[sb], z, self.white_bkgd, want_weights=want_weights, want_aux=want_alpha)
             rgbs.append(rgb)
             depths.append(depth)
             wts.append(w)
-        return DotMap(fine=self._format_outputs(torch.stack(wts) if want_weights else None, torch.stack(rgbs),
-                                                torch.stack(depths), want_weights=want_weights))
+            if want_alpha:
+                alphas.append(aux[0])
+                dvars.append(aux[1])
+        out = self._format_outputs(torch.stack(wts) if want_weights else None, torch.stack(rgbs), torch.stack(depths),
+                                   want_weights=want_weights)
+        if want_alpha:
+            out.alpha, out.depth_var = torch.stack(alphas), torch.stack(dvars)
+        return DotMap(fine=out)
 
     def _format_outputs(self, weights, rgb, depth, want_weights):
         out = DotMap(rgb=rgb, depth=depth)
