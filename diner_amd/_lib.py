@@ -49,6 +49,14 @@ SIGNATURES = {
                                               C.c_void_p, C.c_void_p]),
     "diner_composite_long_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                            C.c_void_p, C.c_void_p, C.c_void_p]),
+    "diner_sample_depthguided_info_f32": (C.c_int, [C.POINTER(DinerScene), C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                    C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                    C.c_uint64, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                    C.c_void_p, C.c_void_p]),
+    "diner_sample_depthguided_info_long_f32": (C.c_int, [C.POINTER(DinerScene), C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                         C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                         C.c_uint64, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                         C.c_void_p, C.c_void_p]),
     "diner_scene_proj_bytes": (C.c_size_t, [C.POINTER(DinerScene)]),
     "diner_scene_prepare_f32": (C.c_int, [C.POINTER(DinerScene), C.c_void_p, C.c_void_p, C.c_void_p]),
     "diner_scene_proj_f16_bytes": (C.c_size_t, [C.POINTER(DinerScene)]),

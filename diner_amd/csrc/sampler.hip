@@ -35,6 +35,16 @@ struct SamplerArgs {
   float depth_diff_max;
 };
 
+// what the info kernels write beside z_out, each only where its pointer is set: the unfilled samples in the reference's slot order
+// (picks by descending likelihood, then the gaussian samples), the likelihood and candidate index of every pick slot, and per ray
+// (sum L, sum O, mean, sigma) of the gaussian fit
+struct SamplerInfo {
+  float* z_ordered;   // (NR, K)
+  float* slot_L;      // (NR, K - G)
+  int* slot_idx;      // (NR, K - G)
+  float* stats;       // (NR, 4)
+};
+
 // surface likelihood of one candidate in one source view (nerf_renderer.py:107-128)
 // kDirHere: the ray direction in this camera is rotated here, where the normal test needs it (dcam unused; dx, dy, dz the world
 // direction) -- the wide scene's instances, which keep no per-view array
@@ -137,6 +147,45 @@ __device__ __forceinline__ void bitonic_sort(float* s, int n2, int lane) {
   }
 }
 
+// in-LDS key/value bitonic sort of n2 (power of two, 1 allowed) pairs: key descending, equal keys by ascending value -- the picks of a
+// ray by descending likelihood bits, ties by candidate index as at the cut-off.  Empty pairs (key 0, value -1) compare equal to each
+// other and below every pick (picks have key > 0).  Same calling rule as bitonic_sort.
+template <int kThreads = kWave>
+__device__ __forceinline__ void bitonic_sort_pairs(uint32_t* key, int* val, int n2, int lane) {
+  for (int k = 2; k <= n2; k <<= 1) {
+    for (int j = k >> 1; j > 0; j >>= 1) {
+      for (int t = lane; t < n2 / 2; t += kThreads) {
+        const int lo = ((t / j) * 2 * j) + (t % j);
+        const int hi = lo + j;
+        const bool fwd = ((lo & k) == 0);
+        const uint32_t ka = key[lo], kb = key[hi];
+        const int va = val[lo], vb = val[hi];
+        const bool a_first = ka > kb || (ka == kb && va < vb);
+        const bool b_first = kb > ka || (ka == kb && vb < va);
+        if (fwd ? b_first : a_first) { key[lo] = kb; key[hi] = ka; val[lo] = vb; val[hi] = va; }
+      }
+      __syncthreads();
+    }
+  }
+}
+
+// the info kernels' ordered picks: the want pairs the compaction left in (key, val) sorted, then per slot the candidate's depth from the
+// intact Z row into S (empty slot: z = 0, likelihood 0, index -1) and the two per-slot outputs
+template <int kThreads>
+__device__ __forceinline__ void order_picks(uint32_t* key, int* val, const float* Z, float* S, int want, int w2, int lane, bool live,
+                                            const SamplerInfo& info, size_t ray) {
+  __syncthreads();
+  bitonic_sort_pairs<kThreads>(key, val, w2, lane);
+  for (int j = lane; j < want; j += kThreads) {
+    const int idx = val[j];
+    S[j] = idx >= 0 ? Z[idx] : 0.0f;
+    if (live) {
+      if (info.slot_L) info.slot_L[ray * want + j] = __uint_as_float(key[j]);
+      if (info.slot_idx) info.slot_idx[ray * want + j] = idx;
+    }
+  }
+}
+
 // fill_up_uniform_samples on a K-slot LDS row (nerf_renderer.py:367-397); row padded with +inf to n2.
 // kThreads == kWave: one wave per row; kThreads == kWideThreads: one workgroup per row, `red` holds the count's partials.
 template <int kThreads = kWave>
@@ -164,8 +213,10 @@ __device__ __forceinline__ void fill_and_sort(float* s, int K, int n2, float nea
 
 // Scene: SceneDev (1..4 views, the instance every 4-view call runs) or SceneDevWide (5..16 views).  The body is a device function of its
 // own: written inside the kernel, the 16-view instance's register allocation left a 64-byte stack slot behind (no scratch access)
-template <class Scene>
-__device__ __forceinline__ void sample_depthguided_body(const Scene& sc, const SamplerArgs& a) {
+// kInfo: the info kernel -- the picks ordered (order_picks, the pairs in the dead L row: keys at [0, 256), indices at [256, 512)) and
+// SamplerInfo's outputs written; z_out is the plain kernel's bit for bit (the fill sorts the same multiset)
+template <class Scene, bool kInfo = false>
+__device__ __forceinline__ void sample_depthguided_body(const Scene& sc, const SamplerArgs& a, const SamplerInfo& info = SamplerInfo{}) {
   __shared__ float sL[kRaysPerBlock][kMaxCand];
   __shared__ float sZ[kRaysPerBlock][kMaxCand];
   __shared__ float sS[kRaysPerBlock][kMaxK];
@@ -267,6 +318,19 @@ __device__ __forceinline__ void sample_depthguided_body(const Scene& sc, const S
     }
     sd = sqrtf(wave_sum(acc));
   }
+  if constexpr (kInfo) {
+    float lsum = 0.0f;
+#pragma unroll
+    for (int k = 0; k < kCandPerLane; ++k) lsum += lv[k];
+    lsum = wave_sum(lsum);
+    if (info.stats && live && lane == 0) {
+      float* st = info.stats + (size_t)ray * 4;
+      st[0] = lsum;
+      st[1] = osum;
+      st[2] = mean;
+      st[3] = sd;
+    }
+  }
 
   // ---- top-(K-G) by likelihood: radix select on the (non-negative) float bit patterns (:172-178) ----
   const int K = a.K, G = a.G, want = K - G;
@@ -301,17 +365,30 @@ __device__ __forceinline__ void sample_depthguided_body(const Scene& sc, const S
   int off_gt = pre_gt - n_gt;
   int off_eq = pre_eq - n_eq;
   for (int j = lane; j < kMaxK; j += kWave) S[j] = (j < K) ? 0.0f : __builtin_inff();
+  uint32_t* pkey = reinterpret_cast<uint32_t*>(L);       // kInfo: the L row is dead (lv holds it), Z stays for the depths
+  int* pval = reinterpret_cast<int*>(L) + kMaxK;
+  int w2 = 1;
+  if constexpr (kInfo) {
+    while (w2 < want) w2 <<= 1;
+    if (want > 0)
+      for (int j = lane; j < w2; j += kWave) { pkey[j] = 0u; pval[j] = -1; }
+  }
   __syncthreads();
   if (want > 0) {
 #pragma unroll
     for (int k = 0; k < kCandPerLane; ++k) {
       if (ub[k] > T) {
-        S[off_gt++] = zv[k];
+        if constexpr (kInfo) { pkey[off_gt] = ub[k]; pval[off_gt] = lane * kCandPerLane + k; ++off_gt; }
+        else S[off_gt++] = zv[k];
       } else if (ub[k] == T && T > 0) {
-        if (off_eq < eq_take) S[tot_gt + off_eq] = zv[k];
+        if (off_eq < eq_take) {
+          if constexpr (kInfo) { pkey[tot_gt + off_eq] = ub[k]; pval[tot_gt + off_eq] = lane * kCandPerLane + k; }
+          else S[tot_gt + off_eq] = zv[k];
+        }
         ++off_eq;
       }
     }
+    if constexpr (kInfo) order_picks<kWave>(pkey, pval, Z, S, want, w2, lane, live, info, (size_t)ray);
   }
   // gaussian samples into the LAST G slots of every ray (zeros when the ray sees no surface)   (:181-190)
   for (int g = lane; g < G; g += kWave) {
@@ -324,8 +401,9 @@ __device__ __forceinline__ void sample_depthguided_body(const Scene& sc, const S
     S[want + g] = zg;
   }
   __syncthreads();
-  if (a.z_unfilled && live)
-    for (int j = lane; j < K; j += kWave) a.z_unfilled[(size_t)ray * K + j] = S[j];
+  float* zu = kInfo ? info.z_ordered : a.z_unfilled;
+  if (zu && live)
+    for (int j = lane; j < K; j += kWave) zu[(size_t)ray * K + j] = S[j];
 
   int n2 = 2;
   while (n2 < K) n2 <<= 1;
@@ -336,6 +414,10 @@ __device__ __forceinline__ void sample_depthguided_body(const Scene& sc, const S
 
 template <class Scene>
 __global__ __launch_bounds__(kRaysPerBlock* kWave) void k_sample_depthguided(Scene sc, SamplerArgs a) { sample_depthguided_body(sc, a); }
+template <class Scene>
+__global__ __launch_bounds__(kRaysPerBlock* kWave) void k_sample_depthguided_info(Scene sc, SamplerArgs a, SamplerInfo info) {
+  sample_depthguided_body<Scene, true>(sc, a, info);
+}
 
 __global__ __launch_bounds__(kRaysPerBlock* kWave) void k_fill_uniform(const float* z_in, const float* rays, int NR, int K,
                                                                         const float* noise_fill, uint64_t seed,
@@ -362,8 +444,15 @@ __global__ __launch_bounds__(kRaysPerBlock* kWave) void k_fill_uniform(const flo
 // likelihood bits are view_likelihood's, the pick rule (all candidates above the threshold T, ties at T in index order)
 // and the noise keys are the bounded kernel's: a ray's picks and draws do not depend on which kernel ran.
 // LDS: 2 x 16 KB candidate rows + 4 KB slot row + the reduction carries (~36 KB, 4 workgroups per CU).
-template <class Scene>
-__global__ __launch_bounds__(kWideThreads) void k_sample_depthguided_wide(Scene sc, SamplerArgs a) {
+// Info...: empty (the plain kernel, two arguments) or SamplerInfo (the info kernel: as in sample_depthguided_body, the pairs in the
+// dead L row, keys at [0, 1024), indices at [1024, 2048)).  The text stays inside the kernel: moved into a device function shared by
+// two wrappers, the plain 16-view instance spilt four more SGPRs.
+__device__ __forceinline__ SamplerInfo info_of() { return SamplerInfo{}; }
+__device__ __forceinline__ SamplerInfo info_of(const SamplerInfo& i) { return i; }
+template <class Scene, class... Info>
+__global__ __launch_bounds__(kWideThreads) void k_sample_depthguided_wide(Scene sc, SamplerArgs a, Info... extra) {
+  constexpr bool kInfo = sizeof...(Info) > 0;
+  const SamplerInfo info = info_of(extra...);
   __shared__ float L[kWideMaxCand];
   __shared__ float Z[kWideMaxCand];
   __shared__ float S[kLongMaxK];
@@ -470,6 +559,19 @@ __global__ __launch_bounds__(kWideThreads) void k_sample_depthguided_wide(Scene 
     }
     sd = sqrtf(wg_sum(acc, red.f, par, tid));
   }
+  if constexpr (kInfo) {
+    float lsum = 0.0f;
+#pragma unroll
+    for (int k = 0; k < kCandPerLane; ++k) lsum += lv[k];
+    lsum = wg_sum(lsum, red.f, par, tid);
+    if (info.stats && tid == 0) {
+      float* st = info.stats + (size_t)ray * 4;
+      st[0] = lsum;
+      st[1] = osum;
+      st[2] = mean;
+      st[3] = sd;
+    }
+  }
 
   // ---- top-(K-G) by likelihood: radix select on the (non-negative) float bit patterns (:172-178) ----
   const int K = a.K, G = a.G, want = K - G;
@@ -500,6 +602,14 @@ __global__ __launch_bounds__(kWideThreads) void k_sample_depthguided_wide(Scene 
     if (lane >= o) { pre_gt += g1; pre_eq += e1; }
   }
   if (lane == kWave - 1) { wscan[0][wave] = pre_gt; wscan[1][wave] = pre_eq; }
+  uint32_t* pkey = reinterpret_cast<uint32_t*>(L);       // kInfo: the L row is dead (every thread's lv holds its part), Z stays for the depths
+  int* pval = reinterpret_cast<int*>(L) + kLongMaxK;
+  int w2 = 1;
+  if constexpr (kInfo) {
+    while (w2 < want) w2 <<= 1;
+    if (want > 0)
+      for (int j = tid; j < w2; j += kWideThreads) { pkey[j] = 0u; pval[j] = -1; }
+  }
   __syncthreads();
   int base_gt = 0, base_eq = 0, tot_gt = 0;  // earlier waves' totals (exclusive scan over waves) and the ray's total
   for (int w = 0; w < kWideWaves; ++w) {
@@ -513,12 +623,17 @@ __global__ __launch_bounds__(kWideThreads) void k_sample_depthguided_wide(Scene 
 #pragma unroll
     for (int k = 0; k < kCandPerLane; ++k) {
       if (ub[k] > T) {
-        S[off_gt++] = zv[k];
+        if constexpr (kInfo) { pkey[off_gt] = ub[k]; pval[off_gt] = tid * kCandPerLane + k; ++off_gt; }
+        else S[off_gt++] = zv[k];
       } else if (ub[k] == T && T > 0) {
-        if (off_eq < eq_take) S[tot_gt + off_eq] = zv[k];
+        if (off_eq < eq_take) {
+          if constexpr (kInfo) { pkey[tot_gt + off_eq] = ub[k]; pval[tot_gt + off_eq] = tid * kCandPerLane + k; }
+          else S[tot_gt + off_eq] = zv[k];
+        }
         ++off_eq;
       }
     }
+    if constexpr (kInfo) order_picks<kWideThreads>(pkey, pval, Z, S, want, w2, tid, true, info, (size_t)ray);
   }
   // gaussian samples into the LAST G slots of every ray (zeros when the ray sees no surface)   (:181-190)
   for (int g = tid; g < G; g += kWideThreads) {
@@ -531,8 +646,9 @@ __global__ __launch_bounds__(kWideThreads) void k_sample_depthguided_wide(Scene 
     S[want + g] = zg;
   }
   __syncthreads();
-  if (a.z_unfilled)
-    for (int j = tid; j < K; j += kWideThreads) a.z_unfilled[(size_t)ray * K + j] = S[j];
+  float* zu = kInfo ? info.z_ordered : a.z_unfilled;
+  if (zu)
+    for (int j = tid; j < K; j += kWideThreads) zu[(size_t)ray * K + j] = S[j];
   __syncthreads();      // the four waves share S: the sort below must not swap slots another wave has yet to copy out
 
   int n2 = 2;
@@ -562,12 +678,18 @@ __global__ __launch_bounds__(kWideThreads) void k_fill_uniform_wide(const float*
 // the scene's cameras into the kernel arguments and the launch: 1..4 views on the SceneDev instance (the kernels as they were before the
 // wide scene existed), 5..16 on the SceneDevWide one
 template <class Scene>
-static int launch_sampler(const DinerScene* scene, const SamplerArgs& a, bool wide, const char* who, hipStream_t stream) {
+static int launch_sampler(const DinerScene* scene, const SamplerArgs& a, bool wide, const char* who, hipStream_t stream,
+                          const SamplerInfo* info) {
   Scene sd;
   int rc = make_scene_dev(scene, &sd);
   if (rc) return rc;
   DINER_CHECK_ARG(scene->depth && scene->depth_std && scene->normals && scene->std_pad_scale, "%s: scene depth/std/normal maps missing", who);
-  if (wide)
+  const dim3 grid_b((a.NR + kRaysPerBlock - 1) / kRaysPerBlock), block_b(kRaysPerBlock * kWave);
+  if (info && wide)
+    hipLaunchKernelGGL((k_sample_depthguided_wide<Scene, SamplerInfo>), dim3(a.NR), dim3(kWideThreads), 0, stream, sd, a, *info);
+  else if (info)
+    hipLaunchKernelGGL(k_sample_depthguided_info<Scene>, grid_b, block_b, 0, stream, sd, a, *info);
+  else if (wide)
     hipLaunchKernelGGL(k_sample_depthguided_wide<Scene>, dim3(a.NR), dim3(kWideThreads), 0, stream, sd, a);
   else
     hipLaunchKernelGGL(k_sample_depthguided<Scene>, dim3((a.NR + kRaysPerBlock - 1) / kRaysPerBlock), dim3(kRaysPerBlock * kWave), 0,
@@ -575,10 +697,28 @@ static int launch_sampler(const DinerScene* scene, const SamplerArgs& a, bool wi
   DINER_LAUNCH_OK();
   return 0;
 }
-static int sample(const DinerScene* scene, const SamplerArgs& a, bool wide, const char* who, hipStream_t stream) {
+static int sample(const DinerScene* scene, const SamplerArgs& a, bool wide, const char* who, hipStream_t stream,
+                  const SamplerInfo* info = nullptr) {
   DINER_CHECK_ARG(scene->nv >= 1 && scene->nv <= kMaxViewsWide, "scene: nv=%d outside [1,%d]", scene->nv, kMaxViewsWide);
-  return scene->nv <= kMaxViews ? launch_sampler<SceneDev>(scene, a, wide, who, stream)
-                                : launch_sampler<SceneDevWide>(scene, a, wide, who, stream);
+  return scene->nv <= kMaxViews ? launch_sampler<SceneDev>(scene, a, wide, who, stream, info)
+                                : launch_sampler<SceneDevWide>(scene, a, wide, who, stream, info);
+}
+
+// the checks of diner_sample_depthguided_f32 / _long_f32 (max_cand, max_k: the entry's limits) for the info entries, then the launch
+static int sample_info(const char* who, int max_cand, int max_k, const DinerScene* scene, const float* rays, int NR, int n_cand, int K,
+                       int G, float depth_diff_max, const float* t_base, const float* noise_coarse, const float* noise_gauss,
+                       const float* noise_fill, uint64_t seed, long long ray_index0, float* z_out, const SamplerInfo& info,
+                       void* stream) {
+  DINER_CHECK_ARG(scene && rays && t_base && z_out, "%s: null pointer argument", who);
+  DINER_CHECK_ARG(NR > 0, "%s: NR must be positive (got %d)", who, NR);
+  DINER_CHECK_ARG(n_cand > 0 && n_cand <= max_cand, "%s: n_cand=%d outside [1,%d]", who, n_cand, max_cand);
+  DINER_CHECK_ARG(K > 0 && K <= max_k, "%s: n_samples K=%d outside [1,%d]", who, K, max_k);
+  DINER_CHECK_ARG(G >= 0 && G <= K, "%s: need 0 <= n_gaussian <= n_samples (got G=%d, K=%d)", who, G, K);
+  DINER_CHECK_ARG(ray_index0 >= 0 && ray_index0 + NR <= (1ll << 32),
+                  "%s: ray_index0 = %lld outside [0, 2^32 - NR] (the noise key of a ray is a 32-bit index)", who, ray_index0);
+  SamplerArgs a{rays, t_base, noise_coarse, noise_gauss, noise_fill, z_out, nullptr, seed, (uint32_t)ray_index0, NR, n_cand, K,
+                G, depth_diff_max};
+  return sample(scene, a, !(K <= kMaxK && n_cand <= kMaxCand), who, (hipStream_t)stream, &info);
 }
 }  // namespace diner
 
@@ -636,6 +776,26 @@ extern "C" int diner_sample_depthguided_long_f32(const DinerScene* scene, const 
   SamplerArgs a{rays, t_base, noise_coarse, noise_gauss, noise_fill, z_out, z_unfilled, seed, (uint32_t)ray_index0, NR, n_cand, K,
                 G, depth_diff_max};
   return sample(scene, a, true, "sample_depthguided_long", (hipStream_t)stream);
+}
+
+extern "C" int diner_sample_depthguided_info_f32(const DinerScene* scene, const float* rays, int NR, int n_cand, int K, int G,
+                                                 float depth_diff_max, const float* t_base, const float* noise_coarse,
+                                                 const float* noise_gauss, const float* noise_fill, uint64_t seed,
+                                                 long long ray_index0, float* z_out, float* z_ordered, float* slot_L,
+                                                 int32_t* slot_idx, float* stats, void* stream) {
+  return sample_info("sample_depthguided_info", kMaxCand, kMaxK, scene, rays, NR, n_cand, K, G, depth_diff_max, t_base, noise_coarse,
+                     noise_gauss, noise_fill, seed, ray_index0, z_out, SamplerInfo{z_ordered, slot_L, slot_idx, stats}, stream);
+}
+
+// the bounded info kernel where it fits, as the plain long entry picks the bounded kernel
+extern "C" int diner_sample_depthguided_info_long_f32(const DinerScene* scene, const float* rays, int NR, int n_cand, int K, int G,
+                                                      float depth_diff_max, const float* t_base, const float* noise_coarse,
+                                                      const float* noise_gauss, const float* noise_fill, uint64_t seed,
+                                                      long long ray_index0, float* z_out, float* z_ordered, float* slot_L,
+                                                      int32_t* slot_idx, float* stats, void* stream) {
+  return sample_info("sample_depthguided_info_long", kWideMaxCand, kLongMaxK, scene, rays, NR, n_cand, K, G, depth_diff_max, t_base,
+                     noise_coarse, noise_gauss, noise_fill, seed, ray_index0, z_out, SamplerInfo{z_ordered, slot_L, slot_idx, stats},
+                     stream);
 }
 
 extern "C" int diner_fill_uniform_long_f32(const float* z_in, const float* rays, int NR, int K, const float* noise_fill,

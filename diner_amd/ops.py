@@ -4,6 +4,7 @@ PyTorch is plumbing here: it owns device memory (caching allocator), the stream 
 process group.  Every function takes/returns torch tensors on a HIP device and enqueues kernels on the
 current stream.  There is no CPU path and no eager-torch fallback: CPU tensors raise.
 """
+import collections
 import ctypes as C
 import os
 import threading
@@ -390,34 +391,53 @@ def field_generic(scene: HipScene, mlp: GenericMlp, rays=None, z=None, xyz=None,
 
 
 # ---------------------------------------------------------------------------------------------------------
+SamplerInfo = collections.namedtuple("SamplerInfo", "z_ordered slot_L slot_idx sum_L sum_O prior_depth prior_std")
+
+
 def sample_depthguided(scene: HipScene, rays, n_samples, n_candidates, n_gaussian, depth_diff_max=0.05,
-                       noise=None, seed=0, want_unfilled=False, ray_index0=0):
+                       noise=None, seed=0, want_unfilled=False, ray_index0=0, want_info=False):
     """rays (NR,8) -> ascending z (NR,K) [, unfilled z with zeros].  noise = (coarse, gauss, fill) or None
     (in-kernel Philox keyed by (`seed`, ray_index0 + i): pass the index of rays[0] in the frame's ray list and one seed per
     frame, and the frame does not depend on how its rays are batched or sharded).  The bounded entry: K <= 256,
-    n_candidates <= 1024 (sample_depthguided_long: K <= 1024, n_candidates <= 4096)."""
-    return _sample_depthguided(lib.diner_sample_depthguided_f32, scene, rays, n_samples, n_candidates, n_gaussian,
-                               depth_diff_max, noise, seed, want_unfilled, ray_index0)
+    n_candidates <= 1024 (sample_depthguided_long: K <= 1024, n_candidates <= 4096).
+    want_unfilled: slot order within a ray unspecified.  want_info (instead): -> (z, SamplerInfo) through the info entry -- the same z
+    bit for bit; z_ordered (NR,K) the unfilled z in the reference's slot order (picks by descending likelihood, then the gaussian
+    samples), slot_L / slot_idx (NR,K-G) likelihood and candidate index of each pick slot (0 / -1: empty), and per ray sum_L, sum_O
+    (the depth maps' probability that the ray meets a surface), prior_depth, prior_std (mean and sigma of the gaussian fit; 0 where
+    sum_O is 0)."""
+    return _sample_depthguided(lib.diner_sample_depthguided_info_f32 if want_info else lib.diner_sample_depthguided_f32, scene, rays,
+                               n_samples, n_candidates, n_gaussian, depth_diff_max, noise, seed, want_unfilled, ray_index0, want_info)
 
 
 def sample_depthguided_long(scene: HipScene, rays, n_samples, n_candidates, n_gaussian, depth_diff_max=0.05,
-                            noise=None, seed=0, want_unfilled=False, ray_index0=0):
+                            noise=None, seed=0, want_unfilled=False, ray_index0=0, want_info=False):
     """sample_depthguided for K <= 1024 samples and n_candidates <= 4096 (the reference's --nsamples): the same kernel as
     sample_depthguided where it fits (K <= 256, n_candidates <= 1024, bit-identical results), one workgroup per ray above."""
-    return _sample_depthguided(lib.diner_sample_depthguided_long_f32, scene, rays, n_samples, n_candidates, n_gaussian,
-                               depth_diff_max, noise, seed, want_unfilled, ray_index0)
+    return _sample_depthguided(lib.diner_sample_depthguided_info_long_f32 if want_info else lib.diner_sample_depthguided_long_f32, scene,
+                               rays, n_samples, n_candidates, n_gaussian, depth_diff_max, noise, seed, want_unfilled, ray_index0, want_info)
 
 
 def _sample_depthguided(entry, scene, rays, n_samples, n_candidates, n_gaussian, depth_diff_max, noise, seed, want_unfilled,
-                        ray_index0):
+                        ray_index0, want_info=False):
     _require_hip(rays)
     rays = _f32c(rays)
     NR = rays.shape[0]
     K, G = int(n_samples), int(n_gaussian)
     z = torch.empty(NR, K, device=rays.device, dtype=torch.float32)
     zu = torch.empty(NR, K, device=rays.device, dtype=torch.float32) if want_unfilled else None
+    if want_info:
+        if want_unfilled:
+            raise ValueError("diner_amd: want_info delivers z_ordered; want_unfilled belongs to the plain entry -- ask for one of them")
+        zo = torch.empty(NR, K, device=rays.device, dtype=torch.float32)
+        sl = torch.empty(NR, max(K - G, 0), device=rays.device, dtype=torch.float32)
+        si = torch.empty(NR, max(K - G, 0), device=rays.device, dtype=torch.int32)
+        st = torch.empty(NR, 4, device=rays.device, dtype=torch.float32)
+        info = SamplerInfo(zo, sl, si, st[:, 0], st[:, 1], st[:, 2], st[:, 3])
+        outs = (_ptr(z), _ptr(zo), _ptr(sl) if K > G else None, _ptr(si) if K > G else None, _ptr(st))
+    else:
+        outs = (_ptr(z), _ptr(zu))
     if NR == 0:                     # nothing to do (the C ABI rejects empty launches)
-        return (z, zu) if want_unfilled else z
+        return (z, info) if want_info else (z, zu) if want_unfilled else z
     nc = ng = nf = None
     if noise is not None:
         nc, ng, nf = (_f32c(t) if t is not None else None for t in noise)
@@ -429,8 +449,8 @@ def _sample_depthguided(entry, scene, rays, n_samples, n_candidates, n_gaussian,
         _lib.check(entry(
             scene.ref, _ptr(rays), NR, int(n_candidates), K, G, float(depth_diff_max),
             _ptr(_t_base(int(n_candidates), rays.device)), _ptr(nc), _ptr(ng), _ptr(nf),
-            C.c_uint64(int(seed) & (2 ** 64 - 1)), int(ray_index0), _ptr(z), _ptr(zu), _stream()))
-    return (z, zu) if want_unfilled else z
+            C.c_uint64(int(seed) & (2 ** 64 - 1)), int(ray_index0), *outs, _stream()))
+    return (z, info) if want_info else (z, zu) if want_unfilled else z
 
 
 def fill_uniform(z_in, rays, noise_fill=None, seed=0, ray_index0=0):

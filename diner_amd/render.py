@@ -59,6 +59,37 @@ def gather_tiles(local, n_total, rank, world, group=None, force=False):
 
 
 @torch.no_grad()
+def predict_surface_prior(nerf, target_extrinsics, target_intrinsics, W, H, znear, zfar, n_samples=40, n_candidates=1000,
+                          n_gaussian=15, depth_diff_max=0.05, ray_batch_size=8192, seed=None):
+    """The depth-guided sampler's view of the (SB) target views: what the source depth maps alone say about every target pixel, without
+    the MLP.  -> hit (SB,1,H,W), the depth maps' probability 1 - prod(1 - L) that the pixel's ray meets a surface; depth (SB,1,H,W) and
+    depth_std (SB,1,H,W), mean and sigma of the likelihood-weighted gaussian the sampler draws its n_gaussian samples from (both 0 where
+    hit is 0).  Needs the depth, std and normal maps of the scene last passed to nerf.encode() only; the latent and the MLP handle are
+    not touched.  Rays, batches and the frame's noise key as in predict_image (one process): the maps do not depend on ray_batch_size,
+    and on the noise only through the candidate jitter (1 / n_candidates of the depth range).  `seed` None: drawn from torch's global
+    CPU generator.  Noise injected with diner_amd.noise.inject is sliced per batch as in predict_image."""
+    from diner_amd import ops
+    SB = target_extrinsics.shape[0]
+    dev = nerf.encoder.depths.device
+    rays = ops.gen_rays(target_extrinsics, target_intrinsics, W, H, znear, zfar, dev)
+    if seed is None:
+        seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+    inj = _noise.current()
+    out = torch.empty(SB, H * W, 3, device=dev, dtype=torch.float32)
+    for sb in range(SB):
+        scene = nerf.hip_scene(sb)
+        for r0 in range(0, H * W, ray_batch_size):
+            r1 = min(H * W, r0 + ray_batch_size)
+            nz = None if inj is None else tuple(None if t is None else t[sb, r0:r1] for t in inj)
+            # the key renderer.forward uses for object sb under noise.keyed(seed, r0)
+            info = ops.sample_depthguided_long(scene, rays[sb, r0:r1].contiguous(), n_samples, n_candidates, n_gaussian, depth_diff_max,
+                                               noise=nz, seed=seed + 0x9E3779B97F4A7C15 * sb, ray_index0=r0, want_info=True)[1]
+            out[sb, r0:r1] = torch.stack((info.sum_O, info.prior_depth, info.prior_std), dim=-1)
+    out = out.view(SB, H, W, 3).permute(0, 3, 1, 2)
+    return out[:, 0:1].contiguous(), out[:, 1:2].contiguous(), out[:, 2:3].contiguous()
+
+
+@torch.no_grad()
 def predict_image(nerf, renderer, target_extrinsics, target_intrinsics, W, H, znear, zfar, ray_batch_size=8192,
                   rank=0, world=1, group=None, seed=None, return_alpha=False):
     """Render the (SB) target views described by target_extrinsics (SB,4,4) / target_intrinsics (SB,3,3) of the

@@ -162,6 +162,30 @@ int diner_sample_depthguided_long_f32(const DinerScene* scene, const float* rays
                                       uint64_t seed, long long ray_index0, float* z_out, float* z_unfilled, void* stream);
 int diner_fill_uniform_long_f32(const float* z_in, const float* rays, int NR, int K, const float* noise_fill,
                                 uint64_t seed, long long ray_index0, float* z_out, void* stream);
+
+/* The sampler with what it knows about the ray beside the samples: the arguments, checks, error codes, limits and z_out (bit for
+ * bit, explicit or Philox noise) of diner_sample_depthguided_f32 / _long_f32, with z_unfilled replaced by four optional outputs,
+ * each written only where its pointer is not NULL:
+ *   z_ordered  (NR, K)      the sampler output before the fill in the reference's slot order (nerf_renderer.py:172-190): the
+ *                           K - G picks by descending surface likelihood -- equal likelihood bits: lower candidate index first,
+ *                           the rule of the ties at the cut-off --, empty pick slots (z = 0) after them, then the G gaussian samples
+ *   slot_L     (NR, K - G)  likelihood of the pick in each slot (0 = empty)
+ *   slot_idx   (NR, K - G)  int32: index of its candidate among the ray's n_cand (-1 = empty)
+ *   stats      (NR, 4)      sum of the candidates' likelihoods L, sum of O = L_i * prod_{j<i}(1 - L_j) -- the depth maps' probability
+ *                           1 - prod(1 - L) that the ray meets a surface --, and the O-weighted mean and standard deviation of the
+ *                           candidate depths (the gaussian the G samples are drawn from, :183); all 0 where the ray sees no surface
+ * K - G = 0 is legal: slot_L / slot_idx are not touched.  The long entry runs the bounded info kernel where it fits
+ * (K <= 256 and n_cand <= 1024): results there equal the bounded entry's bit for bit. */
+int diner_sample_depthguided_info_f32(const DinerScene* scene, const float* rays, int NR, int n_cand, int K, int G,
+                                      float depth_diff_max, const float* t_base,
+                                      const float* noise_coarse, const float* noise_gauss, const float* noise_fill,
+                                      uint64_t seed, long long ray_index0, float* z_out,
+                                      float* z_ordered, float* slot_L, int32_t* slot_idx, float* stats, void* stream);
+int diner_sample_depthguided_info_long_f32(const DinerScene* scene, const float* rays, int NR, int n_cand, int K, int G,
+                                           float depth_diff_max, const float* t_base,
+                                           const float* noise_coarse, const float* noise_gauss, const float* noise_fill,
+                                           uint64_t seed, long long ray_index0, float* z_out,
+                                           float* z_ordered, float* slot_L, int32_t* slot_idx, float* stats, void* stream);
 int diner_composite_long_f32(const float* field, const float* z, const float* rays, int NR, int K, int white_bkgd,
                              float* rgb_out, float* depth_out, float* weights_out, void* stream);
 

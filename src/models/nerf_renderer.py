@@ -86,23 +86,28 @@ class NeRFRendererDGS(torch.nn.Module):
         return (near * (1 - t) + far * t).view(*shp[:-1], n_coarse)
 
     @torch.no_grad()
-    def sample_depthguided(self, rays, model, n_samples, n_candidates, depth_diff_max=0.05, n_gaussian=None):
-        """rays (SB,NR,8) -> z (SB,NR,n_samples): the top (n_samples - n_gaussian) candidates by surface likelihood,
-        n_gaussian samples of the likelihood-weighted gaussian, zeros marking empty slots (:65-190).  Slot order
-        within a ray is unspecified (the reference's is by descending likelihood); fill_up_uniform_samples sorts."""
+    def sample_depthguided(self, rays, model, n_samples, n_candidates, depth_diff_max=0.05, n_gaussian=None, return_info=False):
+        """rays (SB,NR,8) -> z (SB,NR,n_samples) in the reference's slot order (:172-190): the top (n_samples - n_gaussian)
+        candidates by descending surface likelihood (equal likelihoods: lower candidate index first), zeros marking empty slots,
+        then n_gaussian samples of the likelihood-weighted gaussian (zeros where the ray sees no surface).
+        return_info (not in the reference, which computes these and drops them): -> (z, DotMap(slot_L, slot_idx (SB,NR,K-G): likelihood
+        and candidate index of each pick slot; sum_L, sum_O, prior_depth, prior_std (SB,NR): the ray's summed likelihood, the depth
+        maps' probability that it meets a surface, mean and sigma of the gaussian fit)), see ops.sample_depthguided."""
         self._check_model(model)
         n_gaussian = n_gaussian if n_gaussian is not None else self.n_gaussian
         assert n_samples >= n_gaussian
         SB = rays.shape[0]
         inj = _noise.current()
-        out = []
+        infos = []
         for sb in range(SB):
             nz = None if inj is None else tuple(None if t is None else t[sb] for t in inj)
             seed, r0 = _key(sb)
-            _, zu = ops.sample_depthguided_long(model.hip_scene(sb), rays[sb], n_samples, n_candidates, n_gaussian,
-                                                depth_diff_max, noise=nz, seed=seed, want_unfilled=True, ray_index0=r0)
-            out.append(zu)
-        return torch.stack(out)
+            infos.append(ops.sample_depthguided_long(model.hip_scene(sb), rays[sb], n_samples, n_candidates, n_gaussian,
+                                                     depth_diff_max, noise=nz, seed=seed, ray_index0=r0, want_info=True)[1])
+        z = torch.stack([i.z_ordered for i in infos])
+        if not return_info:
+            return z
+        return z, DotMap(**{f: torch.stack([getattr(i, f) for i in infos]) for f in ops.SamplerInfo._fields[1:]})
 
     def fill_up_uniform_samples(self, z_samples, rays):
         """zeros in z (SB,NR,K) -> stratified samples of [near, far]; returns ascending z (:367-397)."""
