@@ -45,12 +45,13 @@ def _hip_device(device):
 
 
 @torch.no_grad()
-def write_prediction_folder(nerf, renderer, batches, outdir, znear, zfar, ray_batch_size=8192, write_alpha=False):
+def write_prediction_folder(nerf, renderer, batches, outdir, znear, zfar, ray_batch_size=8192, write_alpha=False, cull_empty=False):
     """Render every target view of `batches` (collated sample dicts of diner_amd.datasets) with `nerf` / `renderer` and write
     <sample_name>{-pred,-depth,-ref,-gt}.png into `outdir`: the render and its colour-mapped depth, the source views side by side and
     the target, each quantised as save_image does.  Returns {"sample_name": [...], "l1", "l2", "psnr", "ssim": float64 (N,)} -- the
     scores of the renders against their targets, computed on the device from the fp32 tensors (not from the files).  write_alpha: also
-    <sample_name>-alpha.png, the render's opacity (the matte) as an 8-bit grey image, quantised like the others."""
+    <sample_name>-alpha.png, the render's opacity (the matte) as an 8-bit grey image, quantised like the others.
+    cull_empty: passed to predict_image (render only the rays the depth maps put a surface on; an approximation, off by default)."""
     from .datasets import encode_args
     from .imageio import depth_to_uint8, gray_to_uint8, to_uint8
     from .metrics import KEYS, image_metrics
@@ -63,7 +64,7 @@ def write_prediction_folder(nerf, renderer, batches, outdir, znear, zfar, ray_ba
         gt = batch["target_rgb"].to(dev)
         H, W = gt.shape[-2:]
         rgb, depth, *alpha = predict_image(nerf, renderer, batch["target_extrinsics"].to(dev), batch["target_intrinsics"].to(dev), W, H,
-                                           znear, zfar, ray_batch_size=ray_batch_size, return_alpha=write_alpha)
+                                           znear, zfar, ray_batch_size=ray_batch_size, return_alpha=write_alpha, cull_empty=cull_empty)
         src = batch["src_rgbs"].to(dev)
         for i, stem in enumerate(batch["sample_name"]):
             write_png(os.path.join(outdir, stem + PRED_SUFFIX), to_uint8(rgb[i]))

@@ -569,6 +569,82 @@ def render(scene: HipScene, mlp: HipMlp, rays, z, white_bkgd, want_weights=False
     return composite(field, z, rays, white_bkgd, want_weights, want_aux)
 
 
+def sampler_stats(info):
+    """The (NR,4) tensor [sum_L, sum_O, prior_depth, prior_std] a SamplerInfo's four per-ray fields are columns of."""
+    st = info.sum_O._base
+    if st is not None and st.dim() == 2 and st.shape[1] == 4 and st.is_contiguous() and st.data_ptr() == info.sum_L.data_ptr():
+        return st
+    return torch.stack((info.sum_L, info.sum_O, info.prior_depth, info.prior_std), dim=-1).contiguous()
+
+
+def compact_live(stats, threshold, rays, z, ray_index0, rays_out, z_out, live_idx, n_live):
+    """Empty-ray culling, first half (diner_compact_live_f32): append the LIVE rays of one sampler batch, in ray order, to a frame-level
+    list.  stats (NR,4) as the info sampler writes it (sampler_stats(info)) or a SamplerInfo; ray i is live iff
+    not (sum_O[i] <= threshold) -- a NaN is live.  rays (NR,8), z (NR,K); rays_out (capacity,8), z_out (capacity,K), live_idx (capacity)
+    int32 and the device counter n_live (1) int32 are the caller's frame-level buffers: rows n_live .. n_live + live - 1 are written
+    (live_idx: ray_index0 + i), rows at or beyond the capacity are not, and n_live advances by the true live count.
+    -> (slot (NR) int32: the row each ray went to, -1 for a dead ray and for one beyond the capacity; n_live, the same device tensor,
+    NOT read here).  Enqueue-only; the result is a function of the inputs alone (integer arithmetic, no atomics)."""
+    if isinstance(stats, SamplerInfo):
+        stats = sampler_stats(stats)
+    _require_hip(stats, rays, z, rays_out, z_out)
+    stats, rays, z = _f32c(stats), _f32c(rays), _f32c(z)
+    NR, K = z.shape
+    cap = int(rays_out.shape[0])
+    if tuple(stats.shape) != (NR, 4) or tuple(rays.shape) != (NR, 8):
+        raise ValueError(f"diner_amd: compact_live expects stats (NR,4), rays (NR,8), z (NR,K), got {tuple(stats.shape)}, {tuple(rays.shape)}, "
+                         f"{tuple(z.shape)}")
+    if tuple(rays_out.shape) != (cap, 8) or tuple(z_out.shape) != (cap, K) or tuple(live_idx.shape) != (cap,) or n_live.numel() != 1:
+        raise ValueError(f"diner_amd: compact_live expects rays_out (capacity,8), z_out (capacity,{K}), live_idx (capacity), n_live (1), got "
+                         f"{tuple(rays_out.shape)}, {tuple(z_out.shape)}, {tuple(live_idx.shape)}, {tuple(n_live.shape)}")
+    for t in (live_idx, n_live):
+        if not t.is_cuda or t.dtype != torch.int32:
+            raise TypeError("diner_amd: compact_live expects int32 live_idx and n_live on the HIP device")
+    for t in (rays_out, z_out, live_idx, n_live):
+        if not t.is_contiguous():
+            raise ValueError("diner_amd: compact_live writes into contiguous buffers")
+    slot = torch.empty(NR, device=z.device, dtype=torch.int32)
+    if NR == 0:
+        return slot, n_live
+    with torch.cuda.device(z.device):
+        ws = _workspace(lib.diner_compact_live_workspace_bytes(NR), z.device)
+        _lib.check(lib.diner_compact_live_f32(_ptr(stats), float(threshold), _ptr(rays), _ptr(z), NR, K, int(ray_index0), cap,
+                                              _ptr(rays_out), _ptr(z_out), _ptr(live_idx), _ptr(slot), _ptr(n_live), _ptr(ws), _stream()))
+    return slot, n_live
+
+
+def expand_live(tiles, slot, bg, n_tiles=None):
+    """Empty-ray culling, second half (diner_expand_live_f32): tiles (n,C) of the live rays, slot (N) int32 as compact_live wrote it,
+    bg (C) -> out (N,C) with out[i] = tiles[slot[i]] where 0 <= slot[i] < n_tiles (default: n), else bg.  1 <= C <= 8."""
+    _require_hip(tiles, bg)
+    tiles, bg = _f32c(tiles), _f32c(bg)
+    if not slot.is_cuda or slot.dtype != torch.int32:
+        raise TypeError("diner_amd: expand_live expects an int32 slot tensor on the HIP device")
+    slot = slot.contiguous()
+    N, C_ = int(slot.shape[0]), int(bg.shape[0])
+    n = int(tiles.shape[0]) if n_tiles is None else int(n_tiles)
+    if tiles.dim() != 2 or tiles.shape[1] != C_ or slot.dim() != 1 or not 0 <= n <= tiles.shape[0]:
+        raise ValueError(f"diner_amd: expand_live expects tiles (n,C), slot (N), bg (C), got {tuple(tiles.shape)}, {tuple(slot.shape)}, "
+                         f"{tuple(bg.shape)} with n_tiles {n}")
+    out = torch.empty(N, C_, device=slot.device, dtype=torch.float32)
+    if N == 0:
+        return out
+    with torch.cuda.device(slot.device):
+        _lib.check(lib.diner_expand_live_f32(_ptr(tiles) if n > 0 else None, n, _ptr(slot), _ptr(bg), N, C_, _ptr(out), _stream()))
+    return out
+
+
+def background_row(white_bkgd, n_aux, device):
+    """What the compositor returns for a ray of zero density (nerf_renderer.py:349-360 at sigma = 0): rgb 1 with white_bkgd else 0,
+    depth 0, then n_aux zeros (alpha, depth_var).  A cached device tensor (uploaded once per configuration)."""
+    key = ("bg_row", bool(white_bkgd), int(n_aux), str(device))
+    with _const_lock:
+        if key not in _const_cache:
+            c = 1.0 if white_bkgd else 0.0
+            _const_cache[key] = torch.tensor([c, c, c, 0.0] + [0.0] * int(n_aux), dtype=torch.float32).to(device)
+        return _const_cache[key]
+
+
 def posenc(x, num_freqs, freq_factor, include_input=True):
     _require_hip(x)
     shp = x.shape

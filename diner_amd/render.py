@@ -89,9 +89,88 @@ def predict_surface_prior(nerf, target_extrinsics, target_intrinsics, W, H, znea
     return out[:, 0:1].contiguous(), out[:, 1:2].contiguous(), out[:, 2:3].contiguous()
 
 
+CULL_BUFFER_BYTES = 1 << 30      # bound of the frame-level live-ray buffers of render_live_rays; a larger frame goes in chunks of rays
+
+
+@torch.no_grad()
+def render_live_rays(scene, mlp, rays, sample, n_samples, white_bkgd, n_aux=0, cull_below=0.0, ray_batch_size=8192,
+                     rank=0, world=1, group=None):
+    """Empty-ray culling for one object: render only the rays the source depth maps put a surface on.  rays (N,8): a frame's (or a
+    call's) ray list; sample(r0, r1) -> (z (r1-r0, K), SamplerInfo) of rays[r0:r1] (ops.sample_depthguided_long(want_info=True) under
+    the caller's noise key); K = n_samples.  -> (N, 4 + n_aux) rows [rgb, depth (, alpha (, depth_var))] on rank 0, None elsewhere.
+
+    A ray is LIVE iff not (sum_O <= cull_below): sum_O is the depth maps' probability that the ray meets a surface, the reference's
+    ray_mask (nerf_renderer.py:182) at cull_below = 0; a NaN is live.  Live rays are compacted in frame order (ops.compact_live), the
+    live list is rendered by ops.render in batches of ray_batch_size -- a live ray's values are those of the plain frame, since a ray's
+    result does not depend on the launch it is in -- and ops.expand_live puts them back.  A dead ray gets the compositor's values at
+    zero density (ops.background_row) WITHOUT running the MLP.  That is an approximation of the reference, which evaluates the MLP on K
+    stratified samples of such a ray too: wherever the network returns density away from every surface the depth maps know, the plain
+    frame shows it and the culled frame does not.
+
+    One host synchronisation (the 4-byte live count) per chunk: the whole list when the live buffers fit CULL_BUFFER_BYTES, else
+    chunks of rays that do.  A chunk without a live ray launches no field kernel.  With world > 1 every rank compacts the whole list
+    (the sampler is well under 1 % of a frame), renders shard_range(n_live, rank, world) of the live list and gather_tiles brings the
+    live tiles to rank 0: the load is balanced over live rays, not over pixels."""
+    from diner_amd import ops
+    N, K, C = int(rays.shape[0]), int(n_samples), 4 + int(n_aux)
+    dev = rays.device
+    bg = ops.background_row(white_bkgd, n_aux, dev)
+    out = torch.empty(N, C, device=dev, dtype=torch.float32) if rank == 0 else None
+    chunk = max(1, min(N, CULL_BUFFER_BYTES // (4 * K + 40)))
+    for c0 in range(0, N, chunk):
+        c1 = min(N, c0 + chunk)
+        rays_live = torch.empty(c1 - c0, 8, device=dev, dtype=torch.float32)
+        z_live = torch.empty(c1 - c0, K, device=dev, dtype=torch.float32)
+        live_idx = torch.empty(c1 - c0, device=dev, dtype=torch.int32)
+        n_live_dev = torch.zeros(1, device=dev, dtype=torch.int32)
+        slots = []
+        for r0 in range(c0, c1, ray_batch_size):
+            r1 = min(c1, r0 + ray_batch_size)
+            z, info = sample(r0, r1)
+            slots.append(ops.compact_live(info, cull_below, rays[r0:r1], z, r0, rays_live, z_live, live_idx, n_live_dev)[0])
+        n_live = int(n_live_dev.item())                       # the one read-back
+        lo, hi = shard_range(n_live, rank, world)
+        tiles = []
+        for a in range(lo, hi, ray_batch_size):
+            b = min(hi, a + ray_batch_size)
+            _, rgb, depth, *aux = ops.render(scene, mlp, rays_live[a:b], z_live[a:b], white_bkgd, want_aux=n_aux > 0)
+            tiles.append(torch.cat((rgb, depth.unsqueeze(-1)) + tuple(t.unsqueeze(-1) for t in aux[:n_aux]), dim=-1))
+        local = torch.cat(tiles, dim=0) if tiles else torch.zeros(0, C, device=dev)
+        full = gather_tiles(local, n_live, rank, world, group) if n_live > 0 else local
+        if rank == 0:
+            slot = torch.cat(slots) if len(slots) > 1 else slots[0]
+            out[c0:c1] = ops.expand_live(full, slot, bg, n_tiles=n_live)
+    return out
+
+
+def _predict_image_culled(nerf, renderer, rays, SB, n_rays, ray_batch_size, rank, world, group, seed, return_alpha, cull_below):
+    """predict_image(cull_empty=True) per object: -> (n_rays, SB * C) tiles in predict_image's layout on rank 0, None elsewhere."""
+    from diner_amd import ops
+    renderer._check_model(nerf)
+    K, n_cand, G = int(renderer.n_samples), int(renderer.n_depth_candidates), int(renderer.n_gaussian)
+    assert K >= G
+    mlp = nerf.hip_mlp()
+    inj = _noise.current()
+    per_object = []
+    for sb in range(SB):
+        scene = nerf.hip_scene(sb)
+
+        def sample(r0, r1, sb=sb, scene=scene):
+            nz = None if inj is None else tuple(None if t is None else t[sb, r0:r1] for t in inj)
+            # the key renderer.forward uses for object sb under noise.keyed(seed, r0)
+            return ops.sample_depthguided_long(scene, rays[sb, r0:r1], K, n_cand, G, 0.05, noise=nz,
+                                               seed=seed + 0x9E3779B97F4A7C15 * sb, ray_index0=r0, want_info=True)
+
+        per_object.append(render_live_rays(scene, mlp, rays[sb], sample, K, renderer.white_bkgd, n_aux=1 if return_alpha else 0,
+                                           cull_below=cull_below, ray_batch_size=ray_batch_size, rank=rank, world=world, group=group))
+    if rank != 0:
+        return None
+    return torch.stack(per_object, dim=1).reshape(n_rays, -1)
+
+
 @torch.no_grad()
 def predict_image(nerf, renderer, target_extrinsics, target_intrinsics, W, H, znear, zfar, ray_batch_size=8192,
-                  rank=0, world=1, group=None, seed=None, return_alpha=False):
+                  rank=0, world=1, group=None, seed=None, return_alpha=False, cull_empty=False, cull_below=0.0):
     """Render the (SB) target views described by target_extrinsics (SB,4,4) / target_intrinsics (SB,3,3) of the
     scene last passed to nerf.encode().  Returns rgb (SB,3,H,W), depth (SB,1,H,W) on rank 0 (None elsewhere); with return_alpha also
     the opacity map alpha (SB,1,H,W) (renderer.forward(want_alpha=True): one more channel in the gathered tiles, 20 B/ray).
@@ -99,12 +178,23 @@ def predict_image(nerf, renderer, target_extrinsics, target_intrinsics, W, H, zn
     diner_amd.noise.inject for the whole (SB, H*W, .) ray list is handed to every batch as the matching slice (parity
     tests); without injection the sampler draws in-kernel Philox noise keyed by (`seed`, position of the ray in the frame):
     the image does not depend on ray_batch_size or on the number of ranks.  `seed` None: drawn from torch's global CPU
-    generator on rank 0 and, with more than one rank, broadcast (8 bytes) so that all shards belong to the same frame."""
+    generator on rank 0 and, with more than one rank, broadcast (8 bytes) so that all shards belong to the same frame.
+
+    cull_empty (off by default; HIP devices only): render only the rays the source depth maps put a surface on -- see render_live_rays.
+    Per object the info sampler runs over the frame in ray batches (same noise key and injected-noise slices as the plain call), the
+    live rays (not (sum_O <= cull_below)) are compacted, the live list is rendered in batches of ray_batch_size and expanded into the
+    frame; every other pixel gets the compositor's values at zero density (rgb 1 with white_bkgd else 0, depth 0, alpha 0) without
+    running the MLP.  This approximates the reference, which evaluates the MLP on K stratified samples of such rays as well; at the
+    live pixels the frame is the plain frame bit for bit.  One host read-back (the live count) per object and frame.  With more than
+    one rank every rank samples and compacts the whole frame and renders its share of the LIVE list.  With cull_empty False the
+    function runs exactly the code it ran before the option existed."""
     SB = target_extrinsics.shape[0]
     dev = target_extrinsics.device
     znear = torch.as_tensor(znear, device=dev, dtype=torch.float32).expand(SB)
     zfar = torch.as_tensor(zfar, device=dev, dtype=torch.float32).expand(SB)
-    lo, hi = shard_range(H * W, rank, world)
+    if cull_empty and dev.type != "cuda":
+        raise RuntimeError("diner_amd: predict_image(cull_empty=True) runs on a HIP device; there is no CPU fallback")
+    lo, hi = (0, H * W) if cull_empty else shard_range(H * W, rank, world)     # culling: every rank compacts the whole frame
     if dev.type == "cuda":         # this rank's ray range only, generated on the device (diner_gen_rays_f32)
         from diner_amd import ops
         rays = ops.gen_rays(target_extrinsics, target_intrinsics, W, H, znear, zfar, dev, ray0=lo, n_rays=hi - lo)
@@ -120,19 +210,22 @@ def predict_image(nerf, renderer, target_extrinsics, target_intrinsics, W, H, zn
             t = torch.tensor([seed], dtype=torch.int64, device=dev if on_dev else "cpu")
             dist.broadcast(t, src=0, group=group)
             seed = int(t.item())
-    tiles = []
-    inj = _noise.current()
-    for r0 in range(lo, hi, ray_batch_size):
-        r1 = min(hi, r0 + ray_batch_size)
-        rb = rays[:, r0 - base:r1 - base].contiguous()
-        ctx = contextlib.nullcontext() if inj is None else _noise.inject(*(None if t is None else t[:, r0:r1] for t in inj))
-        with ctx, _noise.keyed(seed, r0):
-            out = renderer.forward(model=nerf, rays=rb, want_alpha=True) if return_alpha else renderer.forward(model=nerf, rays=rb)
-        parts = (out.fine.rgb, out.fine.depth.unsqueeze(-1)) + ((out.fine.alpha.unsqueeze(-1),) if return_alpha else ())
-        tiles.append(torch.cat(parts, dim=-1))                                              # (SB, b, C)
     C = 5 if return_alpha else 4
-    local = torch.cat(tiles, dim=1) if tiles else torch.zeros(SB, 0, C, device=dev)
-    full = gather_tiles(local.permute(1, 0, 2).reshape(hi - lo, SB * C), H * W, rank, world, group)
+    if cull_empty:
+        full = _predict_image_culled(nerf, renderer, rays, SB, H * W, ray_batch_size, rank, world, group, seed, return_alpha, cull_below)
+    else:
+        tiles = []
+        inj = _noise.current()
+        for r0 in range(lo, hi, ray_batch_size):
+            r1 = min(hi, r0 + ray_batch_size)
+            rb = rays[:, r0 - base:r1 - base].contiguous()
+            ctx = contextlib.nullcontext() if inj is None else _noise.inject(*(None if t is None else t[:, r0:r1] for t in inj))
+            with ctx, _noise.keyed(seed, r0):
+                out = renderer.forward(model=nerf, rays=rb, want_alpha=True) if return_alpha else renderer.forward(model=nerf, rays=rb)
+            parts = (out.fine.rgb, out.fine.depth.unsqueeze(-1)) + ((out.fine.alpha.unsqueeze(-1),) if return_alpha else ())
+            tiles.append(torch.cat(parts, dim=-1))                                              # (SB, b, C)
+        local = torch.cat(tiles, dim=1) if tiles else torch.zeros(SB, 0, C, device=dev)
+        full = gather_tiles(local.permute(1, 0, 2).reshape(hi - lo, SB * C), H * W, rank, world, group)
     if full is None:
         return (None, None, None) if return_alpha else (None, None)
     full = full.view(H, W, SB, C).permute(2, 3, 0, 1)                                       # (SB,C,H,W)

@@ -101,11 +101,12 @@ def read_apng_frames(path):
 
 @torch.no_grad()
 def create_cam_sweep(nerf, renderer, target_extrinsics, target_intrinsics, W, H, znear, zfar, outpath=None, fps=5,
-                     ray_batch_size=8192, frames_dir=None, rank=0, world=1, group=None):
+                     ray_batch_size=8192, frames_dir=None, rank=0, world=1, group=None, cull_empty=False):
     """Renders the sweep of the scene last passed to nerf.encode(): target_extrinsics (N,4,4), one intrinsics matrix (3,3).
 
     Returns the frame stack (2N-1, 3, 2H, W) float on rank 0 (colour image on top, viridis depth below, played forth and
-    back: frames[cat(arange(N), arange(N-1, 0, -1))], diner.py:204-208) and writes it as an animated PNG to `outpath`."""
+    back: frames[cat(arange(N), arange(N-1, 0, -1))], diner.py:204-208) and writes it as an animated PNG to `outpath`.
+    cull_empty: passed to predict_image (render only the rays the depth maps put a surface on; an approximation, off by default)."""
     from .render import predict_image
     from . import imageio
     N = target_extrinsics.shape[0]
@@ -114,7 +115,7 @@ def create_cam_sweep(nerf, renderer, target_extrinsics, target_intrinsics, W, H,
     rgbs, depth_u8 = [], []
     for i in range(N):
         rgb, depth = predict_image(nerf, renderer, target_extrinsics[i:i + 1], K, W, H, znear, zfar,
-                                   ray_batch_size=ray_batch_size, rank=rank, world=world, group=group)
+                                   ray_batch_size=ray_batch_size, rank=rank, world=world, group=group, cull_empty=cull_empty)
         if rank != 0:
             continue
         rgbs.append(rgb[0])                                                  # (3,H,W)

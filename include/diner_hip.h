@@ -543,6 +543,29 @@ int diner_objective_f32(const float* pred, const float* gt, const float* images,
                         int n_downsampling, double w_mse, double w_antibias, void* workspace, double* losses, float* d_pred,
                         void* stream);
 
+/* ---- empty-ray culling: render only the rays the depth maps put a surface on ----------------------------------------------------
+ * New symbols without an ABI bump; enqueue-only on `stream`, no allocation, no host synchronisation, no floating-point atomics, no
+ * workgroup waiting on another (three launches, ordered by the stream); bad arguments return DINER_E_INVALID before any device work.
+ *
+ * diner_compact_live_f32: order-preserving stream compaction of one sampler batch, appended to a frame-level list.  stats (NR,4) as
+ *   the info sampler entries write it ([1] = sum O, the reference's ray_mask of nerf_renderer.py:182 at threshold 0); ray i is LIVE iff
+ *   !(stats[i][1] <= threshold), so a NaN is live.  With base = *n_live on entry (a device int32 the caller zeroes once per frame), the
+ *   j-th live ray of the batch, in ray order, goes to row base + j: rays_out (capacity,8) and z_out (capacity,K) receive its rows of
+ *   rays (NR,8) / z (NR,K), live_idx (capacity) int32 its frame index ray_index0 + i.  slot (NR) int32 receives the row of every ray of
+ *   the batch, -1 for a dead ray and for a live one whose row is at or beyond `capacity` -- such rows are not written.  *n_live
+ *   advances by the batch's true live count whatever the capacity: a counter above `capacity` tells the caller the list overflowed.
+ *   The bytes written are a function of the inputs alone; a ray list split into consecutive calls gives those of the one call.
+ *   1 <= K <= 1024; rows move as 16-byte vectors when K is a multiple of 4 and the bases are 16-byte aligned, as scalars otherwise.
+ *   workspace: diner_compact_live_workspace_bytes(NR) bytes of device memory (0 for an NR the entry refuses).
+ * diner_expand_live_f32: out (N,C) = slot[i] in [0, n_tiles) ? tiles[slot[i]] : bg, with tiles (n_tiles,C), slot (N) int32, bg (C)
+ *   device; one coalesced pass, 1 <= C <= 8.  n_tiles == 0 (tiles may be NULL) fills the frame with bg. */
+size_t diner_compact_live_workspace_bytes(long long NR);
+int diner_compact_live_f32(const float* stats, float threshold, const float* rays, const float* z, int NR, int K, long long ray_index0,
+                           long long capacity, float* rays_out, float* z_out, int* live_idx, int* slot, int* n_live, void* workspace,
+                           void* stream);
+int diner_expand_live_f32(const float* tiles, long long n_tiles, const int* slot, const float* bg, long long N, int C, float* out,
+                          void* stream);
+
 /* ---- measurement aid (bench.py): per-kernel durations of the two field kernels ------------------
  * With profiling enabled every field call brackets k_field_pre / k_field_post with HIP events on the
  * launch stream; diner_profile_collect waits for them, returns the summed durations (ms), the number

@@ -32,6 +32,15 @@ def _key(sb=0):
 
 
 class NeRFRendererDGS(torch.nn.Module):
+    # Empty-ray culling (not in the reference; off by default).  Plain attributes read at call time, like white_bkgd.  With cull_empty
+    # a no-grad forward renders only the rays whose sum_O -- the depth maps' probability that the ray meets a surface, the reference's
+    # ray_mask of :182 -- is not <= cull_below; every other ray gets the compositor's values at zero density (rgb 1 with white_bkgd else
+    # 0, depth 0, alpha 0, depth_var 0) WITHOUT running the MLP, where the reference evaluates it on K stratified samples: an
+    # approximation (diner_amd.render.render_live_rays).  One host read-back per call and object.  Ignored in grad mode (training renders
+    # every ray) and with want_weights (the per-sample weights are not culled).
+    cull_empty = False
+    cull_below = 0.0
+
     def __init__(self, n_samples=40, n_depth_candidates=1000, n_gaussian=15, eval_batch_size=100000, white_bkgd=True):
         super().__init__()
         self.n_samples = n_samples
@@ -161,10 +170,19 @@ class NeRFRendererDGS(torch.nn.Module):
                 out.alpha = aux[0]
             return DotMap(fine=out)
         alphas, dvars = [], []
+        cull = bool(self.cull_empty) and not want_weights and rays.shape[1] > 0
         for sb in range(SB):
             scene = model.hip_scene(sb)
             nz = None if inj is None else tuple(None if t is None else t[sb] for t in inj)
             seed, r0 = _key(sb)
+            if cull:
+                t = self._forward_culled(scene, mlp, rays[sb], nz, seed, r0, want_alpha)
+                rgbs.append(t[:, :3].contiguous())
+                depths.append(t[:, 3].contiguous())
+                if want_alpha:
+                    alphas.append(t[:, 4].contiguous())
+                    dvars.append(t[:, 5].contiguous())
+                continue
             z = ops.sample_depthguided_long(scene, rays[sb], self.n_samples, self.n_depth_candidates, self.n_gaussian,
                                             0.05, noise=nz, seed=seed, ray_index0=r0)
             w, rgb, depth, *aux = ops.render(scene, mlp, rays[sb], z, self.white_bkgd, want_weights=want_weights, want_aux=want_alpha)
@@ -179,6 +197,19 @@ class NeRFRendererDGS(torch.nn.Module):
         if want_alpha:
             out.alpha, out.depth_var = torch.stack(alphas), torch.stack(dvars)
         return DotMap(fine=out)
+
+    def _forward_culled(self, scene, mlp, rays, nz, seed, r0, want_alpha):
+        """One object of a no-grad forward with cull_empty: (B,8) -> (B, 4 or 6) rows [rgb, depth (, alpha, depth_var)]."""
+        from diner_amd.render import render_live_rays
+        rays = ops._f32c(rays)
+
+        def sample(a, b):
+            part = None if nz is None else tuple(None if t is None else t[a:b] for t in nz)
+            return ops.sample_depthguided_long(scene, rays[a:b], self.n_samples, self.n_depth_candidates, self.n_gaussian, 0.05,
+                                               noise=part, seed=seed, ray_index0=r0 + a, want_info=True)
+
+        return render_live_rays(scene, mlp, rays, sample, self.n_samples, self.white_bkgd, n_aux=2 if want_alpha else 0,
+                                cull_below=float(self.cull_below), ray_batch_size=rays.shape[0])
 
     def _format_outputs(self, weights, rgb, depth, want_weights):
         out = DotMap(rgb=rgb, depth=depth)
