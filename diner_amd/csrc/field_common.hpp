@@ -19,13 +19,8 @@ constexpr int kPreStages = 4 + 3 * 2 * kStagesPerLayer;    // lin_in + 3 x (fc_0
 constexpr int kPostStages = 2 * 2 * kStagesPerLayer + 1;   // 2 x (fc_0, fc_1) + lin_out      = 129
 constexpr int kPtsPerWave = 16;
 
-// Timing-experiment switches (tools/ablate.sh): DINER_ABL_NO_DMA / _NO_BARRIER / _NO_LDS remove one ingredient of the
-// stage loop to price it.  Results are WRONG when any is set; the shipped library is built with none.
 template <int J>
 __device__ __forceinline__ void stage_dma_piece(const float* __restrict__ gsrc, float* lds_dst, int wave, int lane) {
-#ifdef DINER_ABL_NO_DMA
-  return;
-#endif
   constexpr int h = J >> 2, o = (J & 3) * 1024;
   const __attribute__((address_space(1))) void* g =
       (const __attribute__((address_space(1))) void*)(gsrc + wave * 2048 + lane * 4 + h * 1024);
@@ -66,10 +61,8 @@ struct WeightStream {
   // Begin consuming the stage in `slot`: one barrier per stage publishes it (every wave has waited for its own DMA
   // pieces) and retires the previous stage, whose slot then receives the DMA of the next one.
   __device__ __forceinline__ const f32x4* begin() {
-#ifndef DINER_ABL_NO_BARRIER
     __builtin_amdgcn_s_waitcnt(0x0f70);       // vmcnt(0): everything outstanding is at least half a stage old
     __syncthreads();
-#endif
     dma_src = base + (size_t)issue * kStageFloats;
     dma_dst = lds + (slot ^ 1) * kStageFloats;
     issue = (issue + 1 == n_stages) ? 0 : issue + 1;
@@ -111,11 +104,9 @@ struct WeightStreamDeep {
     slot = 0;
   }
   __device__ __forceinline__ const f32x4* begin() {
-#ifndef DINER_ABL_NO_BARRIER
     constexpr int keep = 8 * (D - 1);
     __builtin_amdgcn_s_waitcnt(0x0f70 | (keep & 15) | ((keep >> 4) << 14));
     __builtin_amdgcn_s_barrier();
-#endif
     int sd = slot + D;
     if (sd >= RING) sd -= RING;
     dma_src = base + (size_t)issue * kStageFloats;

@@ -47,7 +47,7 @@ struct DinerMlpImpl {
   float* b_post;   // per block b=3,4: fc_0, fc_1 -> 4 x 512, then lin_out (4, padded to 16)
   // split-precision (f16x3 / f16) copies for the feature-sliced kernels of mlp_h3n.hip: fp16 hi/lo fragments and biases, x16
   _Float16* hn_w;     // lin_in + the 6 per-view layers + the 4 post layers in the four-wave and the eight-wave order (mlp_h3n.hip, WeightLayout)
-  _Float16* hn_w_out; // lin_out fragments, then the fp32 pack of the vector-ALU lin_out
+  float* hn_w_out;    // the fp32 pack of the vector-ALU lin_out
   float* hn_b_pre; // 7 x 512, x16
   float* hn_b_post;// 4 x 512 x16, then lin_out bias (scale 1, padded to 16)
   float* wmax_dev; // max |parameter| (device scalar, reduced at pack time)
@@ -84,12 +84,12 @@ static int mlp_fits(const DinerMlpImpl* m, bool* fits) {
 }
 
 // mlp_h3n.hip
-int h3n_alloc(_Float16** w, _Float16** w_out, float** b_pre, float** b_post);
-int h3n_pack(const DinerMlpParams* p, hipStream_t stream, _Float16* w, _Float16* w_out, float* b_pre, float* b_post, bool train_only);
+int h3n_alloc(_Float16** w, float** w_out, float** b_pre, float** b_post);
+int h3n_pack(const DinerMlpParams* p, hipStream_t stream, _Float16* w, float* w_out, float* b_pre, float* b_post, bool train_only);
 int h3n_set_attributes();
 void h3n_launch_pre(const SceneDev& sc, const FieldArgs& fa, const _Float16* w, const float* b, int grid, bool split,
                     unsigned* tile_counter, hipStream_t stream, const SaveActs* sv = nullptr, const ViewGroup* vg = nullptr);
-void h3n_launch_post(const PostArgs& pa, const _Float16* w, const _Float16* w_out, int grid, bool split, unsigned* tile_counter,
+void h3n_launch_post(const PostArgs& pa, const _Float16* w, const float* w_out, int grid, bool split, unsigned* tile_counter,
                      hipStream_t stream, const SaveActs* sv = nullptr);
 
 // ------------------------------------------------------------------------------------------------------
@@ -142,14 +142,7 @@ typedef __attribute__((address_space(3))) float lds_float;
 //   * one 1 KB LDS-DMA piece of the NEXT stage goes out in each of steps 0..7;
 //   * a per-step hook does 1/16 of the VALU work that prepares the B operands of the next 64-feature chunk.
 // sched_barrier pins MFMA / LDS / VMEM order between steps; VALU and SALU may still float.
-#ifndef DINER_PIN_SCHEDULE
-#define DINER_PIN_SCHEDULE 1
-#endif
-#if DINER_PIN_SCHEDULE
 #define DINER_STEP_FENCE() __builtin_amdgcn_sched_barrier(0)
-#else
-#define DINER_STEP_FENCE()
-#endif
 
 struct NoHook {
   template <int STEP, int PIECE>
@@ -171,15 +164,11 @@ __device__ __forceinline__ void stage_step(WeightStream& ws, const f32x4* __rest
   constexpr int S2 = STEP + 2 < 16 ? STEP + 2 : 15;
   constexpr int ml2 = S2 >> 2, mp2 = S2 & 3;
   DINER_MFMA(acc[a0], f[0][0], bop[4 * ml + 0]);
-#ifndef DINER_ABL_NO_LDS
   if constexpr (STEP + 2 < 16) fnext[0] = cur[((2 * mp2) * 4 + ml2) * 64];
-#endif
   DINER_MFMA(acc[a1], f[1][0], bop[4 * ml + 0]);
   hook.template run<STEP, 0>();
   DINER_MFMA(acc[a0], f[0][1], bop[4 * ml + 1]);
-#ifndef DINER_ABL_NO_LDS
   if constexpr (STEP + 2 < 16) fnext[1] = cur[((2 * mp2 + 1) * 4 + ml2) * 64];
-#endif
   DINER_MFMA(acc[a1], f[1][1], bop[4 * ml + 1]);
   hook.template run<STEP, 1>();
   DINER_MFMA(acc[a0], f[0][2], bop[4 * ml + 2]);
@@ -189,7 +178,6 @@ __device__ __forceinline__ void stage_step(WeightStream& ws, const f32x4* __rest
   DINER_MFMA(acc[a0], f[0][3], bop[4 * ml + 3]);
   hook.template run<STEP, 3>();
   DINER_MFMA(acc[a1], f[1][3], bop[4 * ml + 3]);
-#if DINER_PIN_SCHEDULE
   // the order the scheduler must realise inside this step: MFMAs with at most a few other instructions between them
   __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);   // MFMA
   __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);   // DS read
@@ -206,7 +194,6 @@ __device__ __forceinline__ void stage_step(WeightStream& ws, const f32x4* __rest
   __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
   __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);
   __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-#endif
   DINER_STEP_FENCE();
 }
 
@@ -214,14 +201,10 @@ template <int MG, class Hook>
 __device__ __forceinline__ void stage_compute(WeightStream& ws, const f32x4* __restrict__ cur, const float (&bop)[16],
                                               f32x4 (&acc)[kTiles], Hook& hook) {
   f32x4 fa[2], fb[2], fc[2];
-#ifdef DINER_ABL_NO_LDS
-  asm volatile("" : "=v"(fa[0]), "=v"(fa[1]), "=v"(fb[0]), "=v"(fb[1]), "=v"(fc[0]), "=v"(fc[1]));
-#else
   fa[0] = cur[(0 * 4 + 0) * 64];
   fa[1] = cur[(1 * 4 + 0) * 64];
   fb[0] = cur[(2 * 4 + 0) * 64];
   fb[1] = cur[(3 * 4 + 0) * 64];
-#endif
 #define DINER_STEP(S_, FUSE, FLOAD) stage_step<MG, (S_)>(ws, cur, FUSE, FLOAD, bop, acc, hook);
   DINER_STEP(0, fa, fc)  DINER_STEP(1, fb, fa)  DINER_STEP(2, fc, fb)
   DINER_STEP(3, fa, fc)  DINER_STEP(4, fb, fa)  DINER_STEP(5, fc, fb)
@@ -937,7 +920,7 @@ static int mlp_alloc(DinerMlpImpl& im) {
 }
 
 // Packs the parameters into the handle's buffers on `stream` (no allocation, no synchronisation).  train_only: only what the fused
-// training forward reads -- the four-wave f16x3 layouts, the lin_out packs, the biases of those kernels, the constants of the projected
+// training forward reads -- the four-wave f16x3 layouts, the lin_out pack, the biases of those kernels, the constants of the projected
 // maps (b_hoist) and the weight range; the exact-fp32 stage tiles and the eight-wave layouts keep their old contents.
 static int mlp_pack_into(const DinerMlpParams* p, hipStream_t stream, DinerMlpImpl& im, bool train_only) {
   im.pack_stream = stream;

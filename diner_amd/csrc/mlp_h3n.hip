@@ -40,9 +40,6 @@ static_assert(kLdsBytes <= 160 * 1024, "LDS of one CU");
 // outputs [wave 4][g 4][pt 16] f32x4 (4 KB)
 constexpr size_t kLinOutWBytes = 4 * 8 * 4 * 4 * 16, kLinOutPartBytes = 4 * 4 * 16 * 16;
 constexpr size_t kLdsBytesPost = (size_t)kBHalfs * 2 + kLinOutWBytes + kLinOutPartBytes;
-#ifndef DINER_HN_LINOUT_VALU
-#define DINER_HN_LINOUT_VALU 1
-#endif
 
 // LDS operand buffer addressing: a per-lane byte address kept in one register + immediate offsets (the ds offset
 // field holds 16 bits, so the 128 KB buffer is reached from two bases 64 KB apart).  The bases are made opaque at
@@ -137,9 +134,6 @@ __device__ __forceinline__ void frontend_h3n(const SceneDev& sc, const MapDims& 
   bilinear_taps(dm.Wf, dm.Hf, sc.feature_padding, v, u, w, taps);
 }
 
-#ifndef DINER_HN_DYN            // 1: dynamic tile hand-out (atomic counter); 0: static round-robin tile += gridDim.x
-#define DINER_HN_DYN 1
-#endif
 // Tile hand-out.  The workgroups are persistent (one per CU: LDS and registers admit no second one); with a static round-robin the
 // launch ends when the slowest CU has done its share.  Here thread 0 asks for the NEXT tile at the top of the current one (an atomic
 // on a per-launch counter; the answer is needed ~230 k clocks later) and hands it to the workgroup through LDS at the bottom.
@@ -233,53 +227,35 @@ struct TileQueue {
         const unsigned long long cand = qm.tile(blockIdx.x & 7, e);
         if (cand < (unsigned long long)n_tiles) t = (unsigned)cand;
       }
-#if DINER_HN_DYN
       if (t == 0xffffffffu) t = fetch(counters, n_tiles, qm);
-#else
-      t = blockIdx.x < n_tiles ? blockIdx.x : 0xffffffffu;
-#endif
       *slot = t;
     }
   }
   __device__ __forceinline__ void request(unsigned* counters, long long n_tiles, const QueueMap& qm) {
-#if DINER_HN_DYN
     if (threadIdx.x == 0) nxt = fetch(counters, n_tiles, qm);
-#endif
   }
   // the same in two halves around a barrier the caller has anyway: offer() in front of it, take() behind it
   __device__ __forceinline__ void offer(unsigned* slot) {
-#if DINER_HN_DYN
     if (threadIdx.x == 0) *slot = nxt;
-#endif
   }
   // park(): thread 0 puts the answer into an LDS slot as soon as it has surely arrived (the caller places this behind its first GEMM); the
   // others may read it behind any later barrier, without one of their own.  The caller alternates between two slots: a slot is rewritten
   // two tiles later, behind many barriers.
   __device__ __forceinline__ void park(unsigned* slot) {
-#if DINER_HN_DYN
     if (threadIdx.x == 0) *slot = nxt;
-#endif
   }
   __device__ __forceinline__ long long initial(const unsigned* slot) {       // what first() left in *slot (behind a barrier)
     const unsigned t = (unsigned)__builtin_amdgcn_readfirstlane((int)*slot);
     return t == 0xffffffffu ? 0x7fffffffffffffffll : (long long)t;
   }
-  __device__ __forceinline__ long long take(long long tile, const unsigned* slot) {
-#if DINER_HN_DYN
+  __device__ __forceinline__ long long take(const unsigned* slot) {
     const unsigned t = (unsigned)__builtin_amdgcn_readfirstlane((int)*slot);
     return t == 0xffffffffu ? 0x7fffffffffffffffll : (long long)t;
-#else
-    return tile + gridDim.x;
-#endif
   }
-  __device__ __forceinline__ long long next(long long tile, unsigned* slot) {
-#if DINER_HN_DYN
+  __device__ __forceinline__ long long next(unsigned* slot) {
     offer(slot);
     __syncthreads();
-    return take(tile, slot);
-#else
-    return tile + gridDim.x;
-#endif
+    return take(slot);
   }
 };
 
@@ -338,12 +314,8 @@ struct NoSide {
   __device__ __forceinline__ void finish() {}
 };
 
-#ifndef DINER_HN_RING
-#define DINER_HN_RING 3
-#endif
-#ifndef DINER_HN_RING0          // A ring of the fc_0 GEMMs (no gather buffers live there)
-#define DINER_HN_RING0 DINER_HN_RING
-#endif
+constexpr int kHnRing = 3;
+constexpr int kHnRing0 = kHnRing;      // A ring of the fc_0 GEMMs (no gather buffers live there)
 
 // acc[mo][g] += W[slice rows][all k] . B[k][cols g]   (B from the LDS exchange buffer, A straight from global).
 // Fully unrolled over 2 KT half-steps (k32 block t, row-tile half) of four quarter-steps (column group g): 12 MFMAs
@@ -353,9 +325,6 @@ struct NoSide {
 //   * B fragments (hi, lo of one column group, shared) live in one buffer: group g of the next k32 block is re-read
 //     right after its last use in the second half (576 MFMA cycles before the next use);
 //   * the side task gets a slot per quarter-step, so its VALU / VMEM work is spread between the MFMAs.
-#ifndef DINER_HN_EARLYA
-#define DINER_HN_EARLYA 1
-#endif
 // The weight ring of one GEMM.  start() issues the first R-1 half-steps; on the per-view kernel's fc_0 GEMMs it is called BEFORE
 // the hidden state is published (the barriers in between wait on LDS traffic only, not on vmcnt), so the first fragments arrive
 // while the conversion runs -- neutral there (61.58 M vs 61.71 M clocks per wave); in the post kernel the same costs 5 % (the
@@ -370,26 +339,16 @@ struct ARing {
   gptr abase;
   unsigned avoff;
   __device__ __forceinline__ void load_a2(h8 (&dst)[8], int pair) {      // fragments 2 pair, 2 pair + 1 of the half-step at abase
-#ifdef DINER_HN_NO_A          // ablation: price the weight stream
-    asm volatile("" : "+v"(dst[2 * pair]), "+v"(dst[2 * pair + 1]));
-#else
     asm volatile("" : "+s"(abase));
 #pragma unroll
     for (int i = 2 * pair; i < 2 * pair + 2; ++i)
       dst[i] = *(const __attribute__((address_space(1))) h8*)(abase + avoff + (i * 1024 - 4096));
     if (pair == 3) abase += 8192;
-#endif
   }
   __device__ __forceinline__ void start(const _Float16* __restrict__ layer, int wave, int lane) {
     constexpr int NH = 2 * KT;
     abase = (gptr)(reinterpret_cast<const char*>(layer) + (size_t)wave * KT * 16384 + 4096);
     avoff = lane * 16;
-#if defined(DINER_HN_NO_A) || defined(DINER_HN_NO_B)
-#pragma unroll
-    for (int r = 0; r < R; ++r)
-#pragma unroll
-      for (int i = 0; i < 8; ++i) a[r][i] = *(reinterpret_cast<const h8*>(layer) + (r * 8 + i) * 64 + lane);
-#endif
     static_for<(R - 1 < NH ? R - 1 : NH)>([&](auto H) {
 #pragma unroll
       for (int pr = 0; pr < 4; ++pr) load_a2(a[decltype(H)::value], pr);
@@ -492,18 +451,10 @@ __device__ __forceinline__ void gemm(ARing<KT, R>& ring, LdsB B, int wave, const
     return cb;
   };
   auto load_b = [&](int t, int g) {
-#ifdef DINER_HN_NO_B          // ablation: price the LDS operand reads
-    asm volatile("" : "+v"(bb[g][0]), "+v"(bb[g][1]));
-#else
     bb[g][0] = *LdsB::at(cbp[t >> 2], t & 3, g, 0);
     bb[g][1] = *LdsB::at(cbp[t >> 2], t & 3, g, 1);
-#endif
   };
   cbp[0] = chunk_ptr(0);
-#if defined(DINER_HN_NO_A) || defined(DINER_HN_NO_B)
-#pragma unroll
-  for (int g = 0; g < kGroups; ++g) bb[g][0] = bb[g][1] = *LdsB::at(cbp[0], 0, g, 0);
-#endif
 #pragma unroll
   for (int g = 0; g < kGroups; ++g) load_b(0, g);      // (OWN: block 0 of the own chunk, written by this wave just before)
   u32x4 ch, cl;                          // OWN: the fragment pair being converted
@@ -557,74 +508,40 @@ __device__ __forceinline__ void gemm(const _Float16* __restrict__ layer, LdsB B,
   gemm<KT, R, false>(ring, B, wave, acc, 0.0f, acc, side);
 }
 
-// publish relu(acc) * scale of this wave's 128-feature slice as B operands (its own chunk: k32 blocks 4w .. 4w+3) for all 4 column
-// groups, in front of a GEMM (the GEMMs that carry a gather side task, lin_out)
-__device__ __forceinline__ void publish(LdsB B, int wave, int lane, const f32x4 (&acc)[kSlice][kGroups]) {
-  B.opaque();
-#ifdef DINER_HN_NO_PUBLISH
-  return;
-#endif
-  lds_ptr cb = B.chunk(wave);
-  asm volatile("" : "+v"(cb));
-#pragma unroll
-  for (int tl = 0; tl < 4; ++tl)
-#pragma unroll
-    for (int g = 0; g < kGroups; ++g) {
-      u32x4 h, l;
-      cvt4<true, 0>(acc[2 * tl][g], kInvScale, h, l);
-      cvt4<true, 1>(acc[2 * tl + 1][g], kInvScale, h, l);
-      *LdsB::at(cb, tl, g, 0) = __builtin_bit_cast(h8, h);
-      *LdsB::at(cb, tl, g, 1) = __builtin_bit_cast(h8, l);
-    }
-}
-
-// relu(src) -> B operands and the GEMM of `layer` on them.  OWN: the own-chunk scheme of gemm (one barrier in front, block 0 of the
-// own chunk converted before it so that the wait overlaps with the conversion, one barrier inside the GEMM); otherwise barrier,
-// publish, barrier, GEMM.  The weight ring is started first (EARLY) -- the barriers wait on LDS traffic only.
-template <int R, bool EARLY, bool OWN, bool BIAS_FIRST = true, class Side, class Between>
+// relu(src) -> B operands and the GEMM of `layer` on them, by the own-chunk scheme of gemm (one barrier in front, block 0 of the
+// own chunk converted before it so that the wait overlaps with the conversion, one barrier inside the GEMM).  The weight ring is
+// started first (EARLY) -- the barriers wait on LDS traffic only.
+template <int R, bool EARLY, bool BIAS_FIRST = true, class Side, class Between>
 __device__ __forceinline__ void publish_gemm(const _Float16* __restrict__ layer, LdsB B, int wave, int lane,
                                              const f32x4 (&src)[kSlice][kGroups], f32x4 (&acc)[kSlice][kGroups], Side& side,
                                              Between&& between, Prof& pf, int ph) {
   ARing<16, R> ring;
   if constexpr (EARLY) ring.start(layer, wave, lane);
-  if constexpr (OWN) {
-    if constexpr (BIAS_FIRST) between();          // bias of the accumulators the GEMM adds into (its loads fly during the conversion)
-    u32x4 c0[kGroups][2];
+  if constexpr (BIAS_FIRST) between();          // bias of the accumulators the GEMM adds into (its loads fly during the conversion)
+  u32x4 c0[kGroups][2];
 #pragma unroll
-    for (int g = 0; g < kGroups; ++g) {           // block 0 of the own chunk, converted while the others finish the previous GEMM
-      cvt4<true, 0>(src[0][g], kInvScale, c0[g][0], c0[g][1]);
-      cvt4<true, 1>(src[1][g], kInvScale, c0[g][0], c0[g][1]);
-    }
-    pf.mark(ph);
-    __syncthreads();                              // everybody finished reading the previous B
-    pf.mark(ph + 1);
-    {
-      B.opaque();
-      lds_ptr cb = B.chunk(wave);
-      asm volatile("" : "+v"(cb));
-#pragma unroll
-      for (int g = 0; g < kGroups; ++g) {
-        *LdsB::at(cb, 0, g, 0) = __builtin_bit_cast(h8, c0[g][0]);
-        *LdsB::at(cb, 0, g, 1) = __builtin_bit_cast(h8, c0[g][1]);
-      }
-    }
-    if constexpr (!BIAS_FIRST) between();
-    if constexpr (!EARLY) ring.start(layer, wave, lane);
-    pf.mark(ph + 2);
-    gemm<16, R, true>(ring, B, wave, src, kInvScale, acc, side);
-    pf.mark(ph + 3);
-  } else {
-    __syncthreads();                              // everybody finished reading the previous B
-    pf.mark(ph);
-    publish(B, wave, lane, src);
-    pf.mark(ph + 1);
-    __syncthreads();
-    pf.mark(ph + 2);
-    between();                                    // bias of the accumulators the GEMM adds into
-    if constexpr (!EARLY) ring.start(layer, wave, lane);
-    gemm<16, R, false>(ring, B, wave, src, kInvScale, acc, side);
-    pf.mark(ph + 3);
+  for (int g = 0; g < kGroups; ++g) {           // block 0 of the own chunk, converted while the others finish the previous GEMM
+    cvt4<true, 0>(src[0][g], kInvScale, c0[g][0], c0[g][1]);
+    cvt4<true, 1>(src[1][g], kInvScale, c0[g][0], c0[g][1]);
   }
+  pf.mark(ph);
+  __syncthreads();                              // everybody finished reading the previous B
+  pf.mark(ph + 1);
+  {
+    B.opaque();
+    lds_ptr cb = B.chunk(wave);
+    asm volatile("" : "+v"(cb));
+#pragma unroll
+    for (int g = 0; g < kGroups; ++g) {
+      *LdsB::at(cb, 0, g, 0) = __builtin_bit_cast(h8, c0[g][0]);
+      *LdsB::at(cb, 0, g, 1) = __builtin_bit_cast(h8, c0[g][1]);
+    }
+  }
+  if constexpr (!BIAS_FIRST) between();
+  if constexpr (!EARLY) ring.start(layer, wave, lane);
+  pf.mark(ph + 2);
+  gemm<16, R, true>(ring, B, wave, src, kInvScale, acc, side);
+  pf.mark(ph + 3);
 }
 
 // Tell the register allocator that a block of accumulators lives in the AGPR half of the file at this point (no code).
@@ -652,24 +569,8 @@ __device__ __forceinline__ void add_bias(f32x4 (&acc)[kSlice][kGroups], const fl
   }
 }
 
-#ifndef DINER_HN_OWN            // 1: own-chunk scheme on every GEMM without a gather side task (see gemm); 0: exposed publishes
-#define DINER_HN_OWN 1
-#endif
-#ifndef DINER_HN_EARLY1         // weight ring of the fc_1 GEMMs started in front of the conversion as well
-#define DINER_HN_EARLY1 0
-#endif
-#ifndef DINER_HN_EARLYP         // ... and in the post kernel
-#define DINER_HN_EARLYP 0
-#endif
-#ifndef DINER_HN_OWNG           // the same on the two GEMMs that carry the gather side task
-#define DINER_HN_OWNG 1
-#endif
-#ifndef DINER_HN_GDEPTH
-#define DINER_HN_GDEPTH 2
-#endif
-#ifndef DINER_HN_G0DEPTH        // units in flight for block 0's stand-alone gather (no GEMM buffers live there)
-#define DINER_HN_G0DEPTH 8
-#endif
+constexpr int kHnGDepth = 2;
+constexpr int kHnG0Depth = 8;      // units in flight for block 0's stand-alone gather (no GEMM buffers live there)
 
 // xs[mo][g] += 16 * interp(lin_z[b](latent)) for this wave's feature slice and all four column groups: 32 units
 // (g, mo) of 4 taps each.  As a GEMM side task (SIDE) one unit's taps are requested per half-step, one per quarter-step, and
@@ -706,23 +607,15 @@ struct GatherSide {
   template <int U, int KTAP>       // one of the unit's four taps (the GEMM side task spreads them over the quarter-steps)
   __device__ __forceinline__ void issue_tap() {
     constexpr int g = U >> 3, mo = U & 7;
-#ifdef DINER_HN_G_NOLOAD        // ablation: the side task without its loads
-    asm volatile("" : "+v"(r[U % GD][KTAP]));
-#else
     const char* base = reinterpret_cast<const char*>(tz);          // scalar base + 32-bit lane offset + immediate
     const unsigned lane_off = (32 * wave + q) * 16;
     r[U % GD][KTAP] = *reinterpret_cast<const f32x4*>(base + (off4[g][KTAP] * 2048u + lane_off) + mo * 64);
-#endif
   }
   // tap K's share of the blend sum_k t_k (16 w_k)
   template <int U, int K>
   __device__ __forceinline__ void blend_step() {
     constexpr int g = U >> 3, mo = U & 7;
     const f32x4 (&t)[4] = r[U % GD];
-#ifdef DINER_HN_G_NOBLEND       // ablation: the loads without the arithmetic
-    asm volatile("" :: "v"(t[K]));
-    return;
-#endif
     if constexpr (K == 0) {
       bw = w4[g];
       // Keep w an opaque register value.  Without this the hipcc 7.2 build of an earlier version of this kernel returned
@@ -757,16 +650,13 @@ struct GatherSide {
   // half-step H: unit H's taps are requested and unit V = H - GD + 1 is blended, tap G of either in quarter-step G
   template <int H, int G>
   __device__ __forceinline__ void run() {
-#ifndef DINER_HN_NO_GATHER
     static_assert(GD >= 2, "a tap is blended at least one half-step after it was requested");
     constexpr int V = H - GD + 1;
     if constexpr (V >= 0 && V < 32) blend_step<(V >= 0 && V < 32 ? V : 0), G>();
     if constexpr (H < 32) issue_tap<(H < 32 ? H : 0), G>();
     if constexpr (G == 1 && (H & 7) == 7 && H < 31) prefetch<(H < 31 ? (H + 1) >> 3 : 0)>();
-#endif
   }
   __device__ __forceinline__ void finish() {
-#ifndef DINER_HN_NO_GATHER
     static_for<GD - 1>([&](auto I) {
       constexpr int V = 33 - GD + decltype(I)::value;
       blend_step<V, 0>();
@@ -774,7 +664,6 @@ struct GatherSide {
       blend_step<V, 2>();
       blend_step<V, 3>();
     });
-#endif
   }
   // stand-alone (no GEMM to hide under): block 0
   __device__ __forceinline__ void all() {
@@ -783,26 +672,6 @@ struct GatherSide {
       run<decltype(H)::value, 1>();
       run<decltype(H)::value, 2>();
       run<decltype(H)::value, 3>();
-    });
-    finish();
-  }
-  // the same in two parts (experiment DINER_HN_G0EARLY, round 4): head() = the first GD - 1 units' requests only (no blend reads xs yet),
-  // issued in front of the lin_in GEMM; tail() = the rest behind it
-  __device__ __forceinline__ void head() {
-    static_for<GD - 1>([&](auto H) {
-      run<decltype(H)::value, 0>();
-      run<decltype(H)::value, 1>();
-      run<decltype(H)::value, 2>();
-      run<decltype(H)::value, 3>();
-    });
-  }
-  __device__ __forceinline__ void tail() {
-    static_for<32 - (GD - 1)>([&](auto I) {
-      constexpr int H = GD - 1 + decltype(I)::value;
-      run<H, 0>();
-      run<H, 1>();
-      run<H, 2>();
-      run<H, 3>();
     });
     finish();
   }
@@ -846,7 +715,6 @@ __device__ __forceinline__ void save_block(float* __restrict__ dst, unsigned* __
 template <bool SAVE, bool GROUP = false>
 __device__ __forceinline__ void field_pre_body(const SceneDev& sc, const Args& a, const SaveActs& sv, const ViewGroup& vg = ViewGroup{}) {
   static_assert(!(SAVE && GROUP), "the training forward runs four views");
-  constexpr int kRing = DINER_HN_RING, kRing0 = DINER_HN_RING0, kGDepth = DINER_HN_GDEPTH;
   extern __shared__ __attribute__((aligned(16))) float smem[];
   h8* B = reinterpret_cast<h8*>(smem);
   TapRec* taps_lds = reinterpret_cast<TapRec*>(reinterpret_cast<char*>(smem) + (size_t)kBHalfs * 2);
@@ -872,7 +740,7 @@ __device__ __forceinline__ void field_pre_body(const SceneDev& sc, const Args& a
 
   Prof pf;
   pf.begin();
-  for (long long tile = tq.initial(&s_tile); tile < n_tiles; tile = tq.next(tile, &s_tile)) {
+  for (long long tile = tq.initial(&s_tile); tile < n_tiles; tile = tq.next(&s_tile)) {
     tq.request(a.tile_counter, n_tiles, a.qmap);
     long long p = tile * kPtsPerWave + pt;
     if (p >= fa.P) p = fa.P - 1;
@@ -917,18 +785,10 @@ __device__ __forceinline__ void field_pre_body(const SceneDev& sc, const Args& a
     set_bias(xs, a.b, wave, q);
     {
       NoSide none;
-#if defined(DINER_HN_G0EARLY)   // experiment: block 0's first tap requests in front of the lin_in GEMM (measured, not kept: profiles/r04_ab_runs.txt)
-      GatherSide<DINER_HN_G0DEPTH, false> g0(fa.tz, taps_lds, wave, q, pt, xs);
-      g0.head();
       gemm<2, 2>(w_in, Bl, wave, lane, xs, none);
       pf.mark(4);
-      g0.tail();
-#else
-      gemm<2, 2>(w_in, Bl, wave, lane, xs, none);
-      pf.mark(4);
-      GatherSide<DINER_HN_G0DEPTH, false> g0(fa.tz, taps_lds, wave, q, pt, xs);     // lin_z[0]: nothing long enough to hide under yet
+      GatherSide<kHnG0Depth, false> g0(fa.tz, taps_lds, wave, q, pt, xs);     // lin_z[0]: nothing long enough to hide under yet
       g0.all();
-#endif
       pf.mark(5);
     }
 #pragma nounroll
@@ -937,38 +797,24 @@ __device__ __forceinline__ void field_pre_body(const SceneDev& sc, const Args& a
       if constexpr (SAVE) save_block<true>(sv.X[b], sv.bX[b], fa.P, tile, wave, lane, xs);
       {
         NoSide none;
-        publish_gemm<kRing0, DINER_HN_EARLYA != 0, DINER_HN_OWN != 0>(
+        publish_gemm<kHnRing0, true>(
             w_blk + (size_t)(2 * b) * kLayerHalfs, Bl, wave, lane, xs, ns, none, [&] { set_bias(ns, bias, wave, q); }, pf, 6);
       }
       if constexpr (SAVE) save_block<true>(sv.H[b], sv.bH[b], fa.P, tile, wave, lane, ns);
       // the next block's lin_z contribution rides on the fc_1 GEMM (additions into xs commute); this block's fc_1 bias comes with it
       // (folded into the projected map's bias when the weights are packed, mlp.hip)
       const _Float16* w1 = w_blk + (size_t)(2 * b + 1) * kLayerHalfs;
-#if DINER_HN_OWNG
-      GatherSide<kGDepth> gs(fa.tz + (size_t)(b + 1) * fa.tz_stride, taps_lds, wave, q, pt, xs);
-      publish_gemm<kRing, DINER_HN_EARLY1 != 0, true>(w1, Bl, wave, lane, ns, xs, gs, [&] { pin_acc(xs); }, pf, 10);
-#else
-      __syncthreads();
-      pf.mark(10);
-      publish(Bl, wave, lane, ns);
-      pf.mark(11);
-      __syncthreads();
-      pf.mark(12);
-      pin_acc(xs);
-      GatherSide<kGDepth> gs(fa.tz + (size_t)(b + 1) * fa.tz_stride, taps_lds, wave, q, pt, xs);
-      gemm<16, kRing>(w1, Bl, wave, lane, xs, gs);
-      pf.mark(13);
-#endif
+      GatherSide<kHnGDepth> gs(fa.tz + (size_t)(b + 1) * fa.tz_stride, taps_lds, wave, q, pt, xs);
+      publish_gemm<kHnRing, false>(w1, Bl, wave, lane, ns, xs, gs, [&] { pin_acc(xs); }, pf, 10);
     }
     {   // block 2: no gather left (and its fc_1 bias is added by the post kernel)
       const float* bias = a.b + kHidden * 5;
       NoSide none;
       if constexpr (SAVE) save_block<true>(sv.X[2], sv.bX[2], fa.P, tile, wave, lane, xs);
-      publish_gemm<kRing0, DINER_HN_EARLYA != 0, DINER_HN_OWN != 0>(
+      publish_gemm<kHnRing0, true>(
           w_blk + (size_t)4 * kLayerHalfs, Bl, wave, lane, xs, ns, none, [&] { set_bias(ns, bias, wave, q); }, pf, 6);
       if constexpr (SAVE) save_block<true>(sv.H[2], sv.bH[2], fa.P, tile, wave, lane, ns);
-      publish_gemm<kRing, DINER_HN_EARLY1 != 0, DINER_HN_OWN != 0>(w_blk + (size_t)5 * kLayerHalfs, Bl, wave, lane, ns, xs, none,
-                                                                   [&] { pin_acc(xs); }, pf, 10);
+      publish_gemm<kHnRing, false>(w_blk + (size_t)5 * kLayerHalfs, Bl, wave, lane, ns, xs, none, [&] { pin_acc(xs); }, pf, 10);
     }
     // view mean = mean over the four column groups; hand-over at scale 1 in accumulator layout (row tile 8 w + mo)
     f32x4* out = reinterpret_cast<f32x4*>(fa.xpre) + (size_t)tile * (kTiles * 64) + lane;
@@ -1035,24 +881,10 @@ constexpr size_t kFeatSrcBytes8 = 512 * kSrcStride * 4;
 constexpr size_t kLdsBytes8 = (size_t)2 * kB8Bytes + kTapsBytes + kFeatTabBytes + kFeatSrcBytes8;      // two B buffers (see the kernel)
 static_assert(kLdsBytes8 <= 160 * 1024, "LDS of one CU");
 constexpr size_t kLinInHalfs8 = (size_t)8 * 2 * 4 * 512, kLayerHalfs8 = (size_t)8 * 16 * 4 * 512;
-#ifndef DINER_H8_RING
-#define DINER_H8_RING 3
-#endif
-#ifndef DINER_H8_RING0            // ... of the GEMMs without a side task (no tap buffers live)
-#define DINER_H8_RING0 4
-#endif
-#ifndef DINER_H8_GDEPTH          // units between a tap request and its blend: as a GEMM side task / stand-alone (block 0)
-#define DINER_H8_GDEPTH 1
-#endif
-#ifndef DINER_H8_G0DEPTH
-#define DINER_H8_G0DEPTH 4
-#endif
-#ifndef DINER_H8_FLAGS           // 1: the 512-wide GEMMs wait for the data they need next (per-wave publish flags) instead of a barrier per layer
-#define DINER_H8_FLAGS 0
-#endif
-#ifndef DINER_H8_TAPS_A          // 1: the tap buffers of the side task in AGPRs
-#define DINER_H8_TAPS_A 0
-#endif
+constexpr int kH8Ring = 3;
+constexpr int kH8Ring0 = 4;        // ... of the GEMMs without a side task (no tap buffers live)
+constexpr int kH8GDepth = 1;       // units between a tap request and its blend: as a GEMM side task / stand-alone (block 0)
+constexpr int kH8G0Depth = 4;
 
 __device__ __forceinline__ lds_h8 bfrag8(lds_ptr base, int t, int g) { return (lds_h8)(base + (t * kGroups + g) * 1024); }
 
@@ -1087,35 +919,14 @@ struct NoSide8 {
 
 // acc[mo][g] += W[64 w + 16 mo ..][k] . B[k][16 g ..]: 16 MFMAs per k32 block (one weight fragment per row tile, one B fragment per
 // column group); the fragments of block t + R - 1 are requested one per quarter-step, B fragment g of block t + 1 is re-read right
-// after its last use for block t
-// ACC_A: the accumulator block lives in the AGPR half of the file (the residual stream xs); false: in arch VGPRs (the hidden block ns, dead
-// while the gather-carrying GEMM runs -- with both blocks pinned to AGPRs the arch half is 128 registers and the ring + taps spill)
-// FL (round 5, 512-wide contractions): NO barrier in front of the GEMM.  Wave w walks the k32 blocks in ITS OWN order -- step s is block
-// (2 w + s) & 15: its own two blocks first (it published them itself), then the next wave's, ... -- and, one step before it first reads
-// the blocks of wave j, waits until that wave has published this layer's operands: `flags[j] >= need` (an LDS word per wave, stored with
-// release semantics behind the wave's publish).  The weights are packed in the same rotated order (k_pack_layer_h8).  A wave that is
-// done with its GEMM publishes at once into the other B buffer; nobody waits for the slowest wave any more, only for the data it needs
-// next.  (Two buffers are enough: to FINISH layer L + 1 a wave needs every wave's layer-L operands, which a wave publishes after its
-// own layer-L GEMM -- so nobody can still be reading the buffer a finished layer-(L+1) wave writes into.)
-template <int KT, int R, bool ACC_A, bool FL = false, class Side>
-__device__ __forceinline__ void gemm8(const _Float16* __restrict__ layer, lds_ptr Bb, int wave, int lane, f32x4 (&acc)[kS8][kGroups], Side& side,
-                                      const unsigned* flags = nullptr, unsigned need = 0) {
-  static_assert(!FL || KT == 16, "flag-synchronised walk: 512-wide contractions");
+// after its last use for block t.  The accumulator block lives in the AGPR half of the file.
+template <int KT, int R, class Side>
+__device__ __forceinline__ void gemm8(const _Float16* __restrict__ layer, lds_ptr Bb, int wave, int lane, f32x4 (&acc)[kS8][kGroups], Side& side) {
   ARing8<KT, R> ring;
   ring.start(layer, wave, lane);
   asm volatile("" : "+v"(Bb));
   h8 bb[kGroups];
-  // FL: the lane's pointer to block step s (fragment offsets then are immediates below 4 KB); otherwise Bb + immediates
-  auto step_ptr = [&](int s) -> lds_ptr {
-    if constexpr (FL) {
-      const int blk = (2 * wave + s) & 15;          // (scalar)
-      lds_ptr pp = Bb + blk * (kGroups * 1024);
-      asm volatile("" : "+v"(pp));
-      return pp;
-    } else {
-      return Bb + s * (kGroups * 1024);
-    }
-  };
+  auto step_ptr = [&](int s) -> lds_ptr { return Bb + s * (kGroups * 1024); };      // block step s: Bb + immediates
   lds_ptr pcur = step_ptr(0), pnext = KT > 1 ? step_ptr(1) : pcur;
 #pragma unroll
   for (int g = 0; g < kGroups; ++g) bb[g] = *(lds_h8)(pcur + g * 1024);
@@ -1128,12 +939,6 @@ __device__ __forceinline__ void gemm8(const _Float16* __restrict__ layer, lds_pt
       bb[kGroups - 1] = *(lds_h8)(pcur + (kGroups - 1) * 1024);
       if constexpr (t + 1 < KT) pnext = step_ptr(t + 1);
     }
-    if constexpr (FL && g == 1 && (t & 1) == 1 && t + 1 < KT) {
-      // the blocks of step t + 1, t + 2 belong to wave (w + (t + 1) / 2) & 7: its publish of this layer must have happened
-      const int j = (wave + (t + 1) / 2) & 7;
-      while (__builtin_amdgcn_readfirstlane((int)__hip_atomic_load(flags + j, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP)) - (int)need < 0)
-        __builtin_amdgcn_s_sleep(1);
-    }
     if constexpr (g > 0 && t + 1 < KT) bb[g - 1] = *(lds_h8)(pnext + (g - 1) * 1024);
     side.template run<t, g>();
     h8 (&ac)[4] = ring.a[t % R];
@@ -1141,38 +946,21 @@ __device__ __forceinline__ void gemm8(const _Float16* __restrict__ layer, lds_pt
 #pragma unroll
     for (int m = 0; m < kS8; ++m) DINER_HN_MFMA(acc[m][g], ac[m], b0);
 #pragma unroll
-    for (int m = 0; m < kS8; ++m) {
-      if constexpr (ACC_A) asm volatile("" : "+a"(acc[m][g]));
-      else asm volatile("" : "+v"(acc[m][g]));
-    }
+    for (int m = 0; m < kS8; ++m) asm volatile("" : "+a"(acc[m][g]));
     if constexpr (g == kGroups - 1) pcur = pnext;
   });
   side.finish();
 }
 
 // two row tiles' values of one column group (rows 4q .. 4q+3 each) -> one B fragment: relu on the bit pattern, x 1/16, round to fp16
-template <bool ACC_A>
 __device__ __forceinline__ u32x4 cvt_frag8(const f32x4& x0, const f32x4& x1) {
-  u32x4 h;
-  if constexpr (ACC_A) {
-    u32x4 l;
-    cvt4<false, 0>(x0, kInvScale, h, l);
-    cvt4<false, 1>(x1, kInvScale, h, l);
-  } else {
-    float v[8];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      v[i] = mul1s(__int_as_float(max(__float_as_int(x0[i]), 0)), kInvScale);
-      v[4 + i] = mul1s(__int_as_float(max(__float_as_int(x1[i]), 0)), kInvScale);
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) h[i] = cvt_pk_f16(v[2 * i], v[2 * i + 1]);
-  }
+  u32x4 h, l;
+  cvt4<false, 0>(x0, kInvScale, h, l);
+  cvt4<false, 1>(x1, kInvScale, h, l);
   return h;
 }
 
 // relu(acc) / 16 -> fp16 B operands of this wave's two k32 blocks (2 w, 2 w + 1), all four column groups
-template <bool ACC_A>
 __device__ __forceinline__ void publish8(lds_ptr Bb, int wave, const f32x4 (&acc)[kS8][kGroups]) {
   lds_ptr mine = Bb + wave * (2 * kGroups * 1024);
   asm volatile("" : "+v"(mine));
@@ -1180,7 +968,7 @@ __device__ __forceinline__ void publish8(lds_ptr Bb, int wave, const f32x4 (&acc
   for (int tl = 0; tl < 2; ++tl)
 #pragma unroll
     for (int g = 0; g < kGroups; ++g) {
-      *bfrag8(mine, tl, g) = __builtin_bit_cast(h8, cvt_frag8<ACC_A>(acc[2 * tl][g], acc[2 * tl + 1][g]));
+      *bfrag8(mine, tl, g) = __builtin_bit_cast(h8, cvt_frag8(acc[2 * tl][g], acc[2 * tl + 1][g]));
     }
 }
 
@@ -1239,41 +1027,12 @@ struct Gather8 {
   template <int U, int KTAP>
   __device__ __forceinline__ void issue_tap() {
     constexpr int mp = U & 1;
-#ifdef DINER_H8_G_NOLOAD        // ablation: the side task without its loads
-    asm volatile("" : "+v"(r[U % (D + 1)][KTAP]));
-#else
-#ifdef DINER_H8_TAPS_SAME       // ablation: every tap from texel row 0..3 (always cached): prices the taps' latency
-    r[U % (D + 1)][KTAP] = *reinterpret_cast<const u32x4*>(tz + ((off4[KTAP] & 3u) * 1024u + lane_off) + mp * 64);
-#else
     r[U % (D + 1)][KTAP] = *reinterpret_cast<const u32x4*>(tz + (off4[KTAP] * 1024u + lane_off) + mp * 64);
-#endif
-#if DINER_H8_TAPS_A
-    // the tap lands in the AGPR half of the file (the hidden block's 64 registers are dead while this GEMM runs; the arch half holds the
-    // weight ring and the B fragments): read back one dword at a time where it is blended
-    asm volatile("" : "+a"(r[U % (D + 1)][KTAP]));
-#endif
-#endif
   }
   template <int U, int HF, int K>
   __device__ __forceinline__ void blend_step() {
     constexpr int g = U >> 1, mo = 2 * (U & 1) + HF;
-#if DINER_H8_TAPS_A
-    u32x4 t;
-    {
-      const u32x4& ta = r[U % (D + 1)][K];
-      int t0, t1;
-      asm("v_accvgpr_read_b32 %0, %1" : "=v"(t0) : "a"(ta[2 * HF]));
-      asm("v_accvgpr_read_b32 %0, %1" : "=v"(t1) : "a"(ta[2 * HF + 1]));
-      t[2 * HF] = (unsigned)t0;
-      t[2 * HF + 1] = (unsigned)t1;
-    }
-#else
     const u32x4& t = r[U % (D + 1)][K];
-#endif
-#ifdef DINER_H8_NO_BLEND        // ablation: the loads without the arithmetic
-    asm volatile("" :: "v"(t[2 * HF]), "v"(t[2 * HF + 1]));
-    return;
-#endif
     if constexpr (K == 0) {
       bw = w4;
       asm volatile("" : "+v"(bw));           // (see GatherSide::blend_step)
@@ -1284,10 +1043,6 @@ struct Gather8 {
     bv[2] = mix_lo(t[2 * HF + 1], bw[K], bv[2]);
     bv[3] = mix_hi(t[2 * HF + 1], bw[K], bv[3]);
     if constexpr (K == 3) {
-#ifdef DINER_H8_NO_ACCUM        // ablation: the blend without the accumulator update
-      asm volatile("" :: "v"(bv));
-      return;
-#endif
       asm volatile("" : "+a"(xs[mo][g]));      // keep the accumulator file assignment: read, add, write back
       f32x4 acc = xs[mo][g];
 #pragma unroll
@@ -1325,7 +1080,7 @@ struct Gather8 {
 };
 
 __global__ __launch_bounds__(512, 1) void k_field_pre_h8(SceneDev sc, Args a) {
-  constexpr int R = DINER_H8_RING, R0 = DINER_H8_RING0;
+  constexpr int R = kH8Ring, R0 = kH8Ring0;
   extern __shared__ __attribute__((aligned(16))) float smem[];
   h8* B = reinterpret_cast<h8*>(smem);
   TapRec* taps_lds = reinterpret_cast<TapRec*>(reinterpret_cast<char*>(smem) + (size_t)2 * kB8Bytes);
@@ -1341,9 +1096,6 @@ __global__ __launch_bounds__(512, 1) void k_field_pre_h8(SceneDev sc, Args a) {
     feat_tab[threadIdx.x] = feat_recipe(16 * (sl >> 2) + 4 * (threadIdx.x >> 4) + (sl & 3), fa.freq_factor);
   }
   const long long n_tiles = (fa.P + kPtsPerWave - 1) / kPtsPerWave;
-  __shared__ unsigned s_flag[8];             // per wave: number of publishes done (DINER_H8_FLAGS)
-  if (threadIdx.x < 8) s_flag[threadIdx.x] = 0;
-  unsigned seq = 0;
   __shared__ unsigned s_tile;
   TileQueue tq;
   tq.begin();
@@ -1359,7 +1111,7 @@ __global__ __launch_bounds__(512, 1) void k_field_pre_h8(SceneDev sc, Args a) {
 
   Prof pf;
   pf.begin();
-  for (long long tile = tq.initial(&s_tile); tile < n_tiles; tile = tq.next(tile, &s_tile)) {
+  for (long long tile = tq.initial(&s_tile); tile < n_tiles; tile = tq.next(&s_tile)) {
     tq.request(a.tile_counter, n_tiles, a.qmap);
     long long p = tile * kPtsPerWave + pt;
     if (p >= fa.P) p = fa.P - 1;
@@ -1414,55 +1166,43 @@ __global__ __launch_bounds__(512, 1) void k_field_pre_h8(SceneDev sc, Args a) {
     pin_acc8(xs);
     {
       NoSide8 none;
-      gemm8<2, 2, true>(w_in, Brd, wave, lane, xs, none);
+      gemm8<2, 2>(w_in, Brd, wave, lane, xs, none);
       pf.mark(4);
-      Gather8<DINER_H8_G0DEPTH> g0(tz16, taps_lds, wave, q, pt, xs);      // lin_z[0]: nothing long enough to hide under yet
+      Gather8<kH8G0Depth> g0(tz16, taps_lds, wave, q, pt, xs);      // lin_z[0]: nothing long enough to hide under yet
       g0.all();
       pf.mark(5);
     }
     // one residual block: x += fc_1(relu(fc_0(relu(x)))) (+ the next block's projected taps riding on the fc_1 GEMM).  The hidden block
     // lives inside the lambda: dead behind its publish, its 64 registers are free while the gather-carrying GEMM runs
-    auto published = [&]() {                       // this wave's operands of the next layer are in LDS: tell the others
-      ++seq;
-#if DINER_H8_FLAGS
-      if (lane == 0) __hip_atomic_store(&s_flag[wave], seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-#else
-      __syncthreads();
-#endif
-    };
     auto block = [&](int b, auto&& side) {
       const float* bias = a.b + kHidden * (1 + 2 * b);
       pf.mark(6);
-      publish8<true>(Bwr, wave, xs);                // (the other buffer: nobody reads it now)
+      publish8(Bwr, wave, xs);                // (the other buffer: nobody reads it now)
       pf.mark(7);
-      published();
+      __syncthreads();                        // this layer's operands of every wave are in LDS
       pf.mark(8);
       {
         f32x4 ns[kS8][kGroups];
         set_bias8(ns, bias, wave, q);
         NoSide8 none;
-        gemm8<16, R0, true, DINER_H8_FLAGS != 0>(w_blk + (size_t)(2 * b) * kLayerHalfs8, Bwr, wave, lane, ns, none, s_flag, seq);
+        gemm8<16, R0>(w_blk + (size_t)(2 * b) * kLayerHalfs8, Bwr, wave, lane, ns, none);
         pf.mark(9);
         pf.mark(10);
-        publish8<true>(Brd, wave, ns);
+        publish8(Brd, wave, ns);
         pf.mark(11);
       }
-      published();
+      __syncthreads();                        // this layer's operands of every wave are in LDS
       pf.mark(12);
       pin_acc8(xs);
       constexpr int R1 = std::is_same<std::decay_t<decltype(side)>, NoSide8>::value ? R0 : R;
-      gemm8<16, R1, true, DINER_H8_FLAGS != 0>(w_blk + (size_t)(2 * b + 1) * kLayerHalfs8, Brd, wave, lane, xs, side, s_flag, seq);
+      gemm8<16, R1>(w_blk + (size_t)(2 * b + 1) * kLayerHalfs8, Brd, wave, lane, xs, side);
       pf.mark(13);
     };
 #pragma nounroll
     for (int b = 0; b < 2; ++b) {
       // the next block's lin_z contribution rides on the fc_1 GEMM (additions into xs commute); this block's fc_1 bias comes with it
       // (folded into the projected map's bias when the weights are packed, mlp.hip)
-#ifdef DINER_H8_NO_GATHER       // ablation
-      NoSide8 gs;
-#else
-      Gather8<DINER_H8_GDEPTH> gs(tz16 + (size_t)(b + 1) * fa.tz_stride, taps_lds, wave, q, pt, xs);
-#endif
+      Gather8<kH8GDepth> gs(tz16 + (size_t)(b + 1) * fa.tz_stride, taps_lds, wave, q, pt, xs);
       block(b, gs);
     }
     {   // block 2: no gather left (and its fc_1 bias is added by the post kernel)
@@ -1481,13 +1221,11 @@ __global__ __launch_bounds__(512, 1) void k_field_pre_h8(SceneDev sc, Args a) {
 }
 
 // layer packing for k_field_pre_h8: [w 8][t KT][mo 4][lane 64][8] = W[64 w + 16 mo + (lane & 15)][32 t + 16 (j >> 2) + 4 (lane >> 4) + (j & 3)] * scale
-// (512-wide layers, DINER_H8_FLAGS: position s of wave w's stream is k32 block (2 w + s) & 15 -- the wave's own blocks first, see gemm8)
 __global__ void k_pack_layer_h8(const float* __restrict__ W, int rows, int cols, int KT, float scale, _Float16* __restrict__ dst) {
   const long long total = (long long)8 * KT * 2048;
   for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
     const int j = i & 7, lane = (i >> 3) & 63, mo = (i >> 9) & 3;
-    const int wt = (int)(i >> 11), ts = wt % KT, w = wt / KT;
-    const int t = (KT == 16 && DINER_H8_FLAGS != 0) ? ((2 * w + ts) & 15) : ts;
+    const int wt = (int)(i >> 11), t = wt % KT, w = wt / KT;
     const int row = 64 * w + 16 * mo + (lane & 15);
     const int col = 32 * t + 16 * (j >> 2) + 4 * (lane >> 4) + (j & 3);
     dst[i] = (_Float16)((row < rows && col < cols) ? W[(size_t)row * cols + col] * scale : 0.0f);
@@ -1499,8 +1237,7 @@ struct PostArgsN {
   PostArgs pa;
   const _Float16* w;        // n-split packed fc_0 / fc_1 of blocks 3, 4 (4 layers of 4 * 16 * 16 KB)
   const _Float16* w8;       // the same four layers in the eight-wave kernels' order (hi plane; k_field_post_h8), or null
-  const _Float16* w_out;    // lin_out fragments [t 16][hl 2][lane 64][8] (rows >= 4 zero), x16; behind them (32 KB on) the fp32 pack
-                            // [wave 4][mo 8][q 4][o 4][j 4] = Wout[o][128 wave + 16 mo + 4 q + j] / 16 of the vector-ALU lin_out
+  const float* w_out;       // lin_out for the vector ALU: [wave 4][mo 8][q 4][o 4][j 4] = Wout[o][128 wave + 16 mo + 4 q + j] / 16
   unsigned long long* prof; // DINER_HN_PROF builds: phase counters, else unused
   unsigned* tile_counter;   // see TileQueue
   QueueMap qmap;            // the default map (tile % 8): the post kernel's tiles are 64 consecutive points, no taps
@@ -1535,16 +1272,14 @@ __device__ __forceinline__ void field_post_body(const PostArgsN& a, const SaveAc
   TileQueue tq;
   tq.begin();
   f32x4 xs[kSlice][kGroups], ns[kSlice][kGroups];
-#if DINER_HN_LINOUT_VALU
   typedef __attribute__((address_space(3))) f32x4* lds_f4;
   const lds_f4 lo_w = (lds_f4)((lds_ptr)(reinterpret_cast<char*>(smem)) + (size_t)kBHalfs * 2);
   const lds_f4 lo_part = (lds_f4)((lds_ptr)(reinterpret_cast<char*>(smem)) + (size_t)kBHalfs * 2 + kLinOutWBytes);
   {
-    const f32x4* gw = reinterpret_cast<const f32x4*>(reinterpret_cast<const char*>(a.w_out) + 32768);
+    const f32x4* gw = reinterpret_cast<const f32x4*>(a.w_out);
     for (int i = threadIdx.x; i < (int)(kLinOutWBytes / 16); i += 256) lo_w[i] = gw[i];
     __syncthreads();
   }
-#endif
   // The hand-over of a tile (2 KB per point, written by the per-view kernel in accumulator layout) is REQUESTED while the previous
   // tile's lin_out runs, straight into the residual block, which is dead from lin_out's publish on (round 2's attempt at this made the
   // allocator spill the block; with the accumulator accesses pinned it does not).  A tile starts by waiting for it: x16 + block 2's
@@ -1584,17 +1319,16 @@ __device__ __forceinline__ void field_post_body(const PostArgsN& a, const SaveAc
     for (int b = 0; b < 2; ++b) {
       const float* bias = bpost + 2 * kHidden * b;
       if constexpr (SAVE) save_block<false>(sv.X[3 + b], sv.bX[3 + b], pa.P, tile, wave, lane_here(), xs);
-      publish_gemm<DINER_HN_RING0, DINER_HN_EARLYP != 0, DINER_HN_OWN != 0>(a.w + (size_t)(2 * b) * kLayerHalfs, Bl, wave, lane, xs, ns, none, [&] {
+      publish_gemm<kHnRing0, false>(a.w + (size_t)(2 * b) * kLayerHalfs, Bl, wave, lane, xs, ns, none, [&] {
         set_bias(ns, bias, wave, lane_here() >> 4);
         pin_acc(xs);                              // the residual stream stays in registers across the fc_0 GEMM
       }, pf, 0);
       if (b == 0) tq.park(&s_tile2[par]);           // (the request went out at the top of the tile)
       if constexpr (SAVE) save_block<false>(sv.H[3 + b], sv.bH[3 + b], pa.P, tile, wave, lane_here(), ns);
       pin_acc(xs);
-      publish_gemm<DINER_HN_RING, DINER_HN_EARLYP != 0, DINER_HN_OWN != 0, false>(a.w + (size_t)(2 * b + 1) * kLayerHalfs, Bl, wave, lane, ns, xs, none,
+      publish_gemm<kHnRing, false, false>(a.w + (size_t)(2 * b + 1) * kLayerHalfs, Bl, wave, lane, ns, xs, none,
                                       [&] { add_bias(xs, bias + kHidden, wave, lane_here() >> 4); }, pf, 4);
     }
-#if DINER_HN_LINOUT_VALU
     pin_acc(xs);                                  // (else the block is copied to vector registers here and back for the reads below)
     if constexpr (SAVE) save_block<false>(sv.x_last, nullptr, pa.P, tile, wave, lane_here(), xs);
     // ---- lin_out on relu(x), fp32 on the vector ALU straight from the accumulators: a lane holds 4 features x 4 columns of each of its 8
@@ -1659,7 +1393,7 @@ __device__ __forceinline__ void field_post_body(const PostArgsN& a, const SaveAc
       }
       // x is dead from here on: the next tile's hand-over is requested now (its index was parked in LDS behind the first GEMM), ahead of
       // the sums over lanes and waves and of the barrier, whose wait the loads then fill (the top of a tile waited 5.7 k clocks for them)
-      const long long tile_nx = tq.take(tile, &s_tile2[par]);
+      const long long tile_nx = tq.take(&s_tile2[par]);
       if (tile_nx < n_tiles) request_handover(tile_nx);
 #pragma unroll
       for (int g = 0; g < kGroups; ++g) {
@@ -1683,41 +1417,6 @@ __device__ __forceinline__ void field_post_body(const PostArgsN& a, const SaveAc
       tile_next_v = tile_nx;
     }
     {
-#else
-    const int q_o = q, pt = lane & 15;
-    const bool wave_bad = false;
-    // ---- lin_out on relu(x): wave w produces the four outputs of column group w (its 16 points)
-    // (requesting its 32 weight fragments before the publish moves 4 k clocks from here into the publish and the next tile's
-    // hand-over load: measured, no net gain)
-    __syncthreads();
-    publish(Bl, wave, lane, xs);
-    __syncthreads();
-    tile_next_v = tq.take(tile, &s_tile2[par]);
-    if (tile_next_v < n_tiles) request_handover(tile_next_v);
-    pf.mark(9);
-    {
-      typedef const __attribute__((address_space(1))) h8* gh8;
-      gh8 wo = (gh8)(reinterpret_cast<const h8*>(a.w_out) + lane);
-      asm volatile("" : "+v"(wo));                // loop-invariant otherwise: 32 hoisted (and spilled) addresses
-      LdsB Bo = Bl;                               // column group `wave`: two fragments = 2 KB further on
-      Bo.base += wave * 2048;
-      Bo.opaque();
-      f32x4 o[4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) o[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int t = 0; t < 16; ++t) {
-        if ((t & 3) == 0) __builtin_amdgcn_sched_barrier(0);      // keep the operand loads from being hoisted in one burst
-        const h8 ah = wo[(t * 2 + 0) * 64], al = wo[(t * 2 + 1) * 64];
-        const h8 bh = *LdsB::at(Bo.chunk(t >> 2), t & 3, 0, 0), bl = *LdsB::at(Bo.chunk(t >> 2), t & 3, 0, 1);
-        DINER_HN_MFMA(o[t & 3], ah, bh);
-        DINER_HN_MFMA(o[(t + 1) & 3], al, bh);
-        DINER_HN_MFMA(o[(t + 2) & 3], ah, bl);
-      }
-      f32x4 res = ((o[0] + o[1]) + (o[2] + o[3])) * kInvScale;
-      asm volatile("" : "+v"(res));
-      pf.mark(10);
-#endif
       res += *reinterpret_cast<const f32x4*>(bpost + 4 * kHidden + 4 * q_o);     // lin_out bias kept at scale 1
       const long long t16 = tile * 4 + wave;
       const long long p = t16 * kPtsPerWave + pt;
@@ -1764,7 +1463,7 @@ constexpr size_t kLdsBytesPost8 = (size_t)2 * kB8Bytes + kLinOutWBytes + kLinOut
 static_assert(kLdsBytesPost8 <= 160 * 1024, "LDS of one CU");
 
 __global__ __launch_bounds__(512, 1) void k_field_post_h8(PostArgsN a) {
-  constexpr int R0 = DINER_H8_RING0;
+  constexpr int R0 = kH8Ring0;
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
@@ -1776,7 +1475,7 @@ __global__ __launch_bounds__(512, 1) void k_field_post_h8(PostArgsN a) {
   const lds_f4 lo_w = (lds_f4)((lds_ptr)(reinterpret_cast<char*>(smem)) + (size_t)2 * kB8Bytes);
   const lds_f4 lo_part = (lds_f4)((lds_ptr)(reinterpret_cast<char*>(smem)) + (size_t)2 * kB8Bytes + kLinOutWBytes);
   {
-    const f32x4* gw = reinterpret_cast<const f32x4*>(reinterpret_cast<const char*>(a.w_out) + 32768);
+    const f32x4* gw = reinterpret_cast<const f32x4*>(a.w_out);
     for (int i = threadIdx.x; i < (int)(kLinOutWBytes / 16); i += 512) lo_w[i] = gw[i];
   }
   Prof pf;
@@ -1819,7 +1518,7 @@ __global__ __launch_bounds__(512, 1) void k_field_post_h8(PostArgsN a) {
     for (int b = 0; b < 2; ++b) {
       const float* bias = bpost + 2 * kHidden * b;
       pf.mark(0);
-      publish8<true>(Bwr, wave, xs);
+      publish8(Bwr, wave, xs);
       pf.mark(1);
       __syncthreads();
       pf.mark(2);
@@ -1827,10 +1526,10 @@ __global__ __launch_bounds__(512, 1) void k_field_post_h8(PostArgsN a) {
         f32x4 ns[kS8][kGroups];
         set_bias8(ns, bias, wave, q);
         NoSide8 none;
-        gemm8<16, R0, true>(a.w8 + (size_t)(2 * b) * kLayerHalfs8, Bwr, wave, lane, ns, none);
+        gemm8<16, R0>(a.w8 + (size_t)(2 * b) * kLayerHalfs8, Bwr, wave, lane, ns, none);
         pf.mark(3);
         if (b == 0) tq.park(&s_tile2[par]);         // (the request went out at the top of the tile)
-        publish8<true>(Brd, wave, ns);
+        publish8(Brd, wave, ns);
         pf.mark(5);
       }
       __syncthreads();
@@ -1845,7 +1544,7 @@ __global__ __launch_bounds__(512, 1) void k_field_post_h8(PostArgsN a) {
         }
         pin_acc8(xs);
         NoSide8 none;
-        gemm8<16, R0, true>(a.w8 + (size_t)(2 * b + 1) * kLayerHalfs8, Brd, wave, lane, xs, none);
+        gemm8<16, R0>(a.w8 + (size_t)(2 * b + 1) * kLayerHalfs8, Brd, wave, lane, xs, none);
       }
       pf.mark(7);
     }
@@ -1899,7 +1598,7 @@ __global__ __launch_bounds__(512, 1) void k_field_post_h8(PostArgsN a) {
         }
       }
       // x is dead from here on: the next tile's hand-over is requested now (its index was parked in LDS behind the first GEMM)
-      const long long tile_nx = tq.take(tile, &s_tile2[par]);
+      const long long tile_nx = tq.take(&s_tile2[par]);
       if (tile_nx < n_tiles) request_handover(tile_nx);
 #pragma unroll
       for (int g = 0; g < kGroups; ++g) {
@@ -1966,16 +1665,6 @@ __global__ void k_pack_layer_h3n(const float* __restrict__ W, int rows, int cols
   }
 }
 
-// lin_out fragments [t 16][hl 2][lane 64][8]: Wout[lane&15][32 t + 16 (j>>2) + 4 (lane>>4) + (j&3)] * scale, rows >= d_out zero
-__global__ void k_pack_lin_out_h3n(const float* __restrict__ W, int rows, int cols, float scale, _Float16* __restrict__ dst) {
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < 16384; i += gridDim.x * blockDim.x) {
-    const int j = i & 7, lane = (i >> 3) & 63, hl = (i >> 9) & 1, t = i >> 10;
-    const int row = lane & 15, col = 32 * t + 16 * (j >> 2) + 4 * (lane >> 4) + (j & 3);
-    const float w = (row < rows && col < cols) ? W[(size_t)row * cols + col] * scale : 0.0f;
-    const _Float16 h = (_Float16)w;
-    dst[i] = hl ? (_Float16)(w - (float)h) : h;
-  }
-}
 // lin_out for the vector ALU: [wave 4][mo 8][q 4][o 4][j 4] = Wout[o][128 wave + 16 mo + 4 q + j] * scale (the accumulators carry x16)
 __global__ void k_pack_lin_out_valu(const float* __restrict__ W, int rows, int cols, float scale, float* __restrict__ dst) {
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < 2048; i += gridDim.x * blockDim.x) {
@@ -2003,21 +1692,19 @@ struct WeightLayout {
   static constexpr size_t oLinIn8 = oPost4 + kPost4, oPerView8 = oLinIn8 + kLinIn8, oPost8 = oPerView8 + kPerView8;
   static constexpr size_t kTotal = oPost8 + kPost8;
 };
-// the lin_out buffer (hn_w_out): the MFMA fragments [t 16][hl 2][lane 64][8] halfs, behind them the fp32 pack of the vector-ALU lin_out
-constexpr size_t kLinOutFragHalfs = 16 * 2 * 64 * 8;
 
-// w: see WeightLayout; w_lin_out: lin_out fragments + fp32 pack; b_pre: 7 x 512 (x16); b_post: 4 x 512 (x16) + the lin_out bias at
+// w: see WeightLayout; w_lin_out: the fp32 pack of the vector-ALU lin_out (k_pack_lin_out_valu); b_pre: 7 x 512 (x16); b_post: 4 x 512 (x16) + the lin_out bias at
 // scale 1 (padded to 16) + block 2's fc_1 bias (x16).  The caller frees whatever was allocated when this fails.
-int h3n_alloc(_Float16** w, _Float16** w_lin_out, float** b_pre, float** b_post) {
+int h3n_alloc(_Float16** w, float** w_lin_out, float** b_pre, float** b_post) {
   DINER_HIP_OK(hipMalloc(w, WeightLayout::kTotal * sizeof(_Float16)));
-  DINER_HIP_OK(hipMalloc(w_lin_out, kLinOutFragHalfs * sizeof(_Float16) + h3n::kLinOutWBytes));
+  DINER_HIP_OK(hipMalloc(w_lin_out, h3n::kLinOutWBytes));
   DINER_HIP_OK(hipMalloc(b_pre, 7 * kHidden * sizeof(float)));
   DINER_HIP_OK(hipMalloc(b_post, (5 * kHidden + 16) * sizeof(float)));
   return 0;
 }
-// train_only: the four-wave layouts, the lin_out packs and the biases (what k_train_fwd_pre / k_train_fwd_post read); the eight-wave
+// train_only: the four-wave layouts, the lin_out pack and the biases (what k_train_fwd_pre / k_train_fwd_post read); the eight-wave
 // layouts keep their old contents
-int h3n_pack(const DinerMlpParams* p, hipStream_t stream, _Float16* w, _Float16* w_lin_out, float* b_pre, float* b_post, bool train_only) {
+int h3n_pack(const DinerMlpParams* p, hipStream_t stream, _Float16* w, float* w_lin_out, float* b_pre, float* b_post, bool train_only) {
   using namespace h3n;
   typedef WeightLayout L;
   auto bias = [&](const float* b, int n, int n_pad, float scale, float* dst) {
@@ -2036,9 +1723,7 @@ int h3n_pack(const DinerMlpParams* p, hipStream_t stream, _Float16* w, _Float16*
   }
   bias(p->lin_out_b, 4, 16, 1.0f, b_post + 4 * kHidden);
   bias(p->fc1_b[2], kHidden, kHidden, kScale, b_post + 4 * kHidden + 16);
-  hipLaunchKernelGGL(k_pack_lin_out_h3n, dim3(64), dim3(256), 0, stream, p->lin_out_w, 4, kHidden, kScale, w_lin_out);
-  hipLaunchKernelGGL(k_pack_lin_out_valu, dim3(8), dim3(256), 0, stream, p->lin_out_w, 4, kHidden, kInvScale,
-                     reinterpret_cast<float*>(w_lin_out + kLinOutFragHalfs));
+  hipLaunchKernelGGL(k_pack_lin_out_valu, dim3(8), dim3(256), 0, stream, p->lin_out_w, 4, kHidden, kInvScale, w_lin_out);
   // fc_0, fc_1 of blocks [b0, b1) with `kernel`, one layer of `layer_halfs` behind the other from dst on
   auto blocks = [&](void (*kernel)(const float*, int, int, int, float, _Float16*), int b0, int b1, size_t layer_halfs, _Float16* dst) {
     for (int b = b0; b < b1; ++b)
@@ -2104,8 +1789,8 @@ void h3n_launch_pre(const SceneDev& sc, const FieldArgs& fa, const _Float16* w, 
 #endif
 }
 
-// w: see WeightLayout; w_lin_out: the lin_out fragments + fp32 pack
-void h3n_launch_post(const PostArgs& pa, const _Float16* w, const _Float16* w_lin_out, int grid, bool split, unsigned* tile_counter,
+// w: see WeightLayout; w_lin_out: the fp32 pack of lin_out
+void h3n_launch_post(const PostArgs& pa, const _Float16* w, const float* w_lin_out, int grid, bool split, unsigned* tile_counter,
                      hipStream_t stream, const SaveActs* sv) {
   const long long n_t16 = (pa.P + kPtsPerWave - 1) / kPtsPerWave;
   h3n::PostArgsN a{pa, w + WeightLayout::oPost4, w + WeightLayout::oPost8, w_lin_out, nullptr, tile_counter, h3n::QueueMap::make((n_t16 + 3) / 4, 0, false)};

@@ -279,11 +279,6 @@ constexpr int XM = 128, XN = 128, XK = 32;
 constexpr int kPlaneElems = 2 * 2 * 128 * 8;          // bf16 elements of one plane of one operand tile (8 KB)
 
 __device__ __forceinline__ void split3(const float (&v)[8], bf8& p0, bf8& p1, bf8& p2) {
-#ifdef DINER_BF16X6_NOSPLIT      // ablation (wrong results): what the on-the-fly split costs
-#pragma unroll
-  for (int j = 0; j < 8; ++j) p0[j] = p1[j] = p2[j] = (__bf16)v[j];
-  return;
-#endif
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
     const __bf16 a0 = (__bf16)v[j];

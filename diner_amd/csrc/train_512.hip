@@ -22,17 +22,17 @@ struct Run512 {
 };
 
 __device__ __forceinline__ void lin512_part(const Lin512Args& a, int shape, int bid, int nblk) {
-  if (shape == kShape64) lin512_body<DINER_L512_RING, 2, 1>(a, bid, nblk);
-  else if (shape == kShape32) lin512_body<DINER_L512_RING, 1, 1>(a, bid, nblk);
-  else lin512_body<DINER_L512_RING, 1, 2>(a, bid, nblk);
+  if (shape == kShape64) lin512_body<kL512Ring, 2, 1>(a, bid, nblk);
+  else if (shape == kShape32) lin512_body<kL512Ring, 1, 1>(a, bid, nblk);
+  else lin512_body<kL512Ring, 1, 2>(a, bid, nblk);
 }
 
 // The forward products in the f16x3 arithmetic (lin512_body<.., AR = 1>: half the MFMAs of bf16x6): the same parts, no weight gradient
 __device__ __forceinline__ void lin512_part_f16(const Lin512Args& a, int shape, int bid, int nblk) {
-  if (shape == kShape128) lin512_body<DINER_L512_RING, 4, 1, 1>(a, bid, nblk);
-  else if (shape == kShape64) lin512_body<DINER_L512_RING, 2, 1, 1>(a, bid, nblk);
-  else if (shape == kShape32) lin512_body<DINER_L512_RING, 1, 1, 1>(a, bid, nblk);
-  else lin512_body<DINER_L512_RING, 1, 2, 1>(a, bid, nblk);
+  if (shape == kShape128) lin512_body<kL512Ring, 4, 1, 1>(a, bid, nblk);
+  else if (shape == kShape64) lin512_body<kL512Ring, 2, 1, 1>(a, bid, nblk);
+  else if (shape == kShape32) lin512_body<kL512Ring, 1, 1, 1>(a, bid, nblk);
+  else lin512_body<kL512Ring, 1, 2, 1>(a, bid, nblk);
 }
 __global__ __launch_bounds__(256, 1) void k_fwd512_f16x3(Run512 r) {
   int b = blockIdx.x;
@@ -42,9 +42,9 @@ __global__ __launch_bounds__(256, 1) void k_fwd512_f16x3(Run512 r) {
 // round 5 experiment (DINER_L512_W2=1): the forward products with TWO workgroups per CU (two waves per SIMD, 256 registers each): 64- and
 // 32-row tiles only (128 accumulator registers), 66 KB of LDS per workgroup -- one workgroup's epilogue and staging stalls under the other's MFMAs
 __device__ __forceinline__ void lin512_part_f16_w2(const Lin512Args& a, int shape, int bid, int nblk) {
-  if (shape == kShape64) lin512_body<DINER_L512_RING, 2, 1, 1>(a, bid, nblk);
-  else if (shape == kShape32) lin512_body<DINER_L512_RING, 1, 1, 1>(a, bid, nblk);
-  else lin512_body<DINER_L512_RING, 1, 2, 1>(a, bid, nblk);
+  if (shape == kShape64) lin512_body<kL512Ring, 2, 1, 1>(a, bid, nblk);
+  else if (shape == kShape32) lin512_body<kL512Ring, 1, 1, 1>(a, bid, nblk);
+  else lin512_body<kL512Ring, 1, 2, 1>(a, bid, nblk);
 }
 __global__ __launch_bounds__(256, 2) void k_fwd512_f16x3_w2(Run512 r) {
   int b = blockIdx.x;
@@ -73,7 +73,7 @@ __global__ __launch_bounds__(256, 1) void k_run512(Run512 r) {
 // tiles on every CU, AR = 1 (f16x3) or 0 (its bf16x6 twin)
 template <int AR>
 __global__ __launch_bounds__(256, 1) void k_lin512_rows(Lin512Args a, int nblk) {
-  lin512_body<DINER_L512_RING, 1, 1, AR, 4, true>(a, blockIdx.x, nblk);
+  lin512_body<kL512Ring, 1, 1, AR, 4, true>(a, blockIdx.x, nblk);
 }
 // round 5: the data gradient of an f16x3 launch on eight waves (lin512_body<.., NW = 8>: two waves per SIMD, 64 features and half the staging
 // rows per wave; the shared 32-row shape of a plan runs as plain 32-row tiles -- its second workgroups find no tile)
@@ -83,9 +83,9 @@ __global__ __launch_bounds__(512, 1) void k_dgrad512_w8(Run512 r) {
   if (i) b -= r.n[0];
   const Lin512Args& a = r.part[i];
   const int shape = r.shape[i], nblk = r.n[i];
-  if (shape == kShape128) lin512_body<DINER_L512_RING, 4, 1, 1, 8>(a, b, nblk);
-  else if (shape == kShape64) lin512_body<DINER_L512_RING, 2, 1, 1, 8>(a, b, nblk);
-  else lin512_body<DINER_L512_RING, 1, 1, 1, 8>(a, b, nblk);
+  if (shape == kShape128) lin512_body<kL512Ring, 4, 1, 1, 8>(a, b, nblk);
+  else if (shape == kShape64) lin512_body<kL512Ring, 2, 1, 1, 8>(a, b, nblk);
+  else lin512_body<kL512Ring, 1, 1, 1, 8>(a, b, nblk);
 }
 // round 5: the weight gradient of an f16x3 launch on eight waves (wgrad512_body_w8), a launch of its own behind the data gradient's
 __global__ __launch_bounds__(512, 1) void k_wgrad512_w8(Wgrad512Args a) { wgrad512_body_w8(a, blockIdx.x); }

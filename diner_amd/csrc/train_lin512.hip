@@ -33,10 +33,7 @@ constexpr float kF16Scale = 16.0f, kF16InvScale = 1.0f / 16.0f;      // f16x3 ar
 
 constexpr int kStepsPerSlab = 8;                // k16 steps per staged slab (128 contraction indices)
 constexpr int kSlabs = 512 / (16 * kStepsPerSlab);
-#ifndef DINER_L512_STEP_PAD       // bytes between the k16 steps of a slab buffer beyond their fragments, see lin512_body (staging writes)
-#define DINER_L512_STEP_PAD 32
-#endif
-constexpr int kStepPad = DINER_L512_STEP_PAD;
+constexpr int kStepPad = 32;      // bytes between the k16 steps of a slab buffer beyond their fragments, see lin512_body (staging writes)
 constexpr size_t kLdsBytes512 = (size_t)2 * kStepsPerSlab * (2 * 3 * 1024 + kStepPad);  // two slab buffers of [step 8][row half CT][plane 3] 1 KB fragments: 96 KB at CT = 2
 constexpr size_t kLdsBytes512F16W2 = (size_t)2 * kStepsPerSlab * (2 * 2 * 1024 + kStepPad);  // f16x3 at CT = 2: 66 KB (two workgroups per CU, experiment)
 constexpr size_t kLdsBytes512F16 = (size_t)2 * kStepsPerSlab * (4 * 2 * 1024 + kStepPad);  // f16x3 (two planes) at CT = 4 (128-row tiles): 128 KB
@@ -128,12 +125,8 @@ __global__ void k_pack_w512_many(PackMany w, char* __restrict__ base, int* __res
   pack_w512(w.W[blockIdx.y], blockIdx.z, reinterpret_cast<__bf16*>(base + (size_t)(13 * blockIdx.z + blockIdx.y) * kL512PackBytes), wbad);
 }
 
-#ifndef DINER_L512_RING
-#define DINER_L512_RING 2
-#endif
-#ifndef DINER_L512_EPI_PD      // groups of tensor-term requests in flight in the epilogue of the 128-row shape (1 = round 6's first version)
-#define DINER_L512_EPI_PD 1
-#endif
+constexpr int kL512Ring = 2;       // weight ring depth in k16 steps (lin512_body's R)
+constexpr int kL512EpiPd = 1;      // groups of tensor-term requests in flight in the epilogue of the 128-row shape
 // -DDINER_L512_PROF (measurement build, tools/prof_l512.sh): shader clocks per wave summed over the launches since the last read --
 // [0] whole tile loop, [1] MFMA slab loops without their barriers, [2] slab barriers, [3] epilogues, [4] tiles, [5] waves, [6] prologue
 #ifdef DINER_L512_PROF
@@ -168,11 +161,7 @@ __device__ __forceinline__ void lin512_body(const Lin512Args& a, const int bid, 
   // fragment are 512 bytes apart by the MFMA layout); the fragment reads stay 1 KB contiguous per instruction.
   constexpr int kStepBytes = CT * NP * 1024 + kStepPad, kSlabBytes = kStepsPerSlab * kStepBytes;
   constexpr int NRT = 16 / (FH * NW), NF = NP * NRT;         // MFMA row (= feature) tiles per wave, weight fragments per k16 step
-#ifdef DINER_L512_OLD_EPI      // A/B build: the direct epilogue for every shape
-  constexpr bool kLdsEpi = false;
-#else
   constexpr bool kLdsEpi = CT == 4 && NW == 4 && FH == 1 && AR == 1;      // the epilogue leaves through LDS (below)
-#endif
   if (a.gate && *a.gate == 0) return;                        // fall-back launch of an f16x3 product that stayed in range: nothing to do
   if (a.gate2 && *a.gate2 == 0) return;
   long long Mrows = a.M;
@@ -292,9 +281,6 @@ __device__ __forceinline__ void lin512_body(const Lin512Args& a, const int bid, 
   const unsigned woff = lane * 16;
   bf8 wr[R][NF];
   auto load_w = [&](bf8 (&dst)[NF], int step, int first, int count) {        // fragments [first, first + count) of step (0..31)
-#ifdef DINER_L512_ABL_W       // ablation (wrong results): a 24 KB weight working set per wave, i.e. no L2 latency on the weight stream
-    step &= 1;
-#endif
     gptr p = (step >= 32 ? wbase2 : wbase) + (size_t)(step & 31) * (4 * NP) * 1024;
     asm volatile("" : "+s"(p));                  // scalar base + per-lane 32-bit offset + immediate: no address registers per load
 #pragma unroll
@@ -377,7 +363,6 @@ __device__ __forceinline__ void lin512_body(const Lin512Args& a, const int bid, 
           // // (which steps makes no measurable difference)
           constexpr int g0 = AR == 1 ? NG - 3 : (CT == 2 ? 8 : 2);
           constexpr int g1 = 3;                                // CT = 4 (16 requests per slab): a second request per step, s + 8, in groups 3..5
-#ifndef DINER_L512_ABL_X
           if constexpr (s < NQ && g == g0) stash_half(s, 0);
           if constexpr (s < NQ && g == g0 + 1) stash_half(s, 1);
           if constexpr (s < NQ && g == g0 + 2) {
@@ -390,7 +375,6 @@ __device__ __forceinline__ void lin512_body(const Lin512Args& a, const int bid, 
             stash_write(buf ^ 1, s + 8);
             request_one(s + 8, t2, s2);
           }
-#endif
           const bf8 b = bb[kRollB ? 0 : (s & 1)][ct][ib];
 #pragma unroll
           for (int rt = 0; rt < NRT; ++rt) {
@@ -471,10 +455,10 @@ __device__ __forceinline__ void lin512_body(const Lin512Args& a, const int bid, 
         constexpr bool BITS = decltype(BITSc)::value, GEN = decltype(GENc)::value;
         const __amdgpu_buffer_rsrc_t rs_p = rsrc(PK == 1 ? a.resid : a.Y);
         const __amdgpu_buffer_rsrc_t rs_mb = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned*>((BITS ? a.maskbits : (const unsigned*)a.Y) + (size_t)row0 * 16), 0, left * 64, 0x00020000);
-        // a ring of PD groups of term requests in flight (DINER_L512_EPI_PD).  Measured (profiles/r06_train_wgrad_phase_timer.txt): 2 groups ahead
+        // a ring of PD groups of term requests in flight (kL512EpiPd).  Measured (profiles/r06_train_wgrad_phase_timer.txt): 2 groups ahead
         // change nothing (accumulating epilogue 22.3 k clocks per tile, step 120.9 ms against 120.9), 3 cost 70 spill instructions and 1 ms:
-        // the epilogue is not waiting for latency any more.  Default 1.
-        constexpr int PD = (PK != 0 || BITS) ? DINER_L512_EPI_PD : 1;
+        // the epilogue is not waiting for latency any more.
+        constexpr int PD = (PK != 0 || BITS) ? kL512EpiPd : 1;
         f32x4 pre[PD][GN];
         unsigned mb[PD][GN];
         auto issue = [&](f32x4 (&tp)[GN], unsigned (&tm)[GN], int g) {

@@ -323,6 +323,26 @@ def test_no_spill_code_in_the_training_kernels(tmp_path):
     assert not any("v_mfma_f32_32x32x16_bf16" in l for l in found["k_run512_f16x3"])
 
 
+def test_kernel_sources_have_one_code_path():
+    """The kernel sources compile one way: the only macros a preprocessor conditional tests are the two phase timers (measurement builds with
+    tools behind them: tools/prof_phases.sh, tools/prof_l512.py) and __HIPCC__ (common.hpp, shared with the host compiler).  Ablation arms,
+    lost experiments and tunables behind `#ifndef X / #define X n` were removed once (profiles/ablation_arms_removed.txt); a new one fails
+    here.  A tunable is a constexpr beside the comment with its measurement; an experiment that lost goes to tools/ubench/*.hip.txt."""
+    allowed = {"DINER_HN_PROF", "DINER_L512_PROF", "__HIPCC__"}
+    csrc = os.path.join(ROOT, "diner_amd", "csrc")
+    found = {}
+    for name in sorted(os.listdir(csrc)):
+        with open(os.path.join(csrc, name)) as f:
+            for no, line in enumerate(f, 1):
+                m = re.match(r"\s*#\s*(if|ifdef|ifndef|elif)\b(.*)", line)
+                if m:
+                    tested = set(re.findall(r"[A-Za-z_]\w*", m.group(2).split("//")[0])) - {"defined"}
+                    assert tested, f"{name}:{no}: conditional on a constant"
+                    for macro in tested - allowed:
+                        found.setdefault(macro, f"{name}:{no}")
+    assert not found, f"compile-time switches in the kernel sources: {found}"
+
+
 def test_bench_line_contract():
     """The committed bench line (profiles/, produced by `python bench.py` on an MI355X) carries every field of the
     driver's contract, the roofline object and the CPU baseline object."""
