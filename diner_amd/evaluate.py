@@ -24,6 +24,9 @@ GT_SUFFIX = "-gt.png"
 REF_SUFFIX = "-ref.png"
 DEPTH_SUFFIX = "-depth.png"
 ALPHA_SUFFIX = "-alpha.png"
+ZDEPTH_SUFFIX = "-zdepth.png"
+NORMAL_SUFFIX = "-normal.png"
+PLY_SUFFIX = ".ply"
 AVERAGE_SCORE_FILENAME = "average_scores.json"
 REPORT_DETAIL_FILENAME = "detailed_report.json"
 EXAMPLE_PLOT_FILENAME = "examples.png"
@@ -45,13 +48,18 @@ def _hip_device(device):
 
 
 @torch.no_grad()
-def write_prediction_folder(nerf, renderer, batches, outdir, znear, zfar, ray_batch_size=8192, write_alpha=False, cull_empty=False):
+def write_prediction_folder(nerf, renderer, batches, outdir, znear, zfar, ray_batch_size=8192, write_alpha=False, cull_empty=False,
+                            write_geometry=False):
     """Render every target view of `batches` (collated sample dicts of diner_amd.datasets) with `nerf` / `renderer` and write
     <sample_name>{-pred,-depth,-ref,-gt}.png into `outdir`: the render and its colour-mapped depth, the source views side by side and
     the target, each quantised as save_image does.  Returns {"sample_name": [...], "l1", "l2", "psnr", "ssim": float64 (N,)} -- the
     scores of the renders against their targets, computed on the device from the fp32 tensors (not from the files).  write_alpha: also
     <sample_name>-alpha.png, the render's opacity (the matte) as an 8-bit grey image, quantised like the others.
-    cull_empty: passed to predict_image (render only the rays the depth maps put a surface on; an approximation, off by default)."""
+    cull_empty: passed to predict_image (render only the rays the depth maps put a surface on; an approximation, off by default).
+    write_geometry (off by default): render with predict_geometry instead -- the same colour, depth and opacity bit for bit -- and also
+    write <sample_name>-zdepth.png (the camera-z depth of the surface through the depth colour map), <sample_name>-normal.png (the
+    camera-frame normals as n * 0.5 + 0.5, quantised like the others) and <sample_name>.ply (diner_amd.geometry.point_cloud at its
+    defaults: points, colours and world-frame normals).  cull_empty does not combine with it and is ignored then."""
     from .datasets import encode_args
     from .imageio import depth_to_uint8, gray_to_uint8, to_uint8
     from .metrics import KEYS, image_metrics
@@ -63,8 +71,15 @@ def write_prediction_folder(nerf, renderer, batches, outdir, znear, zfar, ray_ba
         nerf.encode(**encode_args(batch, dev))
         gt = batch["target_rgb"].to(dev)
         H, W = gt.shape[-2:]
-        rgb, depth, *alpha = predict_image(nerf, renderer, batch["target_extrinsics"].to(dev), batch["target_intrinsics"].to(dev), W, H,
-                                           znear, zfar, ray_batch_size=ray_batch_size, return_alpha=write_alpha, cull_empty=cull_empty)
+        if write_geometry:
+            from .geometry import point_cloud, write_ply
+            from .render import predict_geometry
+            geo = predict_geometry(nerf, renderer, batch["target_extrinsics"].to(dev), batch["target_intrinsics"].to(dev), W, H, znear,
+                                   zfar, ray_batch_size=ray_batch_size)
+            rgb, depth, alpha = geo["rgb"], geo["depth"], [geo["alpha"]]
+        else:
+            rgb, depth, *alpha = predict_image(nerf, renderer, batch["target_extrinsics"].to(dev), batch["target_intrinsics"].to(dev), W, H,
+                                               znear, zfar, ray_batch_size=ray_batch_size, return_alpha=write_alpha, cull_empty=cull_empty)
         src = batch["src_rgbs"].to(dev)
         for i, stem in enumerate(batch["sample_name"]):
             write_png(os.path.join(outdir, stem + PRED_SUFFIX), to_uint8(rgb[i]))
@@ -73,6 +88,10 @@ def write_prediction_folder(nerf, renderer, batches, outdir, znear, zfar, ray_ba
             write_png(os.path.join(outdir, stem + GT_SUFFIX), to_uint8(gt[i]))
             if write_alpha:
                 write_png(os.path.join(outdir, stem + ALPHA_SUFFIX), gray_to_uint8(alpha[0][i]))
+            if write_geometry:
+                write_png(os.path.join(outdir, stem + ZDEPTH_SUFFIX), depth_to_uint8(geo["zdepth"][i]))
+                write_png(os.path.join(outdir, stem + NORMAL_SUFFIX), to_uint8(geo["normals"][i] * 0.5 + 0.5))
+                write_ply(os.path.join(outdir, stem + PLY_SUFFIX), *point_cloud({k: v[i:i + 1] for k, v in geo.items()}))
             names.append(stem)
         s = image_metrics(rgb, gt)
         for k in KEYS:

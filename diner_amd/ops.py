@@ -689,6 +689,96 @@ def depth2normal(dmap, K):
     return out
 
 
+RayGeometry = collections.namedtuple("RayGeometry", "depth_median median_idx depth_mean zdepth points")
+POINT_DEPTH = {"median": 0, "mean": 1}
+
+
+def _check_ray_geometry_args(weights, z, rays, cam_fwd, quantile, alpha_min, point_depth):
+    """The argument checks of ray_geometry that need no device: -> (NR, K, cam_fwd as three host floats or None)."""
+    if point_depth not in POINT_DEPTH:
+        raise ValueError(f"diner_amd: ray_geometry point_depth must be 'median' or 'mean', got {point_depth!r}")
+    if not 0.0 < float(quantile) <= 1.0:
+        raise ValueError(f"diner_amd: ray_geometry quantile {quantile} outside (0, 1]")
+    if not float(alpha_min) >= 0.0:
+        raise ValueError(f"diner_amd: ray_geometry alpha_min {alpha_min} must be >= 0")
+    if z.dim() != 2 or tuple(weights.shape) != tuple(z.shape) or tuple(rays.shape) != (z.shape[0], 8):
+        raise ValueError(f"diner_amd: ray_geometry expects weights (NR,K), z (NR,K), rays (NR,8), got {tuple(weights.shape)}, "
+                         f"{tuple(z.shape)}, {tuple(rays.shape)}")
+    NR, K = int(z.shape[0]), int(z.shape[1])
+    if not 1 <= K <= 1024:
+        raise ValueError(f"diner_amd: ray_geometry K = {K} outside [1, 1024]")
+    fwd = None
+    if cam_fwd is not None:
+        fwd = torch.as_tensor(cam_fwd).detach().to("cpu", torch.float32).reshape(-1)
+        if fwd.numel() != 3:
+            raise ValueError(f"diner_amd: ray_geometry cam_fwd holds {fwd.numel()} values, expected 3 (row 2 of the world->camera rotation)")
+        fwd = (C.c_float * 3)(*fwd.tolist())
+    return NR, K, fwd
+
+
+def ray_geometry(weights, z, rays, cam_fwd=None, quantile=0.5, alpha_min=1e-3, point_depth="median"):
+    """Geometry of rendered rays (diner_ray_geometry_f32): weights (NR,K) as composite / render return them with want_weights, the z
+    (NR,K) and rays (NR,8) they were given -> RayGeometry(depth_median (NR), median_idx (NR) int32, depth_mean (NR), zdepth (NR) | None,
+    points (NR,3)).  With c_k the running sum of the weights in sample order and A = c_{K-1}: a ray is valid iff A > alpha_min;
+    median_idx is the first k with c_k >= quantile A, depth_median = z[median_idx], depth_mean = sum_k w_k z_k / A; points = o + t d with
+    t the median (point_depth "median") or the mean ("mean"); zdepth = t (d . cam_fwd), the camera-z depth of the point, needs cam_fwd
+    (3 values, host or device: row 2 of the target's world->camera rotation) and is None without it.  An invalid ray gets 0 in every
+    float output and -1 in median_idx.  No gradient flows through any output."""
+    NR, K, fwd = _check_ray_geometry_args(weights, z, rays, cam_fwd, quantile, alpha_min, point_depth)
+    _require_hip(weights, z, rays)
+    weights, z, rays = _f32c(weights), _f32c(z), _f32c(rays)
+    dev = z.device
+    d_med = torch.empty(NR, device=dev, dtype=torch.float32)
+    idx = torch.empty(NR, device=dev, dtype=torch.int32)
+    d_mean = torch.empty(NR, device=dev, dtype=torch.float32)
+    zd = torch.empty(NR, device=dev, dtype=torch.float32) if fwd is not None else None
+    pts = torch.empty(NR, 3, device=dev, dtype=torch.float32)
+    if NR > 0:
+        with torch.cuda.device(dev):
+            _lib.check(lib.diner_ray_geometry_f32(_ptr(weights), _ptr(z), _ptr(rays), NR, K, float(quantile), float(alpha_min), fwd,
+                                                  POINT_DEPTH[point_depth], _ptr(d_med), _ptr(idx), _ptr(d_mean), _ptr(zd), _ptr(pts),
+                                                  _stream()))
+    return RayGeometry(d_med, idx, d_mean, zd, pts)
+
+
+def _check_depth_consistency_args(depth, intrinsics, extrinsics, px_thr, rel_thr):
+    """The argument checks of depth_consistency that need no device: -> (N, H, W, host intrinsics, host extrinsics)."""
+    if depth.dim() == 4 and depth.shape[1] == 1:
+        depth = depth[:, 0]
+    if depth.dim() != 3:
+        raise ValueError(f"diner_amd: depth_consistency expects depth (N,H,W) or (N,1,H,W), got {tuple(depth.shape)}")
+    N, H, W = (int(v) for v in depth.shape)
+    if not 2 <= N <= _lib.MAX_VIEWS:
+        raise ValueError(f"diner_amd: depth_consistency takes 2 .. {_lib.MAX_VIEWS} views, got {N}")
+    if tuple(intrinsics.shape) != (N, 3, 3) or tuple(extrinsics.shape) != (N, 4, 4):
+        raise ValueError(f"diner_amd: depth_consistency expects intrinsics ({N},3,3) and extrinsics ({N},4,4), got "
+                         f"{tuple(intrinsics.shape)}, {tuple(extrinsics.shape)}")
+    if not (float(px_thr) >= 0.0 and float(rel_thr) >= 0.0):
+        raise ValueError(f"diner_amd: depth_consistency thresholds must be >= 0, got {px_thr}, {rel_thr}")
+    Km = intrinsics.detach().to("cpu", torch.float32).contiguous()
+    E = extrinsics.detach().to("cpu", torch.float32).contiguous()
+    return N, H, W, Km, E
+
+
+def depth_consistency(depth, intrinsics, extrinsics, px_thr=1.0, rel_thr=0.01):
+    """Cross-view consistency of N z-depth maps (diner_depth_consistency_f32): depth (N,H,W) or (N,1,H,W) with 0 = no surface,
+    intrinsics (N,3,3), extrinsics (N,4,4) world->camera (read on the host), 2 <= N <= 16 -> count (N,H,W) int32, depth_avg (N,H,W).
+    Every pixel of every view is carried into each other view at its depth, that view's depth is sampled there (bilinear; all four
+    taps inside and non-zero) and carried back: the pair agrees iff the pixel returns within px_thr pixels and its depth within rel_thr
+    relative.  count = the agreeing views, depth_avg = the mean of the pixel's depth and the agreeing views' returned depths; both 0
+    where the pixel has no surface.  Pixel centres at +0.5, as gen_rays and depth2normal."""
+    N, H, W, Km, E = _check_depth_consistency_args(depth, intrinsics, extrinsics, px_thr, rel_thr)
+    _require_hip(depth)
+    depth = _f32c(depth).reshape(N, H, W)
+    count = torch.empty(N, H, W, device=depth.device, dtype=torch.int32)
+    avg = torch.empty(N, H, W, device=depth.device, dtype=torch.float32)
+    if H * W > 0:
+        with torch.cuda.device(depth.device):
+            _lib.check(lib.diner_depth_consistency_f32(_ptr(depth), Km.data_ptr(), E.data_ptr(), N, H, W, float(px_thr), float(rel_thr),
+                                                       _ptr(count), _ptr(avg), _stream()))
+    return count, avg
+
+
 def gen_rays(extrinsics, intrinsics, W, H, z_near, z_far, device, ray0=0, n_rays=None):
     """Reference src/util/cam_geometry.py:5-48 on the device: rays [ray0, ray0+n_rays) of each camera's row-major
     (H, W) list -> (B, n_rays, 8).  Camera tensors may live anywhere (they are read on the host: B x 27 floats)."""

@@ -232,3 +232,52 @@ def predict_image(nerf, renderer, target_extrinsics, target_intrinsics, W, H, zn
     if return_alpha:
         return full[:, :3].contiguous(), full[:, 3:4].contiguous(), full[:, 4:5].contiguous()
     return full[:, :3].contiguous(), full[:, 3:4].contiguous()
+
+
+GEOMETRY_MAPS = ("depth", "alpha", "depth_var", "depth_median", "depth_mean", "zdepth")
+
+
+@torch.no_grad()
+def predict_geometry(nerf, renderer, target_extrinsics, target_intrinsics, W, H, znear, zfar, ray_batch_size=8192, seed=None,
+                     quantile=0.5, alpha_min=1e-3, point_depth="median"):
+    """predict_image with the geometry of the rendered surface (one process; HIP devices only).  Same rays, ray order, batches and frame
+    noise key as predict_image: rgb (SB,3,H,W), depth and alpha (SB,1,H,W) are predict_image(return_alpha=True)'s of the same seed bit
+    for bit.  -> dict of maps: rgb; depth (the reference's sum_k w_k z_k, a distance along the ray), alpha, depth_var; depth_median (the
+    sample depth at which the accumulated weight crosses `quantile` of the opacity), depth_mean (depth / alpha), both along the ray;
+    zdepth (SB,1,H,W), the camera-z depth of the surface point -- the unit of the source depth maps and of depth2normal --; points
+    (SB,3,H,W), the world-space surface point o + t d with t the median (point_depth "median") or the mean ("mean"); valid (SB,1,H,W)
+    bool, alpha > alpha_min as ops.ray_geometry decides it (an invalid pixel has 0 in depth_median, depth_mean, zdepth and points); and
+    normals (SB,3,H,W) = ops.depth2normal(zdepth, target_intrinsics): camera-frame normals with the reference's hole rule (an invalid
+    pixel is a hole), the convention of the normal maps the encoder receives; and extrinsics, the target_extrinsics of the call (what
+    diner_amd.geometry.point_cloud needs to turn the normals into the world frame).  Injected noise is sliced per batch as in predict_image."""
+    from diner_amd import ops
+    SB = target_extrinsics.shape[0]
+    dev = target_extrinsics.device
+    if dev.type != "cuda":
+        raise RuntimeError("diner_amd: predict_geometry runs on a HIP device; there is no CPU fallback")
+    znear = torch.as_tensor(znear, device=dev, dtype=torch.float32).expand(SB)
+    zfar = torch.as_tensor(zfar, device=dev, dtype=torch.float32).expand(SB)
+    rays = ops.gen_rays(target_extrinsics, target_intrinsics, W, H, znear, zfar, dev)
+    cam_fwd = target_extrinsics.detach().to("cpu", torch.float32)[:, 2, :3].contiguous()
+    if seed is None:
+        seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+    tiles = []
+    inj = _noise.current()
+    for r0 in range(0, H * W, ray_batch_size):
+        r1 = min(H * W, r0 + ray_batch_size)
+        rb = rays[:, r0:r1].contiguous()
+        ctx = contextlib.nullcontext() if inj is None else _noise.inject(*(None if t is None else t[:, r0:r1] for t in inj))
+        with ctx, _noise.keyed(seed, r0):
+            f = renderer.forward_geometry(nerf, rb, cam_fwd=cam_fwd, quantile=quantile, alpha_min=alpha_min, point_depth=point_depth).fine
+        tiles.append(torch.cat((f.rgb,) + tuple(f[k].unsqueeze(-1) for k in GEOMETRY_MAPS) + (f.points, f.median_idx.unsqueeze(-1).float()),
+                               dim=-1))                                                  # (SB, b, 13)
+    C = 3 + len(GEOMETRY_MAPS) + 4
+    full = (torch.cat(tiles, dim=1) if tiles else torch.zeros(SB, 0, C, device=dev)).view(SB, H, W, C).permute(0, 3, 1, 2)
+    out = {"rgb": full[:, :3].contiguous()}
+    for i, k in enumerate(GEOMETRY_MAPS):
+        out[k] = full[:, 3 + i:4 + i].contiguous()
+    out["points"] = full[:, 9:12].contiguous()
+    out["valid"] = full[:, 12:13] >= 0
+    out["extrinsics"] = target_extrinsics
+    out["normals"] = ops.depth2normal(out["zdepth"], target_intrinsics.to(dev)) if H * W > 0 else torch.zeros(SB, 3, H, W, device=dev)
+    return out

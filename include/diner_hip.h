@@ -566,6 +566,38 @@ int diner_compact_live_f32(const float* stats, float threshold, const float* ray
 int diner_expand_live_f32(const float* tiles, long long n_tiles, const int* slot, const float* bg, long long N, int C, float* out,
                           void* stream);
 
+/* ---- geometry from a render: median / mean / z-depth, world points, cross-view depth consistency ----------------------------------
+ * New symbols without an ABI bump (geometry.hip); enqueue-only on `stream`, one launch each, no allocation, no host synchronisation,
+ * no atomics; bad arguments return DINER_E_INVALID with a message before any device work.
+ *
+ * diner_ray_geometry_f32: one reduction over weights (NR,K) as the compositor entries write them (nerf_renderer.py:351), the z (NR,K)
+ *   and rays (NR,8) they were given; one wavefront per ray in the compositor's lane layout.  With w_k in sample order,
+ *   c_k = sum_{j<=k} w_j (the lane's running sum + the wave scan of the lane totals before it) and A = c_{K-1}, the last element of that
+ *   same sequence: a ray is VALID iff A > alpha_min (a NaN is invalid).  median_idx = min{k : c_k >= quantile * A} -- it exists because A
+ *   is c_{K-1}, and "first k" keeps it defined where a weight is negative (a sample beyond `far`); depth_median = z[median_idx], on a
+ *   surface where the mean of :356 lies between two; depth_mean = (sum_k w_k z_k) / A, the depth of :356 normalised by the opacity of
+ *   :359; t = depth_median (point_mode 0) or depth_mean (point_mode 1); points (NR,3) = o + t d; zdepth = t (d . cam_fwd) with cam_fwd
+ *   (host, 3 floats) row 2 of the target's world->camera rotation: the camera-z depth depth2normal.py:23-31 and the encoder take, where
+ *   cam_geometry.py:33 normalises d and the depth of :356 is a distance along the ray.  An invalid ray writes 0 to every float output
+ *   and -1 to median_idx (int32).  Any output pointer may be NULL; zdepth_out without cam_fwd is DINER_E_INVALID.
+ *   NR >= 1, 1 <= K <= 1024, 0 < quantile <= 1, alpha_min >= 0.
+ * diner_depth_consistency_f32: depth (N,H,W) device z-depth maps, 0 = no surface; intrinsics (N,3,3) and extrinsics (N,4,4)
+ *   world->camera are HOST arrays (they travel as kernel arguments, 1 KiB); 2 <= N <= DINER_MAX_VIEWS.  Per reference view r and pixel
+ *   (i, j) with D = depth[r][i][j] != 0, for every other view s: back-project ((j + 0.5 - cx) / fx D, (i + 0.5 - cy) / fy D, D), to
+ *   world by R_r^T (X - t_r), into s; reject if z_s <= 0; project to (u, v), sample depth[s] bilinearly at (u - 0.5, v - 0.5) and reject
+ *   unless all four taps are inside the image and non-zero; back-project (u, v) at the sampled depth from s and bring it into r: (u', v')
+ *   and d'.  The pair is consistent iff hypot(u' - (j + 0.5), v' - (i + 0.5)) < px_thr and |d' - D| / D < rel_thr.  count (int32) = the
+ *   consistent s, depth_avg = (D + sum of their d') / (count + 1); a pixel with D == 0 gets 0 and 0.  This is
+ *   check_geometric_consistency / reproject_with_depth and the averaging of filter_depth (deps/TransMVSNet/dynamic_fusion.py) with one
+ *   threshold pair, but with this project's pixel centres at +0.5 (depth2normal.py:23-31, cam_geometry.py:25-31) where that file uses
+ *   integer pixels, and a tap rule stricter than its cv2.remap, which blends with zeros: the numbers are not its numbers bit for bit.
+ *   Either output may be NULL. */
+int diner_ray_geometry_f32(const float* weights, const float* z, const float* rays, int NR, int K, float quantile, float alpha_min,
+                           const float* cam_fwd, int point_mode, float* depth_median_out, int* median_idx_out, float* depth_mean_out,
+                           float* zdepth_out, float* points_out, void* stream);
+int diner_depth_consistency_f32(const float* depth, const float* intrinsics, const float* extrinsics, int N, int H, int W, float px_thr,
+                                float rel_thr, int* count_out, float* depth_avg_out, void* stream);
+
 /* ---- measurement aid (bench.py): per-kernel durations of the two field kernels ------------------
  * With profiling enabled every field call brackets k_field_pre / k_field_post with HIP events on the
  * launch stream; diner_profile_collect waits for them, returns the summed durations (ms), the number

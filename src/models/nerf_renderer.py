@@ -198,6 +198,46 @@ class NeRFRendererDGS(torch.nn.Module):
             out.alpha, out.depth_var = torch.stack(alphas), torch.stack(dvars)
         return DotMap(fine=out)
 
+    def forward_geometry(self, model, rays, cam_fwd=None, want_weights=False, quantile=0.5, alpha_min=1e-3, point_depth="median"):
+        """forward with the geometry of the rendered rays (not in the reference; a method of its own, so that forward keeps its signature
+        and its code).  No-grad mode only, ValueError in grad mode.  rays (SB,B,8) -> DotMap(fine=...) as forward(want_alpha=True)
+        returns it -- rgb, depth, alpha, depth_var [, weights] are that call's, from the same sampler and compositor launches -- plus the
+        outputs of ops.ray_geometry on the rendered weights and the same z: depth_median, median_idx (int32), depth_mean (SB,B), points
+        (SB,B,3) and, with cam_fwd (SB,3), row 2 of each target's world->camera rotation, zdepth (SB,B); quantile, alpha_min and
+        point_depth are ops.ray_geometry's.  cull_empty is ignored, as it is with want_weights."""
+        assert len(rays.shape) == 3
+        self._check_model(model)
+        model._check_poscode()
+        assert self.n_samples >= self.n_gaussian
+        if model.needs_grad():
+            raise ValueError("diner_amd: forward_geometry has no gradient; call it under torch.no_grad()")
+        SB = rays.shape[0]
+        if cam_fwd is not None:
+            cam_fwd = torch.as_tensor(cam_fwd).detach().to("cpu", torch.float32)
+            if tuple(cam_fwd.shape) != (SB, 3):
+                raise ValueError(f"diner_amd: cam_fwd must be ({SB},3), got {tuple(cam_fwd.shape)}")
+        mlp = model.hip_mlp()
+        inj = _noise.current()
+        cols = {k: [] for k in ("weights", "rgb", "depth", "alpha", "depth_var") + ops.RayGeometry._fields}
+        for sb in range(SB):
+            scene = model.hip_scene(sb)
+            nz = None if inj is None else tuple(None if t is None else t[sb] for t in inj)
+            seed, r0 = _key(sb)
+            z = ops.sample_depthguided_long(scene, rays[sb], self.n_samples, self.n_depth_candidates, self.n_gaussian,
+                                            0.05, noise=nz, seed=seed, ray_index0=r0)
+            res = ops.render(scene, mlp, rays[sb], z, self.white_bkgd, want_weights=True, want_aux=True)
+            geo = ops.ray_geometry(res[0], z, rays[sb], None if cam_fwd is None else cam_fwd[sb], quantile, alpha_min, point_depth)
+            for k, v in zip(("weights", "rgb", "depth", "alpha", "depth_var"), res):
+                cols[k].append(v)
+            for k, v in zip(ops.RayGeometry._fields, geo):
+                cols[k].append(v)
+        out = self._format_outputs(torch.stack(cols["weights"]) if want_weights else None, torch.stack(cols["rgb"]),
+                                   torch.stack(cols["depth"]), want_weights=want_weights)
+        for k in ("alpha", "depth_var") + ops.RayGeometry._fields:
+            if cols[k][0] is not None:
+                out[k] = torch.stack(cols[k])
+        return DotMap(fine=out)
+
     def _forward_culled(self, scene, mlp, rays, nz, seed, r0, want_alpha):
         """One object of a no-grad forward with cull_empty: (B,8) -> (B, 4 or 6) rows [rgb, depth (, alpha, depth_var)]."""
         from diner_amd.render import render_live_rays
