@@ -62,6 +62,7 @@ SIGNATURES = {
     "diner_scene_proj_f16_bytes": (C.c_size_t, [C.POINTER(DinerScene)]),
     "diner_scene_prepare_f16": (C.c_int, [C.POINTER(DinerScene), C.c_void_p, C.c_void_p]),
     "diner_field_workspace_bytes": (C.c_size_t, [C.c_longlong]),
+    "diner_field_release_buffers": (C.c_int, []),
     "diner_field_from_rays_f32": (C.c_int, [C.POINTER(DinerScene), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                             C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "diner_field_from_points_f32": (C.c_int, [C.POINTER(DinerScene), C.c_void_p, C.c_void_p, C.c_void_p,

@@ -247,7 +247,8 @@ struct FieldArgs {
   const int* gate;              // optional: the kernel returns at once when *gate == 0 (device-side fp32 fall-back, mlp.hip)
   const float* w_pre;
   const float* b_pre;
-  float* xpre;                  // (P/16 tiles, NV, 32, 64) f32x4
+  float* xpre;                  // (P/16 tiles, 32, 64) f32x4: the view mean of the residual stream, in accumulator layout
+  float* rbar;                  // f16x3 kernels only: the same shape, the view mean of relu(h) of block 2 (whose fc_1 the post kernel runs)
 };
 
 // sample point p of the call: position (and viewing direction) from explicit xyz / viewdirs or from (ray, z)
@@ -350,6 +351,7 @@ struct PostArgs {
   const int* gate;     // optional: return at once when *gate == 0
   int* overflow;       // optional (fp16-operand kernels): set to 1 when a raw lin_out value is not finite
   unsigned int* fallback_count;   // optional (gated exact pass): +1 per launch that actually recomputes
+  const float* rbar;   // f16x3 kernels only: the second hand-over plane (FieldArgs.rbar)
 };
 
 }  // namespace diner

@@ -698,6 +698,58 @@ static size_t xpre_bytes(long long P, int /*nv*/) {
 }
 constexpr size_t kFlagBytes = 256;                           // overflow flag of the fp16-operand kernels (+ padding)
 
+// The second hand-over plane of the f16x3 kernels (the view mean of block 2's relu(h), FieldArgs.rbar): 2 KB per point in whole 16-point
+// tiles, like the plane in the caller's workspace, whose size is part of the ABI.  It lives in a library-owned buffer per (device, stream):
+// launches on one stream are ordered, so the launches of a stream share one buffer; it only ever grows (hipFree waits for the device, then
+// hipMalloc), which happens while a caller warms up and not in steady state.  diner_field_release_buffers() frees them all.
+struct SidePlanes {
+  struct Entry {
+    int dev;
+    hipStream_t stream;
+    void* ptr;
+    size_t bytes;
+  };
+  std::mutex mu;
+  std::vector<Entry> entries;
+};
+static SidePlanes g_side;
+
+static int side_plane(hipStream_t stream, long long P, float** out) {
+  const size_t bytes = xpre_bytes(P, kMaxViews);
+  int dev = 0;
+  DINER_HIP_OK(hipGetDevice(&dev));
+  std::lock_guard<std::mutex> lock(g_side.mu);
+  SidePlanes::Entry* e = nullptr;
+  for (auto& c : g_side.entries)
+    if (c.dev == dev && c.stream == stream) e = &c;
+  if (!e) {
+    g_side.entries.push_back({dev, stream, nullptr, 0});
+    e = &g_side.entries.back();
+  }
+  if (e->bytes < bytes) {
+    if (e->ptr) {
+      void* old = e->ptr;
+      e->ptr = nullptr;
+      e->bytes = 0;
+      DINER_HIP_OK(hipFree(old));
+    }
+    DINER_HIP_OK(hipMalloc(&e->ptr, bytes));
+    e->bytes = bytes;
+  }
+  *out = (float*)e->ptr;
+  return 0;
+}
+
+extern "C" int diner_field_release_buffers(void) {
+  std::lock_guard<std::mutex> lock(g_side.mu);
+  int rc = 0;
+  for (auto& c : g_side.entries)
+    if (c.ptr && hipFree(c.ptr) != hipSuccess) rc = DINER_E_HIP;
+  g_side.entries.clear();
+  if (rc) set_error("field_release_buffers: hipFree failed");
+  return rc;
+}
+
 // precision: DINER_PRECISION_*.  The fp16-operand modes are followed by a GATED pass of the exact-fp32 kernels: the post
 // kernel raises a device flag when a raw output is not finite (an activation left the fp16 range, or an input was not
 // finite to begin with), and only then do the fp32 kernels (which return at once otherwise) recompute the launch.  No
@@ -731,6 +783,7 @@ static int launch_field(const SceneDev* sc, const DinerMlpImpl* m, FieldArgs fa,
   fa.w_pre = m->w_pre;
   fa.b_pre = m->b_pre;
   fa.xpre = (float*)workspace;
+  fa.rbar = nullptr;
   fa.freq_factor = m->freq_factor;
   fa.gate = nullptr;
   int* flag = reinterpret_cast<int*>((char*)workspace + xpre_bytes(fa.P, nv));
@@ -757,6 +810,10 @@ static int launch_field(const SceneDev* sc, const DinerMlpImpl* m, FieldArgs fa,
   }
   PostArgs pa{(const float*)workspace, m->w_post, m->b_post, out, fa.P, nv, raw, nullptr, nullptr, m->fallback_dev};
   if (use_hn) {
+    if (split) {
+      int rcs = side_plane(stream, fa.P, &fa.rbar);
+      if (rcs) return rcs;
+    }
     DINER_HIP_OK(hipMemsetAsync(flag, 0, 24 * sizeof(int), stream));     // overflow flag + the tile counters (8 queues) of the two kernels
     if (timed) DINER_HIP_OK(hipEventRecord(e0, stream));
     h3n_launch_pre(*sc, fa, m->hn_w, m->hn_b_pre, grid_pre, split, reinterpret_cast<unsigned*>(flag) + 8, stream);
@@ -765,6 +822,7 @@ static int launch_field(const SceneDev* sc, const DinerMlpImpl* m, FieldArgs fa,
     PostArgs pn = pa;
     pn.b_post = m->hn_b_post;
     pn.overflow = flag;
+    pn.rbar = fa.rbar;
     h3n_launch_post(pn, m->hn_w, m->hn_w_out, grid_post, split, reinterpret_cast<unsigned*>(flag) + 16, stream);
     DINER_LAUNCH_OK();
     if (timed) DINER_HIP_OK(hipEventRecord(e2, stream));
@@ -824,6 +882,7 @@ static int launch_field_views(const DinerScene* scene, const DinerMlpImpl* m, Fi
   fa.w_pre = m->w_pre;
   fa.b_pre = m->b_pre;
   fa.xpre = (float*)workspace;
+  fa.rbar = nullptr;
   fa.freq_factor = m->freq_factor;
   fa.gate = nullptr;
   int* flag = reinterpret_cast<int*>((char*)workspace + xpre_bytes(fa.P, nv));
@@ -847,6 +906,10 @@ static int launch_field_views(const DinerScene* scene, const DinerMlpImpl* m, Fi
   PostArgs pa{(const float*)workspace, m->w_post, m->b_post, out, fa.P, nv, 0, nullptr, nullptr, m->fallback_dev};
   if (use_hn) {
     static_assert(kFlagBytes >= 48 * sizeof(int), "range flag + the tile counters of four groups and the post kernel");
+    {
+      int rcs = side_plane(stream, fa.P, &fa.rbar);
+      if (rcs) return rcs;
+    }
     DINER_HIP_OK(hipMemsetAsync(flag, 0, 48 * sizeof(int), stream));
     if (timed) DINER_HIP_OK(hipEventRecord(e0, stream));
     for (int g = 0; g < n_groups; ++g) {
@@ -860,6 +923,7 @@ static int launch_field_views(const DinerScene* scene, const DinerMlpImpl* m, Fi
     PostArgs pn = pa;
     pn.b_post = m->hn_b_post;
     pn.overflow = flag;
+    pn.rbar = fa.rbar;
     h3n_launch_post(pn, m->hn_w, m->hn_w_out, grid_post, true, reinterpret_cast<unsigned*>(flag) + 16, stream);
     DINER_LAUNCH_OK();
     if (timed) DINER_HIP_OK(hipEventRecord(e2, stream));
@@ -1204,6 +1268,8 @@ int field_forward_save(const DinerScene* scene, const DinerMlp* mlp, const float
     return DINER_E_UNSUPPORTED;
   }
   fa.xpre = (float*)workspace;
+  rc = side_plane(stream, P, &fa.rbar);
+  if (rc) return rc;
   fa.freq_factor = im->freq_factor;
   int* flag = reinterpret_cast<int*>((char*)workspace + xpre_bytes(P, sd.nv));
   DINER_HIP_OK(hipMemsetAsync(flag, 0, 24 * sizeof(int), stream));
@@ -1216,7 +1282,7 @@ int field_forward_save(const DinerScene* scene, const DinerMlp* mlp, const float
   static const bool nosave = [] { const char* e = getenv("DINER_TRAIN_NOSAVE"); return e && *e == '1'; }();
   h3n_launch_pre(sd, fa, im->hn_w, im->hn_b_pre, grid_pre, true, reinterpret_cast<unsigned*>(flag) + 8, stream, nosave ? nullptr : &sv);
   DINER_LAUNCH_OK();
-  PostArgs pn{(const float*)workspace, im->w_post, im->hn_b_post, out, P, sd.nv, 0, nullptr, flag, im->fallback_dev};
+  PostArgs pn{(const float*)workspace, im->w_post, im->hn_b_post, out, P, sd.nv, 0, nullptr, flag, im->fallback_dev, fa.rbar};
   h3n_launch_post(pn, im->hn_w, im->hn_w_out, grid_post, true, reinterpret_cast<unsigned*>(flag) + 16, stream, &sv);
   DINER_LAUNCH_OK();
   if (overflow_flag) *overflow_flag = flag;

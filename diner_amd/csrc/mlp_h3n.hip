@@ -11,6 +11,9 @@
 //   * activations are exchanged between layers through a 128 KB LDS buffer already in B-operand form (fp16 hi / lo,
 //     1/16 scale folded in): every wave converts its 128-feature slice, two barriers per layer;
 //   * the view mean is a register sum over the four column groups;
+//   * block 2's fc_1 is linear and the last per-view layer: fc_1(mean_v relu(h_v)) = mean_v fc_1(relu(h_v)).  The per-view kernel stops
+//     behind block 2's fc_0 and hands over TWO planes per point, mean_v x_v and mean_v relu(h_v); the post kernel runs the layer once per
+//     point (five per-view 512 x 512 layers per point and view instead of six; the exact-fp32 kernels keep the reference's order);
 //   * no bias pass on the residual stream in the per-view kernel: the fc_1 biases of blocks 0 and 1 travel in the bias of the next
 //     block's projected map (mlp.hip, mlp_pack), block 2's is added by the post kernel to the view mean it takes over.
 // Measuring stick: -DDINER_HN_PROF builds book shader clocks per phase of the tile loop (tools/prof_phases.sh); what was learnt
@@ -186,7 +189,7 @@ struct QueueMap {
 };
 struct Args {
   FieldArgs fa;
-  const _Float16* w;       // n-split packed weights: lin_in, then per block b<3: fc_0, fc_1
+  const _Float16* w;       // n-split packed weights: lin_in, then per block b<3: fc_0, fc_1 (the four-wave kernel stops behind block 2's fc_0)
   const _Float16* w8;      // the same seven layers in the 8-wave kernel's order (k_field_pre_h8; hi plane only), or null
   const float* b;          // biases x16: lin_in, then per block: fc_0, fc_1  (7 x 512)
   unsigned long long* prof;   // DINER_HN_PROF builds: 32 phase counters (shader clocks summed over waves), else unused
@@ -422,6 +425,26 @@ __device__ __forceinline__ void cvt4(const f32x4& x, float scale, u32x4& h, u32x
     l[2 * PART + 1] = cvt_pk_f16(resid_lo(h1, v[2]), resid_hi(h1, v[3]));
   }
 }
+
+// relu as cvt4 takes it, on the bit pattern: +inf and a NaN with a clear sign bit pass, -inf and a NaN with the sign bit set become 0
+__device__ __forceinline__ f32x4 relu_bits(const f32x4& x) {
+  f32x4 r;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) r[i] = __int_as_float(max(__float_as_int(x[i]), 0));
+  return r;
+}
+
+// Wave `wave`'s eight row tiles (1 KB each) of 16-point tile t16 of a hand-over plane: a scalar base, made opaque where it is used, + the
+// lane's 16 bytes as one 32-bit offset + immediates (as ARing's loads).  A per-lane 64-bit address would be hoisted out of the tile loop
+// and live in two registers across every GEMM, or come back from scratch.
+typedef __attribute__((address_space(1))) char* gbytes;
+typedef __attribute__((address_space(1))) f32x4* gf32x4;
+__device__ __forceinline__ gbytes handover_rows(const float* plane, long long t16, int wave) {
+  gbytes p = (gbytes)(reinterpret_cast<char*>(const_cast<float*>(plane)) + (size_t)t16 * (kTiles * 1024) + (size_t)wave * 8192 + 4096);
+  asm volatile("" : "+s"(p));
+  return p;
+}
+__device__ __forceinline__ gf32x4 handover_at(gbytes rows, unsigned lane_off, int mo) { return (gf32x4)(rows + lane_off + (mo * 1024 - 4096)); }
 
 // acc[mo][g] += W[slice rows][all k] . B[k][cols g]   (A straight from global, wave-private; B = the activations in fp16 hi / lo).
 // Fully unrolled over 2 KT half-steps (k32 block, row-tile half) of four quarter-steps (column group g): 12 MFMAs
@@ -807,20 +830,24 @@ __device__ __forceinline__ void field_pre_body(const SceneDev& sc, const Args& a
       GatherSide<kHnGDepth> gs(fa.tz + (size_t)(b + 1) * fa.tz_stride, taps_lds, wave, q, pt, xs);
       publish_gemm<kHnRing, false>(w1, Bl, wave, lane, ns, xs, gs, [&] { pin_acc(xs); }, pf, 10);
     }
-    {   // block 2: no gather left (and its fc_1 bias is added by the post kernel)
+    {   // block 2 stops behind fc_0: its fc_1 is linear, so the post kernel runs it once per point on the view means (no gather left here)
       const float* bias = a.b + kHidden * 5;
       NoSide none;
       if constexpr (SAVE) save_block<true>(sv.X[2], sv.bX[2], fa.P, tile, wave, lane, xs);
       publish_gemm<kHnRing0, true>(
           w_blk + (size_t)4 * kLayerHalfs, Bl, wave, lane, xs, ns, none, [&] { set_bias(ns, bias, wave, q); }, pf, 6);
       if constexpr (SAVE) save_block<true>(sv.H[2], sv.bH[2], fa.P, tile, wave, lane, ns);
-      publish_gemm<kHnRing, false>(w_blk + (size_t)5 * kLayerHalfs, Bl, wave, lane, ns, xs, none, [&] { pin_acc(xs); }, pf, 10);
     }
-    // view mean = mean over the four column groups; hand-over at scale 1 in accumulator layout (row tile 8 w + mo)
-    f32x4* out = reinterpret_cast<f32x4*>(fa.xpre) + (size_t)tile * (kTiles * 64) + lane;
+    // view means over the four column groups, handed over in accumulator layout (row tile 8 w + mo): the residual stream entering block
+    // 2's fc_1 at scale 1 (xpre, as the other kernel families hand it over) and relu of that layer's input at the network's scale, x16
+    // (rbar: the post kernel loads it into its accumulators as it is)
+    pin_acc(xs);                                  // both blocks stay in the accumulator half across the GEMM and are read from there
+    pin_acc(ns);
+    const gbytes out = handover_rows(fa.xpre, tile, wave), outr = handover_rows(fa.rbar, tile, wave);
+    const unsigned lane_off = lane * 16;
     if constexpr (GROUP) {
       // the sum over the LIVE views in the four-view order ((v0 + v1) + v2) + v3, by wave-uniform selection (never a multiplication with
-      // zero: an inf / NaN of a dead column must not reach the result, one of a live column must); scale = 1 / (16 NV)
+      // zero: an inf / NaN of a dead column must not reach the result, one of a live column must); vg.scale = 1 / (16 NV)
       int n_live = vg.n_live, first = vg.first;
       float scale = vg.scale;
       asm volatile("" : "+s"(n_live), "+s"(first), "+s"(scale));      // per-tile scalars, as the map sizes above
@@ -831,13 +858,24 @@ __device__ __forceinline__ void field_pre_body(const SceneDev& sc, const Args& a
         if (n_live > 2) s += xs[mo][2];
         if (n_live > 3) s += xs[mo][3];
         s *= scale;
-        if (!first) s += out[(8 * wave + mo) * 64];
-        out[(8 * wave + mo) * 64] = s;
+        if (!first) s += *handover_at(out, lane_off, mo);
+        *handover_at(out, lane_off, mo) = s;
+        // (the reference never forms this mean, so no order of its to keep: pairwise, (v0 + v1) + (v2 + v3), the smaller error bound)
+        f32x4 r = relu_bits(ns[mo][0]);
+        if (n_live > 1) r += relu_bits(ns[mo][1]);
+        if (n_live > 3) r += relu_bits(ns[mo][2]) + relu_bits(ns[mo][3]);
+        else if (n_live > 2) r += relu_bits(ns[mo][2]);
+        r *= scale * kScale;                      // 1 / NV at the network's scale
+        if (!first) r += *handover_at(outr, lane_off, mo);
+        *handover_at(outr, lane_off, mo) = r;
       }
     } else {
 #pragma unroll
-      for (int mo = 0; mo < kSlice; ++mo)
-        out[(8 * wave + mo) * 64] = (((xs[mo][0] + xs[mo][1]) + xs[mo][2]) + xs[mo][3]) * (0.25f * kInvScale);
+      for (int mo = 0; mo < kSlice; ++mo) {
+        *handover_at(out, lane_off, mo) = (((xs[mo][0] + xs[mo][1]) + xs[mo][2]) + xs[mo][3]) * (0.25f * kInvScale);
+        *handover_at(outr, lane_off, mo) =
+            ((relu_bits(ns[mo][0]) + relu_bits(ns[mo][1])) + (relu_bits(ns[mo][2]) + relu_bits(ns[mo][3]))) * 0.25f;      // (pairwise: see GROUP)
+      }
     }
     pf.mark(14);
   }
@@ -1235,7 +1273,7 @@ __global__ void k_pack_layer_h8(const float* __restrict__ W, int rows, int cols,
 
 struct PostArgsN {
   PostArgs pa;
-  const _Float16* w;        // n-split packed fc_0 / fc_1 of blocks 3, 4 (4 layers of 4 * 16 * 16 KB)
+  const _Float16* w;        // n-split packed fc_1 of block 2, then fc_0 / fc_1 of blocks 3, 4 (5 layers of 4 * 16 * 16 KB)
   const _Float16* w8;       // the same four layers in the eight-wave kernels' order (hi plane; k_field_post_h8), or null
   const float* w_out;       // lin_out for the vector ALU: [wave 4][mo 8][q 4][o 4][j 4] = Wout[o][128 wave + 16 mo + 4 q + j] / 16
   unsigned long long* prof; // DINER_HN_PROF builds: phase counters, else unused
@@ -1261,7 +1299,6 @@ __device__ __forceinline__ void field_post_body(const PostArgsN& a, const SaveAc
   const int lane = threadIdx.x & 63;
   const int q = lane >> 4, pt = lane & 15;
   const PostArgs& pa = a.pa;
-  const LdsB Bl = LdsB::make(B, lane);
   const long long n_t16 = (pa.P + kPtsPerWave - 1) / kPtsPerWave;
   const long long n_tiles = (n_t16 + 3) / 4;
 
@@ -1280,20 +1317,22 @@ __device__ __forceinline__ void field_post_body(const PostArgsN& a, const SaveAc
     for (int i = threadIdx.x; i < (int)(kLinOutWBytes / 16); i += 256) lo_w[i] = gw[i];
     __syncthreads();
   }
-  // The hand-over of a tile (2 KB per point, written by the per-view kernel in accumulator layout) is REQUESTED while the previous
-  // tile's lin_out runs, straight into the residual block, which is dead from lin_out's publish on (round 2's attempt at this made the
-  // allocator spill the block; with the accumulator accesses pinned it does not).  A tile starts by waiting for it: x16 + block 2's
-  // fc_1 bias, which the per-view kernel leaves to this one.
+  // The hand-over of a tile (two planes of 2 KB per point, written by the per-view kernel in accumulator layout: the view means of the
+  // residual stream and of block 2's relu(h)) is REQUESTED while the previous tile's lin_out runs, straight into the residual and hidden
+  // blocks, which are both dead by then (round 2's attempt at this made the allocator spill the block; with the accumulator accesses
+  // pinned it does not).  A tile starts by waiting for it (the residual plane x16), then runs block 2's fc_1 with its bias on it: the
+  // per-view kernel leaves that layer to this one, which runs it once per point instead of once per point and view.
   auto request_handover = [&](long long t) {
 #pragma unroll
     for (int g = 0; g < kGroups; ++g) {
       long long t16 = t * 4 + g;
       if (t16 >= n_t16) t16 = n_t16 - 1;
-      const f32x4* xp = reinterpret_cast<const f32x4*>(pa.xpre);
-      asm volatile("" : "+s"(xp));                 // per-tile address arithmetic: hoisted, the 64-bit lane addresses get spilled
-      const f32x4* in = xp + (size_t)t16 * (kTiles * 64) + lane_here();
+      const gbytes xp = handover_rows(pa.xpre, t16, wave), rp = handover_rows(pa.rbar, t16, wave);
+      const unsigned lane_off = lane_here() * 16;
 #pragma unroll
-      for (int mo = 0; mo < kSlice; ++mo) xs[mo][g] = in[(8 * wave + mo) * 64];
+      for (int mo = 0; mo < kSlice; ++mo) xs[mo][g] = *handover_at(xp, lane_off, mo);
+#pragma unroll
+      for (int mo = 0; mo < kSlice; ++mo) ns[mo][g] = *handover_at(rp, lane_off, mo);
     }
   };
   long long tile = blockIdx.x;
@@ -1302,31 +1341,36 @@ __device__ __forceinline__ void field_post_body(const PostArgsN& a, const SaveAc
     long long tile_next_v = n_tiles;
     // lane-derived quantities are re-derived per tile from an opaque copy: hoisted out of the tile loop they do not survive the GEMMs in
     // registers (the kernel uses all 512) and come back from scratch
-    const int q = lane_here() >> 4;
-    tq.request(a.tile_counter, n_tiles, a.qmap);
+    QueueMap qm = a.qmap;
+    asm volatile("" : "+s"(qm.R), "+s"(qm.m), "+s"(qm.per_pass));      // per-tile scalars: else the divisors' reciprocals cross the GEMMs in scratch
+    tq.request(a.tile_counter, n_tiles, qm);
     const float* bpost = pa.b_post;
     asm volatile("" : "+s"(bpost));                // (as above)
 #pragma unroll
-    for (int mo = 0; mo < kSlice; ++mo) {
-      const f32x4 b2 = *reinterpret_cast<const f32x4*>(bpost + 4 * kHidden + 16 + 128 * wave + 16 * mo + 4 * q);
+    for (int mo = 0; mo < kSlice; ++mo)
 #pragma unroll
-      for (int g = 0; g < kGroups; ++g) xs[mo][g] = xs[mo][g] * kScale + b2;
-    }
+      for (int g = 0; g < kGroups; ++g) xs[mo][g] = xs[mo][g] * kScale;
     NoSide none;
     pin_acc(xs);
+    pin_acc(ns);                                  // (comes at the network's scale and needs no arithmetic: its loads go straight into the accumulator half)
     pf.mark(8);
+    // block 2's fc_1 on the view means (the mean over the views commutes with the layer; the publish's relu is the identity on a mean of
+    // relus), with its bias: the stream entering block 3
+    publish_gemm<kHnRing, false, false>(a.w, LdsB::make(B, lane_here()), wave, lane_here(), ns, xs, none,
+                                        [&] { add_bias(xs, bpost + 4 * kHidden + 16, wave, lane_here() >> 4); }, pf, 4);
 #pragma nounroll
     for (int b = 0; b < 2; ++b) {
       const float* bias = bpost + 2 * kHidden * b;
+      pin_acc(xs);                                // (the block comes out of a GEMM in front of the loop and of one at its end)
       if constexpr (SAVE) save_block<false>(sv.X[3 + b], sv.bX[3 + b], pa.P, tile, wave, lane_here(), xs);
-      publish_gemm<kHnRing0, false>(a.w + (size_t)(2 * b) * kLayerHalfs, Bl, wave, lane, xs, ns, none, [&] {
+      publish_gemm<kHnRing0, false>(a.w + (size_t)(2 * b + 1) * kLayerHalfs, LdsB::make(B, lane_here()), wave, lane_here(), xs, ns, none, [&] {
         set_bias(ns, bias, wave, lane_here() >> 4);
         pin_acc(xs);                              // the residual stream stays in registers across the fc_0 GEMM
       }, pf, 0);
       if (b == 0) tq.park(&s_tile2[par]);           // (the request went out at the top of the tile)
       if constexpr (SAVE) save_block<false>(sv.H[3 + b], sv.bH[3 + b], pa.P, tile, wave, lane_here(), ns);
       pin_acc(xs);
-      publish_gemm<kHnRing, false, false>(a.w + (size_t)(2 * b + 1) * kLayerHalfs, Bl, wave, lane, ns, xs, none,
+      publish_gemm<kHnRing, false, false>(a.w + (size_t)(2 * b + 2) * kLayerHalfs, LdsB::make(B, lane_here()), wave, lane_here(), ns, xs, none,
                                       [&] { add_bias(xs, bias + kHidden, wave, lane_here() >> 4); }, pf, 4);
     }
     pin_acc(xs);                                  // (else the block is copied to vector registers here and back for the reads below)
@@ -1382,6 +1426,7 @@ __device__ __forceinline__ void field_post_body(const PostArgsN& a, const SaveAc
           m_pos = max(max(m_pos, xi[2]), xi[3]);
           m_neg = max(max(m_neg, (unsigned)xi[0]), (unsigned)xi[1]);
           m_neg = max(max(m_neg, (unsigned)xi[2]), (unsigned)xi[3]);
+          asm volatile("" : "+v"(m_pos), "+v"(m_neg));      // taken here: put off to where they are used, the maxima keep all 128 raw values alive
 #pragma unroll
           for (int o = 0; o < 4; ++o) {
             float t = po[g][o];
@@ -1393,8 +1438,13 @@ __device__ __forceinline__ void field_post_body(const PostArgsN& a, const SaveAc
       }
       // x is dead from here on: the next tile's hand-over is requested now (its index was parked in LDS behind the first GEMM), ahead of
       // the sums over lanes and waves and of the barrier, whose wait the loads then fill (the top of a tile waited 5.7 k clocks for them)
+      // (No branch around the request: the products above have their readers below it, and the optimiser sinks them past a conditional
+      // block, holding the 128 raw values of x in registers and scratch across the 64 loads.  Behind the last tile the workgroup reads
+      // the launch's last tile once more, for nothing.)
+      __builtin_amdgcn_sched_barrier(0);
       const long long tile_nx = tq.take(&s_tile2[par]);
-      if (tile_nx < n_tiles) request_handover(tile_nx);
+      request_handover(tile_nx < n_tiles ? tile_nx : n_tiles - 1);
+      __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int g = 0; g < kGroups; ++g) {
 #pragma unroll
@@ -1683,7 +1733,7 @@ __global__ void k_scale_pad(const float* __restrict__ src, int n, int n_pad, flo
 // The packed-weight buffer (DinerMlpImpl::hn_w), in _Float16 units: every layer of the network twice, once per kernel family.  This is the
 // one place that says where a plane lives; a kernel gets the start of its lin_in plane and walks on by the per-layer constants.
 //   four-wave order (k_pack_layer_h3n: hi and lo planes -- k_field_pre_h3n / k_field_post_h3n and the training forward):
-//     lin_in | fc_0, fc_1 of the per-view blocks 0-2 | fc_0, fc_1 of the post blocks 3-4
+//     lin_in | fc_0, fc_1 of the per-view blocks 0-2 | fc_0, fc_1 of the post blocks 3-4   (block 2's fc_1 is run by the post kernel)
 //   eight-wave order (k_pack_layer_h8: hi plane only -- k_field_pre_h8 / k_field_post_h8), the same three planes
 struct WeightLayout {
   static constexpr size_t kLinIn4 = h3n::kLinInHalfs, kPerView4 = 6 * h3n::kLayerHalfs, kPost4 = 4 * h3n::kLayerHalfs;
@@ -1691,6 +1741,9 @@ struct WeightLayout {
   static constexpr size_t oLinIn4 = 0, oPerView4 = oLinIn4 + kLinIn4, oPost4 = oPerView4 + kPerView4;
   static constexpr size_t oLinIn8 = oPost4 + kPost4, oPerView8 = oLinIn8 + kLinIn8, oPost8 = oPerView8 + kPerView8;
   static constexpr size_t kTotal = oPost8 + kPost8;
+  // what the four-wave kernels stream: the per-view kernel lin_in and the first five per-view layers (it stops behind block 2's fc_0), the
+  // post kernel block 2's fc_1 -- the last layer of the per-view plane, which lies directly in front of the post plane -- and the post layers
+  static constexpr size_t oPostStream4 = oPost4 - h3n::kLayerHalfs;
 };
 
 // w: see WeightLayout; w_lin_out: the fp32 pack of the vector-ALU lin_out (k_pack_lin_out_valu); b_pre: 7 x 512 (x16); b_post: 4 x 512 (x16) + the lin_out bias at
@@ -1793,7 +1846,7 @@ void h3n_launch_pre(const SceneDev& sc, const FieldArgs& fa, const _Float16* w, 
 void h3n_launch_post(const PostArgs& pa, const _Float16* w, const float* w_lin_out, int grid, bool split, unsigned* tile_counter,
                      hipStream_t stream, const SaveActs* sv) {
   const long long n_t16 = (pa.P + kPtsPerWave - 1) / kPtsPerWave;
-  h3n::PostArgsN a{pa, w + WeightLayout::oPost4, w + WeightLayout::oPost8, w_lin_out, nullptr, tile_counter, h3n::QueueMap::make((n_t16 + 3) / 4, 0, false)};
+  h3n::PostArgsN a{pa, w + WeightLayout::oPostStream4, w + WeightLayout::oPost8, w_lin_out, nullptr, tile_counter, h3n::QueueMap::make((n_t16 + 3) / 4, 0, false)};
 #ifdef DINER_HN_PROF
   static unsigned long long* prof = nullptr;
   if (!prof) hipMalloc(&prof, 32 * sizeof(unsigned long long));
@@ -1808,6 +1861,7 @@ void h3n_launch_post(const PostArgs& pa, const _Float16* w, const float* w_lin_o
   unsigned long long h[32];
   hipStreamSynchronize(stream);
   hipMemcpy(h, prof, sizeof(h), hipMemcpyDeviceToHost);
+  // (fc_0: blocks 3 and 4; fc_1: block 2's on the view means, then blocks 3 and 4)
   static const char* names[12] = {"fc_0 sync A", "fc_0 publish", "fc_0 sync B", "fc_0 gemm", "fc_1 sync A", "fc_1 publish", "fc_1 sync B",
                                   "fc_1 gemm", "hand-over load", "lin_out publish", "lin_out MFMAs", "epilogue"};
   const double waves = (double)h[26], tot = (double)h[24];

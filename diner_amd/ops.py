@@ -17,7 +17,8 @@ from . import _lib
 lib = _lib.load()          # ImportError when the extension is not built -- by design
 
 # points per field launch: bounds the 2 KB/point hand-over workspace (2 GiB at the default) without costing throughput
-# (a launch of 2^20 points is 64 tiles per CU)
+# (a launch of 2^20 points is 64 tiles per CU).  The f16x3 kernels hand over a second plane of the same size, which the library keeps
+# per stream (diner_field_release_buffers): + 2 GiB per stream at the default.
 MAX_POINTS_PER_LAUNCH = int(os.environ.get("DINER_AMD_MAX_POINTS", 1 << 20))
 
 
@@ -831,11 +832,12 @@ def gen_rays_at(extrinsics, intrinsics, W, H, z_near, z_far, pix):
 
 
 # FLOPs of the two field kernels per sample point: NV views x (lin_in + 3 x (lin_z, fc_0, fc_1))
-# before the view mean, 2 x (fc_0, fc_1) + lin_out after it.
+# before the view mean, 2 x (fc_0, fc_1) + lin_out after it.  Executed (the default f16x3 kernels): lin_z once per pixel, and fc_1 of the
+# last per-view block once per point, in the post kernel, on the view means -- 5 per-view layers and 5 post layers.
 FLOP_PRE_PER_POINT_REFERENCE = 2 * 4 * (55 * 512 + 9 * 512 * 512)     # as the reference computes it
-FLOP_PRE_PER_POINT = 2 * 4 * (55 * 512 + 6 * 512 * 512)               # executed: lin_z hoisted to once per pixel
+FLOP_PRE_PER_POINT = 2 * 4 * (55 * 512 + 5 * 512 * 512)               # executed: lin_z hoisted, block 2's fc_1 moved behind the view mean
 FLOP_HOIST_PER_PIXEL = 2 * 3 * 512 * 512
-FLOP_POST_PER_POINT = 2 * (4 * 512 * 512 + 512 * 4)
+FLOP_POST_PER_POINT = 2 * (5 * 512 * 512 + 4 * 512)
 
 
 def profile_enable(flag=True):

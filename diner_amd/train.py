@@ -199,11 +199,13 @@ def _step_mlp(params, freq_factor):
 
 def release_buffers():
     """Frees what the training path keeps between steps: the shared work buffers (`_SCRATCH`: 4.6 GiB per stream at one object of 4096 rays
-    x 40 samples, 17 GiB for the batched step of four), the projected-map buffers (`_PROJ`) and the persistent packed-weights handles.  Call it
+    x 40 samples, 17 GiB for the batched step of four), the projected-map buffers (`_PROJ`), the persistent packed-weights handles and the library-owned second hand-over plane of the f16x3 field kernels
+    (2 KB per point of the largest launch per stream).  Call it
     when leaving training for, e.g., a validation render in the same process; the next step allocates them again."""
     _SCRATCH.clear()
     _PROJ.clear()
     _STEP_MLP.clear()
+    _lib.check(lib.diner_field_release_buffers())
 
 
 def _channels_last(latent):

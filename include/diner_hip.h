@@ -225,8 +225,15 @@ int diner_scene_prepare_f16(const DinerScene* scene, void* latent_proj_f16_out, 
  * Points are o + z*d for every (ray, sample); view directions are the ray directions.
  *   precision  DINER_PRECISION_* (above)
  *   field_out  (NR*K, 4) = [sigmoid(r,g,b), relu(sigma)]
- *   workspace  diner_field_workspace_bytes(NR*K) bytes of device scratch */
+ *   workspace  diner_field_workspace_bytes(NR*K) bytes of device scratch: the hand-over between the per-view and the post kernel (the view
+ *              mean of the residual stream, 2 KB per point) and the flag block.  DINER_PRECISION_F16X3 hands over a second plane of the same
+ *              size (the view mean of relu(h) of the last per-view block, whose fc_1 the post kernel runs once per point); that one lives
+ *              in a buffer the library owns per (device, stream), grown when a launch needs more than the stream has had and kept until
+ *              diner_field_release_buffers() -- the training forward on the fused kernels uses it too. */
 size_t diner_field_workspace_bytes(long long n_points);
+/* Frees the library-owned hand-over buffers of every device and stream (waits for the device); the next f16x3 launch allocates its own
+ * again.  Returns 0 when there was nothing to free -- no device is touched then.  New symbol, no ABI bump. */
+int diner_field_release_buffers(void);
 int diner_field_from_rays_f32(const DinerScene* scene, const DinerMlp* mlp, const float* rays, const float* z,
                               int NR, int K, int precision, float* field_out, void* workspace, void* stream);
 /* Same, explicit points / view directions (P,3): PixelNeRF.forward(xyz, viewdirs) (pixelnerf.py:55). */
@@ -235,7 +242,8 @@ int diner_field_from_points_f32(const DinerScene* scene, const DinerMlp* mlp, co
 
 /* ---- the same for scenes with ANY number of source views, 1 .. DINER_MAX_VIEWS (pixelnerf.py:67 takes any) -------------------------
  * The mean over the views (resnetfc.py:148-151) is linear: an NV-view scene runs as ceil(NV / 4) launches of the four-view per-view
- * kernel over groups of four cameras, each adding (1 / NV) x the sum over its live views into the same 2 KB-per-point hand-over, and one
+ * kernel over groups of four cameras, each adding (1 / NV) x the sum over its live views into the same 2 KB-per-point hand-over (f16x3:
+ * into both of its planes, see diner_field_workspace_bytes), and one
  * unchanged post kernel.  A partial group's spare columns recompute one of its own views and are left out of the sum.  Arguments,
  * workspace size and results as the four-view namesakes above; NV = 4 IS the four-view entry (same bits).  New symbols, no ABI bump.
  *   diner_scene_proj_views_bytes    3 NV Hf Wf 512 4 bytes for 1 <= NV <= DINER_MAX_VIEWS, else 0
