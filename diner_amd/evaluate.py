@@ -27,6 +27,7 @@ ALPHA_SUFFIX = "-alpha.png"
 ZDEPTH_SUFFIX = "-zdepth.png"
 NORMAL_SUFFIX = "-normal.png"
 PLY_SUFFIX = ".ply"
+MESH_SUFFIX = "-mesh.ply"
 AVERAGE_SCORE_FILENAME = "average_scores.json"
 REPORT_DETAIL_FILENAME = "detailed_report.json"
 EXAMPLE_PLOT_FILENAME = "examples.png"
@@ -49,7 +50,7 @@ def _hip_device(device):
 
 @torch.no_grad()
 def write_prediction_folder(nerf, renderer, batches, outdir, znear, zfar, ray_batch_size=8192, write_alpha=False, cull_empty=False,
-                            write_geometry=False):
+                            write_geometry=False, write_mesh=False):
     """Render every target view of `batches` (collated sample dicts of diner_amd.datasets) with `nerf` / `renderer` and write
     <sample_name>{-pred,-depth,-ref,-gt}.png into `outdir`: the render and its colour-mapped depth, the source views side by side and
     the target, each quantised as save_image does.  Returns {"sample_name": [...], "l1", "l2", "psnr", "ssim": float64 (N,)} -- the
@@ -59,7 +60,9 @@ def write_prediction_folder(nerf, renderer, batches, outdir, znear, zfar, ray_ba
     write_geometry (off by default): render with predict_geometry instead -- the same colour, depth and opacity bit for bit -- and also
     write <sample_name>-zdepth.png (the camera-z depth of the surface through the depth colour map), <sample_name>-normal.png (the
     camera-frame normals as n * 0.5 + 0.5, quantised like the others) and <sample_name>.ply (diner_amd.geometry.point_cloud at its
-    defaults: points, colours and world-frame normals).  cull_empty does not combine with it and is ignored then."""
+    defaults: points, colours and world-frame normals).  cull_empty does not combine with it and is ignored then.
+    write_mesh (off by default): also <sample_name>-mesh.ply, the triangle mesh diner_amd.surface.mesh_from_sources fuses out of the
+    sample's source depth maps and colours at its defaults (the prior's surface: no MLP involved, the renders are untouched)."""
     from .datasets import encode_args
     from .imageio import depth_to_uint8, gray_to_uint8, to_uint8
     from .metrics import KEYS, image_metrics
@@ -92,6 +95,9 @@ def write_prediction_folder(nerf, renderer, batches, outdir, znear, zfar, ray_ba
                 write_png(os.path.join(outdir, stem + ZDEPTH_SUFFIX), depth_to_uint8(geo["zdepth"][i]))
                 write_png(os.path.join(outdir, stem + NORMAL_SUFFIX), to_uint8(geo["normals"][i] * 0.5 + 0.5))
                 write_ply(os.path.join(outdir, stem + PLY_SUFFIX), *point_cloud({k: v[i:i + 1] for k, v in geo.items()}))
+            if write_mesh:
+                from .surface import mesh_from_sources, write_mesh_ply
+                write_mesh_ply(os.path.join(outdir, stem + MESH_SUFFIX), *mesh_from_sources(batch, sb=i, device=dev)[0])
             names.append(stem)
         s = image_metrics(rgb, gt)
         for k in KEYS:

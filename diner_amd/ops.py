@@ -780,6 +780,109 @@ def depth_consistency(depth, intrinsics, extrinsics, px_thr=1.0, rel_thr=0.01):
     return count, avg
 
 
+SURFACE_MAX_DIM = 1024
+
+
+def _check_volume(who, tsdf, wsum, color4, origin, voxel):
+    """The volume checks of tsdf_integrate / surface_extract that need no device: -> (Nx, Ny, Nz, origin as three host floats)."""
+    if tsdf.dim() != 3 or tuple(wsum.shape) != tuple(tsdf.shape):
+        raise ValueError(f"diner_amd: {who} expects tsdf and wsum (Nz,Ny,Nx), got {tuple(tsdf.shape)}, {tuple(wsum.shape)}")
+    Nz, Ny, Nx = (int(v) for v in tsdf.shape)
+    if not all(2 <= n <= SURFACE_MAX_DIM for n in (Nx, Ny, Nz)) or Nx * Ny * Nz >= 2 ** 31:
+        raise ValueError(f"diner_amd: {who} takes volumes of 2 .. {SURFACE_MAX_DIM} samples a side and fewer than 2^31 in all, got "
+                         f"{(Nz, Ny, Nx)}")
+    if color4 is not None and tuple(color4.shape) != (4, Nz, Ny, Nx):
+        raise ValueError(f"diner_amd: {who} expects color4 (4,{Nz},{Ny},{Nx}), got {tuple(color4.shape)}")
+    o = torch.as_tensor(origin, dtype=torch.float32).detach().to("cpu").reshape(-1)
+    if o.numel() != 3:
+        raise ValueError(f"diner_amd: {who} origin holds {o.numel()} values, expected 3")
+    if not float(voxel) > 0.0:
+        raise ValueError(f"diner_amd: {who} voxel size {voxel} must be > 0")
+    return Nx, Ny, Nz, (C.c_float * 3)(*o.tolist())
+
+
+def _require_volume(who, *planes):
+    _require_hip(*planes)
+    for t in planes:
+        if t is not None and not t.is_contiguous():
+            raise ValueError(f"diner_amd: {who} works on contiguous volume planes")
+
+
+def _check_tsdf_integrate_args(tsdf, wsum, color4, origin, voxel, trunc, depth, intrinsics, extrinsics, weight, color):
+    """The argument checks of tsdf_integrate that need no device: -> (Nx, Ny, Nz, origin, N, H, W, host intrinsics, host extrinsics)."""
+    Nx, Ny, Nz, o = _check_volume("tsdf_integrate", tsdf, wsum, color4, origin, voxel)
+    if not float(trunc) > 0.0:
+        raise ValueError(f"diner_amd: tsdf_integrate truncation distance {trunc} must be > 0")
+    if depth.dim() == 4 and depth.shape[1] == 1:
+        depth = depth[:, 0]
+    if depth.dim() != 3:
+        raise ValueError(f"diner_amd: tsdf_integrate expects depth (N,H,W) or (N,1,H,W), got {tuple(depth.shape)}")
+    N, H, W = (int(v) for v in depth.shape)
+    if not 1 <= N <= _lib.MAX_VIEWS:
+        raise ValueError(f"diner_amd: tsdf_integrate takes 1 .. {_lib.MAX_VIEWS} views, got {N}")
+    if H < 1 or W < 1:
+        raise ValueError(f"diner_amd: tsdf_integrate got empty depth maps {tuple(depth.shape)}")
+    if tuple(intrinsics.shape) != (N, 3, 3) or tuple(extrinsics.shape) != (N, 4, 4):
+        raise ValueError(f"diner_amd: tsdf_integrate expects intrinsics ({N},3,3) and extrinsics ({N},4,4), got "
+                         f"{tuple(intrinsics.shape)}, {tuple(extrinsics.shape)}")
+    if weight is not None and weight.numel() != N * H * W:
+        raise ValueError(f"diner_amd: tsdf_integrate expects weight ({N},{H},{W}) or ({N},1,{H},{W}), got {tuple(weight.shape)}")
+    if color is not None and tuple(color.shape) != (N, 3, H, W):
+        raise ValueError(f"diner_amd: tsdf_integrate expects color ({N},3,{H},{W}), got {tuple(color.shape)}")
+    if (color is None) != (color4 is None):
+        raise ValueError("diner_amd: tsdf_integrate takes color maps and the color4 planes together or not at all")
+    Km = intrinsics.detach().to("cpu", torch.float32).contiguous()
+    E = extrinsics.detach().to("cpu", torch.float32).contiguous()
+    return Nx, Ny, Nz, o, N, H, W, Km, E
+
+
+def tsdf_integrate(tsdf, wsum, color4, origin, voxel, trunc, depth, intrinsics, extrinsics, weight=None, color=None, carve=False,
+                   max_weight=0.0):
+    """Fuse N z-depth maps into a TSDF volume IN PLACE (diner_tsdf_integrate_f32, one launch): tsdf, wsum (Nz,Ny,Nx) and color4
+    (4,Nz,Ny,Nx) or None, contiguous on the HIP device (fresh: 1, 0, 0); sample (i,j,k) lies at origin + (i,j,k) voxel.  depth (N,H,W)
+    or (N,1,H,W) camera-z maps with 0 = no surface, weight the same shape or None (1), color (N,3,H,W) or None -- given iff color4 is;
+    intrinsics (N,3,3), extrinsics (N,4,4) world->camera (read on the host), 1 <= N <= 16.  Each voxel is projected into every view in
+    order (nearest pixel, centres at +0.5) and takes the running weighted mean of min(1, (D - z) / trunc) where D > 0 and D - z >= -trunc;
+    carve: a pixel with D == 0 votes free space (1) along its whole ray.  max_weight > 0 caps wsum.  Returns None."""
+    Nx, Ny, Nz, o, N, H, W, Km, E = _check_tsdf_integrate_args(tsdf, wsum, color4, origin, voxel, trunc, depth, intrinsics, extrinsics,
+                                                               weight, color)
+    _require_volume("tsdf_integrate", tsdf, wsum, color4)
+    _require_hip(depth, weight, color)
+    depth = _f32c(depth).reshape(N, H, W)
+    weight = None if weight is None else _f32c(weight).reshape(N, H, W)
+    color = None if color is None else _f32c(color)
+    with torch.cuda.device(tsdf.device):
+        _lib.check(lib.diner_tsdf_integrate_f32(_ptr(tsdf), _ptr(wsum), _ptr(color4), Nx, Ny, Nz, o, float(voxel), float(trunc), _ptr(depth),
+                                                _ptr(weight), _ptr(color), Km.data_ptr(), E.data_ptr(), N, H, W, int(bool(carve)),
+                                                float(max_weight), _stream()))
+
+
+SurfaceMesh = collections.namedtuple("SurfaceMesh", "vertices normals rgb faces")
+
+
+def surface_extract(tsdf, wsum, color4, origin, voxel, min_weight=0.0):
+    """The naive surface nets mesh of a TSDF volume (diner_surface_count + diner_surface_extract_f32): tsdf, wsum (Nz,Ny,Nx), color4
+    (4,Nz,Ny,Nx) or None as tsdf_integrate leaves them -> SurfaceMesh(vertices (nv,3), normals (nv,3), rgb (nv,3) float32 in [0, 1] or
+    None without color4, faces (2 nq,3) int32).  One vertex per cell whose 8 corners are observed (wsum > min_weight) and of both
+    signs, in linear cell order; one quad -- two triangles, wound so that the normal points out of the negative side -- per
+    sign-changing grid edge whose four cells are active.  The counts are read back once (8 bytes) to size the outputs: not a hot path."""
+    Nx, Ny, Nz, o = _check_volume("surface_extract", tsdf, wsum, color4, origin, voxel)
+    _require_volume("surface_extract", tsdf, wsum, color4)
+    dev = tsdf.device
+    with torch.cuda.device(dev):
+        ws = _workspace(lib.diner_surface_workspace_bytes(Nx, Ny, Nz), dev)
+        counts = torch.empty(2, dtype=torch.int32, device=dev)
+        _lib.check(lib.diner_surface_count(_ptr(tsdf), _ptr(wsum), Nx, Ny, Nz, float(min_weight), _ptr(ws), _ptr(counts), _stream()))
+        nv, nq = (int(c) for c in counts.tolist())
+        vertices = torch.empty(nv, 3, dtype=torch.float32, device=dev)
+        normals = torch.empty(nv, 3, dtype=torch.float32, device=dev)
+        rgb = None if color4 is None else torch.empty(nv, 3, dtype=torch.float32, device=dev)
+        faces = torch.empty(2 * nq, 3, dtype=torch.int32, device=dev)
+        _lib.check(lib.diner_surface_extract_f32(_ptr(tsdf), _ptr(wsum), _ptr(color4), Nx, Ny, Nz, o, float(voxel), float(min_weight), _ptr(ws),
+                                                 nv, nq, _ptr(vertices), _ptr(normals), _ptr(rgb), _ptr(faces), _stream()))
+    return SurfaceMesh(vertices, normals, rgb, faces)
+
+
 def gen_rays(extrinsics, intrinsics, W, H, z_near, z_far, device, ray0=0, n_rays=None):
     """Reference src/util/cam_geometry.py:5-48 on the device: rays [ray0, ray0+n_rays) of each camera's row-major
     (H, W) list -> (B, n_rays, 8).  Camera tensors may live anywhere (they are read on the host: B x 27 floats)."""

@@ -606,6 +606,52 @@ int diner_ray_geometry_f32(const float* weights, const float* z, const float* ra
 int diner_depth_consistency_f32(const float* depth, const float* intrinsics, const float* extrinsics, int N, int H, int W, float px_thr,
                                 float rel_thr, int* count_out, float* depth_avg_out, void* stream);
 
+/* ---- surfaces: depth maps fused into a TSDF volume, and a triangle mesh out of it ---------------------------------------------------
+ * New symbols without an ABI bump (surface.hip); no allocation, no atomics, no workgroup waiting on another (the stream is the only
+ * ordering between launches); every output byte is a function of the inputs alone; bad arguments return DINER_E_INVALID with a
+ * message before any device work.
+ *
+ * The volume is an axis-aligned box: sample (i, j, k) lies at origin + (i, j, k) voxel, origin (3 floats) on the HOST; each of Nx, Ny,
+ * Nz is 2 .. 1024 and Nx Ny Nz < 2^31.  The device planes are (Nz, Ny, Nx) fp32, x fastest: tsdf (a fresh volume holds 1), wsum (0)
+ * and optionally color4 (4, Nz, Ny, Nx) = sum w r, sum w g, sum w b, sum w (0).
+ *
+ * diner_tsdf_integrate_f32: one launch, enqueue-only, one thread per voxel; the voxel's values live in registers across a loop over the
+ *   views IN VIEW ORDER, so the volume is read and written once per call whatever N, and one call with N views leaves the bits of N
+ *   single-view calls in that order.  depth (N,H,W) device z-depth maps (camera z, the unit of predict_geometry's zdepth and of the
+ *   source depth maps), weight (N,H,W) device or NULL (1 everywhere), color (N,3,H,W) device or NULL; intrinsics (N,3,3) and
+ *   extrinsics (N,4,4) world->camera are HOST arrays (kernel arguments, 1 KiB); 1 <= N <= DINER_MAX_VIEWS.  Per view, with p the
+ *   voxel's position: X = R p + t, skip unless X.z > 0; u = fx (X.x / X.z) + cx, v = fy (X.y / X.z) + cy, skip unless 0 <= u < W and
+ *   0 <= v < H; the pixel is (floor v, floor u), the nearest with centres at +0.5; wp = weight there (or 1), skip unless wp > 0;
+ *   D = depth there.  D > 0: sdf = D - X.z, skip if sdf < -trunc, d = min(1, sdf / trunc).  D == 0 with `carve`: d = 1 (the pixel is
+ *   known to be empty: the whole ray is free space).  Anything else (D == 0 without carve, negative, NaN): skip.  Then
+ *   tsdf = (tsdf wsum + d wp) / (wsum + wp) and wsum += wp, clamped to max_weight when max_weight > 0.  The colour sums take
+ *   wp (r, g, b, 1) only where D > 0 and |sdf| <= trunc, and are never clamped.  color without color4, or the reverse, is refused.
+ * diner_surface_workspace_bytes: device bytes diner_surface_count / _extract need for this volume (0 for dimensions they refuse).
+ * diner_surface_count: two launches, enqueue-only: counts_out (device int32[2]) = the vertices and the quads of the naive surface
+ *   nets mesh below; the workspace keeps the per-block offsets and the counts for diner_surface_extract_f32.
+ * diner_surface_extract_f32: must follow diner_surface_count on the same stream with the same volume, min_weight and workspace, and
+ *   be given the counts it wrote: it reads them back from the workspace (8 bytes, its one host synchronisation) and returns
+ *   DINER_E_INVALID if they differ, before launching.  Two launches: vertices (+ the cell -> vertex map in the workspace), faces.
+ *     A corner is NEGATIVE iff tsdf < 0 (an exact 0 and a NaN are positive) and OBSERVED iff wsum > min_weight.  Cell (i, j, k), i < Nx-1,
+ *   j < Ny-1, k < Nz-1, is ACTIVE iff its 8 corners are observed and both signs occur.  One vertex per active cell, ids in linear cell
+ *   order (x fastest): position = origin + voxel (cell + m), m = the mean over the sign-changing cell edges (a, b) of a + t (b - a),
+ *   t = f_a / (f_a - f_b); normal = the normalised gradient of the trilinear interpolant of the 8 corner values at m -- towards
+ *   increasing tsdf, free space -- or 0 where the gradient is 0; rgb (float) = trilinear(sum w c) / trilinear(sum w) at m, 0 where
+ *   the denominator is not positive or color4 is NULL.  One quad per grid edge that starts at (i, j, k), runs to +x, +y or +z, changes
+ *   sign and has its four neighbouring cells existing and active; quads in linear order of the start point, then x-, y-, z-edge; each
+ *   starts at the neighbouring cell with the smallest indices and is wound so that its right-hand normal points from the negative to
+ *   the positive end; triangles (0,1,2), (0,2,3).  An edge with a missing or inactive cell emits nothing: the mesh has a boundary there.
+ *   vertices_out (nv,3), normals_out (nv,3) or NULL, rgb_out (nv,3) or NULL, faces_out (2 nq,3) int32. */
+int diner_tsdf_integrate_f32(float* tsdf, float* wsum, float* color4, int Nx, int Ny, int Nz, const float* origin, float voxel,
+                             float trunc, const float* depth, const float* weight, const float* color, const float* intrinsics,
+                             const float* extrinsics, int N, int H, int W, int carve, float max_weight, void* stream);
+size_t diner_surface_workspace_bytes(int Nx, int Ny, int Nz);
+int diner_surface_count(const float* tsdf, const float* wsum, int Nx, int Ny, int Nz, float min_weight, void* workspace, int* counts_out,
+                        void* stream);
+int diner_surface_extract_f32(const float* tsdf, const float* wsum, const float* color4, int Nx, int Ny, int Nz, const float* origin,
+                              float voxel, float min_weight, void* workspace, int n_vertices, int n_quads, float* vertices_out,
+                              float* normals_out, float* rgb_out, int* faces_out, void* stream);
+
 /* ---- measurement aid (bench.py): per-kernel durations of the two field kernels ------------------
  * With profiling enabled every field call brackets k_field_pre / k_field_post with HIP events on the
  * launch stream; diner_profile_collect waits for them, returns the summed durations (ms), the number
