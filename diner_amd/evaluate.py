@@ -28,6 +28,8 @@ ZDEPTH_SUFFIX = "-zdepth.png"
 NORMAL_SUFFIX = "-normal.png"
 PLY_SUFFIX = ".ply"
 MESH_SUFFIX = "-mesh.ply"
+VDEPTH_SUFFIX = "-vdepth.png"
+VNORMAL_SUFFIX = "-vnormal.png"
 AVERAGE_SCORE_FILENAME = "average_scores.json"
 REPORT_DETAIL_FILENAME = "detailed_report.json"
 EXAMPLE_PLOT_FILENAME = "examples.png"
@@ -50,7 +52,7 @@ def _hip_device(device):
 
 @torch.no_grad()
 def write_prediction_folder(nerf, renderer, batches, outdir, znear, zfar, ray_batch_size=8192, write_alpha=False, cull_empty=False,
-                            write_geometry=False, write_mesh=False):
+                            write_geometry=False, write_mesh=False, write_volume_view=False):
     """Render every target view of `batches` (collated sample dicts of diner_amd.datasets) with `nerf` / `renderer` and write
     <sample_name>{-pred,-depth,-ref,-gt}.png into `outdir`: the render and its colour-mapped depth, the source views side by side and
     the target, each quantised as save_image does.  Returns {"sample_name": [...], "l1", "l2", "psnr", "ssim": float64 (N,)} -- the
@@ -62,7 +64,10 @@ def write_prediction_folder(nerf, renderer, batches, outdir, znear, zfar, ray_ba
     camera-frame normals as n * 0.5 + 0.5, quantised like the others) and <sample_name>.ply (diner_amd.geometry.point_cloud at its
     defaults: points, colours and world-frame normals).  cull_empty does not combine with it and is ignored then.
     write_mesh (off by default): also <sample_name>-mesh.ply, the triangle mesh diner_amd.surface.mesh_from_sources fuses out of the
-    sample's source depth maps and colours at its defaults (the prior's surface: no MLP involved, the renders are untouched)."""
+    sample's source depth maps and colours at its defaults (the prior's surface: no MLP involved, the renders are untouched).
+    write_volume_view (off by default): also <sample_name>-vdepth.png and <sample_name>-vnormal.png, that volume ray-cast into the target
+    camera (TsdfVolume.raycast): its z-depth through the depth colour map and its camera-frame normals encoded as -normal.png is --
+    the prior's surface as the target camera sees it, no MLP involved.  With write_mesh the two share one volume."""
     from .datasets import encode_args
     from .imageio import depth_to_uint8, gray_to_uint8, to_uint8
     from .metrics import KEYS, image_metrics
@@ -95,9 +100,15 @@ def write_prediction_folder(nerf, renderer, batches, outdir, znear, zfar, ray_ba
                 write_png(os.path.join(outdir, stem + ZDEPTH_SUFFIX), depth_to_uint8(geo["zdepth"][i]))
                 write_png(os.path.join(outdir, stem + NORMAL_SUFFIX), to_uint8(geo["normals"][i] * 0.5 + 0.5))
                 write_ply(os.path.join(outdir, stem + PLY_SUFFIX), *point_cloud({k: v[i:i + 1] for k, v in geo.items()}))
-            if write_mesh:
+            if write_mesh or write_volume_view:
                 from .surface import mesh_from_sources, write_mesh_ply
-                write_mesh_ply(os.path.join(outdir, stem + MESH_SUFFIX), *mesh_from_sources(batch, sb=i, device=dev)[0])
+                mesh, vol = mesh_from_sources(batch, sb=i, device=dev)
+                if write_mesh:
+                    write_mesh_ply(os.path.join(outdir, stem + MESH_SUFFIX), *mesh)
+                if write_volume_view:
+                    view = vol.raycast(batch["target_extrinsics"][i:i + 1], batch["target_intrinsics"][i:i + 1], W, H)
+                    write_png(os.path.join(outdir, stem + VDEPTH_SUFFIX), depth_to_uint8(view["zdepth"][0]))
+                    write_png(os.path.join(outdir, stem + VNORMAL_SUFFIX), to_uint8(view["normal"][0] * 0.5 + 0.5))
             names.append(stem)
         s = image_metrics(rgb, gt)
         for k in KEYS:

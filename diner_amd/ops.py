@@ -883,6 +883,83 @@ def surface_extract(tsdf, wsum, color4, origin, voxel, min_weight=0.0):
     return SurfaceMesh(vertices, normals, rgb, faces)
 
 
+RAYCAST_MAX_SAMPLES = 1 << 20
+TsdfRaycast = collections.namedtuple("TsdfRaycast", "zdepth normal rgb weight")
+
+
+def tsdf_bricks(tsdf, wsum, min_weight=0.0):
+    """The brick mask of a TSDF volume (diner_tsdf_bricks, one launch): tsdf, wsum (Nz,Ny,Nx) contiguous on the HIP device -> uint8
+    (ceil((Nz-1)/8), ceil((Ny-1)/8), ceil((Nx-1)/8)): 1 iff some cell of the brick of 8^3 cells has all 8 corners observed
+    (wsum > min_weight) and at least one negative -- the only cells a ray-cast can end in.  For tsdf_raycast(bricks=...) on the same
+    planes with the same min_weight."""
+    if tsdf.dim() != 3 or tuple(wsum.shape) != tuple(tsdf.shape):
+        raise ValueError(f"diner_amd: tsdf_bricks expects tsdf and wsum (Nz,Ny,Nx), got {tuple(tsdf.shape)}, {tuple(wsum.shape)}")
+    Nz, Ny, Nx = (int(v) for v in tsdf.shape)
+    if not all(2 <= n <= SURFACE_MAX_DIM for n in (Nx, Ny, Nz)) or Nx * Ny * Nz >= 2 ** 31:
+        raise ValueError(f"diner_amd: tsdf_bricks takes volumes of 2 .. {SURFACE_MAX_DIM} samples a side and fewer than 2^31 in all, got "
+                         f"{(Nz, Ny, Nx)}")
+    _require_volume("tsdf_bricks", tsdf, wsum)
+    dev = tsdf.device
+    with torch.cuda.device(dev):
+        bricks = torch.empty((Nz + 6) // 8, (Ny + 6) // 8, (Nx + 6) // 8, dtype=torch.uint8, device=dev)
+        assert bricks.numel() == lib.diner_tsdf_bricks_bytes(Nx, Ny, Nz)
+        _lib.check(lib.diner_tsdf_bricks(_ptr(tsdf), _ptr(wsum), Nx, Ny, Nz, float(min_weight), _ptr(bricks), _stream()))
+    return bricks
+
+
+def _check_tsdf_raycast_args(tsdf, wsum, color4, origin, voxel, intrinsics, extrinsics, W, H, znear, zfar, step, bricks):
+    """The argument checks of tsdf_raycast that need no device: -> (Nx, Ny, Nz, origin, V, host intrinsics, host extrinsics)."""
+    Nx, Ny, Nz, o = _check_volume("tsdf_raycast", tsdf, wsum, color4, origin, voxel)
+    V = int(extrinsics.shape[0]) if extrinsics.dim() == 3 else -1
+    if tuple(extrinsics.shape) != (V, 4, 4) or tuple(intrinsics.shape) != (V, 3, 3):
+        raise ValueError(f"diner_amd: tsdf_raycast expects extrinsics (V,4,4) and intrinsics (V,3,3), got {tuple(extrinsics.shape)}, "
+                         f"{tuple(intrinsics.shape)}")
+    if not 1 <= V <= _lib.MAX_VIEWS:
+        raise ValueError(f"diner_amd: tsdf_raycast takes 1 .. {_lib.MAX_VIEWS} views a call, got {V}")
+    if int(H) < 1 or int(W) < 1:
+        raise ValueError(f"diner_amd: tsdf_raycast got an empty image {H} x {W}")
+    znear, zfar, step = float(znear), float(zfar), float(step)
+    if not (step > 0.0 and np.isfinite(step)):
+        raise ValueError(f"diner_amd: tsdf_raycast step {step} must be > 0 and finite")
+    if not znear >= 0.0:
+        raise ValueError(f"diner_amd: tsdf_raycast znear {znear} must be >= 0")
+    if not (np.isfinite(zfar) and zfar > znear):
+        raise ValueError(f"diner_amd: tsdf_raycast zfar {zfar} must be finite and > znear {znear}")
+    if bricks is not None and (bricks.dtype != torch.uint8 or tuple(bricks.shape) != ((Nz + 6) // 8, (Ny + 6) // 8, (Nx + 6) // 8)):
+        raise ValueError(f"diner_amd: tsdf_raycast expects bricks uint8 {((Nz + 6) // 8, (Ny + 6) // 8, (Nx + 6) // 8)} (tsdf_bricks), got "
+                         f"{bricks.dtype} {tuple(bricks.shape)}")
+    Km = intrinsics.detach().to("cpu", torch.float32).contiguous()
+    E = extrinsics.detach().to("cpu", torch.float32).contiguous()
+    return Nx, Ny, Nz, o, V, Km, E
+
+
+def tsdf_raycast(tsdf, wsum, color4, origin, voxel, intrinsics, extrinsics, W, H, znear, zfar, step, min_weight=0.0, bricks=None,
+                 want_normal=True, want_rgb=True, want_weight=True):
+    """Ray-cast a TSDF volume into V cameras (diner_tsdf_raycast_f32, one launch): tsdf, wsum (Nz,Ny,Nx), color4 (4,Nz,Ny,Nx) or None as
+    tsdf_integrate leaves them; intrinsics (V,3,3), extrinsics (V,4,4) world->camera (read on the host), 1 <= V <= 16.  Every pixel's ray
+    is sampled at camera depths z_n = n step / |d_c| (d_c the pixel's direction with z = 1), znear <= z_n <= zfar, with the trilinear
+    interpolant of tsdf; the first observed negative sample ends the march, a hit iff the sample before it was observed too.
+    -> TsdfRaycast(zdepth (V,H,W) camera z, 0 = miss; normal (V,3,H,W) camera frame, facing the camera; rgb (V,3,H,W), None without
+    color4; weight (V,H,W) the interpolated wsum), each None when not wanted.  bricks: tsdf_bricks of the same planes and min_weight --
+    the march jumps over bricks no ray can end in; the outputs are the same bits with and without it."""
+    Nx, Ny, Nz, o, V, Km, E = _check_tsdf_raycast_args(tsdf, wsum, color4, origin, voxel, intrinsics, extrinsics, W, H, znear, zfar, step,
+                                                       bricks)
+    _require_volume("tsdf_raycast", tsdf, wsum, color4)
+    if bricks is not None and not (bricks.is_cuda and bricks.is_contiguous()):
+        raise RuntimeError("diner_amd: tsdf_raycast expects the brick mask contiguous on the HIP device; there is no CPU fallback")
+    dev = tsdf.device
+    H, W = int(H), int(W)
+    with torch.cuda.device(dev):
+        zdepth = torch.empty(V, H, W, dtype=torch.float32, device=dev)
+        normal = torch.empty(V, 3, H, W, dtype=torch.float32, device=dev) if want_normal else None
+        rgb = torch.empty(V, 3, H, W, dtype=torch.float32, device=dev) if want_rgb and color4 is not None else None
+        weight = torch.empty(V, H, W, dtype=torch.float32, device=dev) if want_weight else None
+        _lib.check(lib.diner_tsdf_raycast_f32(_ptr(tsdf), _ptr(wsum), _ptr(color4), Nx, Ny, Nz, o, float(voxel), _ptr(bricks), Km.data_ptr(),
+                                              E.data_ptr(), V, H, W, float(znear), float(zfar), float(step), float(min_weight),
+                                              _ptr(zdepth), _ptr(normal), _ptr(rgb), _ptr(weight), _stream()))
+    return TsdfRaycast(zdepth, normal, rgb, weight)
+
+
 def gen_rays(extrinsics, intrinsics, W, H, z_near, z_far, device, ray0=0, n_rays=None):
     """Reference src/util/cam_geometry.py:5-48 on the device: rays [ray0, ray0+n_rays) of each camera's row-major
     (H, W) list -> (B, n_rays, 8).  Camera tensors may live anywhere (they are read on the host: B x 27 floats)."""

@@ -8,8 +8,11 @@
     mesh, vol, views = mesh_from_views(nerf, renderer, Es, Ks, W, H, znear, zfar)   # the model's surface: rendered z-depth of V views
     mesh, vol = mesh_from_sources(batch)                                             # the prior's surface: the source depth maps, no MLP
 
-Fusing and meshing are HIP kernels (ops.tsdf_integrate, ops.surface_extract: surface.hip); choosing the box is torch on the device --
-once per mesh, not a hot path -- and the PLY writer is numpy on the host."""
+    maps = vol.raycast(Es, Ks, W, H)                                          # the volume seen by any cameras: zdepth, normal, rgb, ...
+    src, vol = sources_through_volume(batch)                                  # view-consistent, hole-filled source depth maps
+
+Fusing, meshing and ray-casting are HIP kernels (ops.tsdf_integrate, ops.surface_extract: surface.hip; ops.tsdf_raycast, ops.tsdf_bricks:
+raycast.hip); choosing the box is torch on the device -- once per mesh, not a hot path -- and the PLY writer is numpy on the host."""
 import collections
 
 import numpy as np
@@ -93,6 +96,47 @@ class TsdfVolume:
         from . import ops
         m = ops.surface_extract(self.tsdf, self.wsum, self.color4, self.origin, self.voxel, min_weight=min_weight)
         return Mesh(m.vertices, m.normals, None if m.rgb is None else _quantize_u8(m.rgb), m.faces)
+
+
+    def raycast(self, extrinsics, intrinsics, W, H, znear=0.0, zfar=None, step=None, min_weight=0.0, accelerate=True):
+        """The volume seen by V cameras (any V; 16 views per kernel call, in view order): extrinsics (V,4,4) world->camera, intrinsics
+        (V,3,3) or one (3,3).  zfar None: each camera's distance to the farthest corner of the box; step None: voxel / 2; accelerate:
+        build the brick mask once and let the march jump over the bricks no ray can end in (the same bits either way).
+        -> dict in predict_geometry's names and layouts: zdepth (V,1,H,W) camera z with 0 = no surface, normal (V,3,H,W) camera frame
+        and facing the camera (also under predict_geometry's key "normals"), rgb (V,3,H,W) or None for a volume without colour planes,
+        weight (V,1,H,W) the interpolated wsum, valid (V,1,H,W) bool = zdepth > 0, points (V,3,H,W) = backproject(zdepth), extrinsics."""
+        from . import ops
+        if extrinsics.dim() != 3 or tuple(extrinsics.shape[1:]) != (4, 4) or extrinsics.shape[0] < 1:
+            raise ValueError(f"diner_amd: TsdfVolume.raycast expects extrinsics (V,4,4) with V >= 1, got {tuple(extrinsics.shape)}")
+        V = int(extrinsics.shape[0])
+        if intrinsics.dim() == 2:
+            intrinsics = intrinsics[None].expand(V, -1, -1)
+        if tuple(intrinsics.shape) != (V, 3, 3):
+            raise ValueError(f"diner_amd: TsdfVolume.raycast expects intrinsics ({V},3,3) or (3,3), got {tuple(intrinsics.shape)}")
+        E = extrinsics.detach().to("cpu", torch.float32)
+        Km = intrinsics.detach().to("cpu", torch.float32)
+        step = 0.5 * self.voxel if step is None else float(step)
+        if zfar is None:
+            hi = self.origin + (torch.tensor(self.dims, dtype=torch.float32) - 1.0) * self.voxel
+            box = torch.stack([torch.stack([(self.origin, hi)[(c >> a) & 1][a] for a in range(3)]) for c in range(8)])
+            eye = -torch.einsum("vba,vb->va", E[:, :3, :3], E[:, :3, 3])
+            zfars = (box[None] - eye[:, None]).norm(dim=-1).max(dim=1).values.tolist()
+        else:
+            zfars = [float(zfar)] * V
+        bricks = ops.tsdf_bricks(self.tsdf, self.wsum, min_weight) if accelerate else None
+        parts = []
+        for a in range(0, V, MAX_VIEWS_PER_CALL):
+            b = min(V, a + MAX_VIEWS_PER_CALL)
+            # one zfar a launch: the farthest of its cameras (a longer march changes no hit)
+            parts.append(ops.tsdf_raycast(self.tsdf, self.wsum, self.color4, self.origin, self.voxel, Km[a:b], E[a:b], W, H, znear,
+                                          max(zfars[a:b]), step, min_weight=min_weight, bricks=bricks))
+        zdepth = torch.cat([p.zdepth for p in parts])[:, None]
+        normal = torch.cat([p.normal for p in parts])
+        dev = self.device
+        return {"zdepth": zdepth, "normal": normal, "normals": normal,
+                "rgb": None if self.color4 is None else torch.cat([p.rgb for p in parts]),
+                "weight": torch.cat([p.weight for p in parts])[:, None], "valid": zdepth > 0,
+                "points": backproject(zdepth, Km.to(dev), E.to(dev)), "extrinsics": extrinsics}
 
 
 def _volume_for(lo, hi, grow, voxel, trunc):
@@ -259,3 +303,33 @@ def read_mesh_ply(path):
         raise ValueError(f"diner_amd: {path}: no x y z properties")
     return Mesh(xyz, cols(("nx", "ny", "nz"), np.float32), cols(("red", "green", "blue"), np.uint8),
                 np.ascontiguousarray(frec["v"]).astype(np.int32, copy=False).reshape(F, 3))
+
+
+@torch.no_grad()
+def sources_through_volume(batch, sb=0, bounds=None, voxel=None, trunc=None, carve=False, min_weight=0.0, device=None):
+    """View-consistent, hole-filled source depth maps in the encoder's unit: fuse src_depths / src_rgbs of object `sb` of a collated
+    sample as mesh_from_sources does -- but carve=False by default: a hole must not vote free space -- and ray-cast the volume back
+    into every source camera.  -> (dict, TsdfVolume); the dict holds src_depths (NV,1,H,W) the cast z-depth (0 = the volume shows no
+    surface there), src_normals (NV,3,H,W) camera frame and facing the camera, filled (NV,1,H,W) bool: the original was 0 and the cast
+    hit, agree (NV,1,H,W) bool: both are positive and |cast - original| <= trunc.  Feeding them to `encode` is the caller's choice."""
+    device = torch.device("cuda" if device is None else device)
+    if device.type != "cuda":
+        raise RuntimeError(f"diner_amd: sources_through_volume runs on a HIP device, not on {device}; there is no CPU fallback")
+    depth = batch["src_depths"][sb].to(device, torch.float32)
+    rgb = batch["src_rgbs"][sb].to(device, torch.float32)
+    Km, E = batch["src_intrinsics"][sb].to(torch.float32), batch["src_extrinsics"][sb].to(torch.float32)
+    if depth.dim() != 4 or depth.shape[1] != 1 or tuple(rgb.shape) != (depth.shape[0], 3) + tuple(depth.shape[2:]):
+        raise ValueError(f"diner_amd: sources_through_volume expects src_depths (SB,NV,1,H,W) and src_rgbs (SB,NV,3,H,W), got "
+                         f"{tuple(batch['src_depths'].shape)}, {tuple(batch['src_rgbs'].shape)}")
+    if bounds is None:
+        lo, hi = _bounds_of(backproject(depth, Km, E), depth > 0)
+    else:
+        lo, hi = bounds
+    origin, voxel, dims = _volume_for(lo, hi, bounds is None, voxel, trunc)
+    vol = TsdfVolume(origin, voxel, dims, trunc=trunc, color=True, device=device)
+    vol.integrate(depth, Km, E, rgb=rgb, carve=carve)
+    H, W = (int(n) for n in depth.shape[-2:])
+    cast = vol.raycast(E, Km, W, H, min_weight=min_weight)
+    z = cast["zdepth"]
+    return {"src_depths": z, "src_normals": cast["normal"], "filled": (depth == 0) & (z > 0),
+            "agree": (depth > 0) & (z > 0) & ((z - depth).abs() <= vol.trunc)}, vol

@@ -652,6 +652,54 @@ int diner_surface_extract_f32(const float* tsdf, const float* wsum, const float*
                               float voxel, float min_weight, void* workspace, int n_vertices, int n_quads, float* vertices_out,
                               float* normals_out, float* rgb_out, int* faces_out, void* stream);
 
+/* ---- ray-casting the TSDF volume: z-depth, normals, colour and confidence maps of any cameras ------------------------------------------
+ * New symbols without an ABI bump (raycast.hip); no allocation, no LDS, no atomics, no barrier, one launch each, enqueue-only; every
+ * output byte is a function of the inputs alone; bad arguments return DINER_E_INVALID with a message before any device work.
+ *
+ * The volume is the one above: sample (i, j, k) at origin + (i, j, k) voxel, origin (3 floats) on the HOST, planes (Nz, Ny, Nx) fp32;
+ * a corner is OBSERVED iff wsum > min_weight and NEGATIVE iff tsdf < 0 (an exact 0 and a NaN are positive).
+ *
+ * diner_tsdf_raycast_f32: one thread per ray, a wavefront per 8 x 8 pixel tile.  intrinsics (V,3,3) and extrinsics (V,4,4) world->camera
+ *   (R, t) are HOST arrays (kernel arguments), 1 <= V <= DINER_MAX_VIEWS.  Every fp32 operation below is rounded once, in this order.
+ *     The ray of pixel (r, c): dcx = ((c + 0.5) - cx) / fx, dcy = ((r + 0.5) - cy) / fy, d_c = (dcx, dcy, 1);
+ *   eye_a = -((R[0][a] t0 + R[1][a] t1) + R[2][a] t2); d_w,a = (R[0][a] dcx + R[1][a] dcy) + R[2][a]; the point at camera depth z is
+ *   p_a(z) = eye_a + z d_w,a: the march is parametrised by camera z, the unit of the source depth maps.
+ *     The samples sit on a lattice anchored at the camera: dz = step / sqrt((dcx dcx + dcy dcy) + 1), `step` a world length;
+ *   z_n = (float)n dz for n = 1, 2, ... while z_n <= zfar -- a product, never a running sum.
+ *     Sampling: g_a = (p_a(z_n) - origin_a) / voxel.  The sample is INSIDE iff 0 <= g_a <= N_a - 1 on every axis and z_n >= znear; its
+ *   cell is min(floor g_a, N_a - 2) per axis and its fraction m_a = g_a - cell_a; it is OBSERVED iff it is inside and the 8 corners of
+ *   the cell are observed; f_n = the trilinear interpolant of tsdf over the cell's corners at m, along x, then y, then z, each lerp as
+ *   a + w (b - a).  (Sample 0, the eye, is never observed.)
+ *     Termination: the first observed sample with f_n < 0 ends the march.  It is a HIT iff sample n - 1 was observed too (its f is then
+ *   not negative); otherwise -- a solid met from behind, or out of unknown space -- and when the lattice runs out, the ray is a MISS.
+ *     A hit's depth: z = z_(n-1) + dz (f_(n-1) / (f_(n-1) - f_n)).  Its attributes are taken at p(z), in the cell p(z) falls in
+ *   (floor g clamped to 0 .. N - 2), with no observedness test there:
+ *       normal = R n_w, n_w = grad / |grad| of the trilinear interpolant there (d/dx = the four x-differences of the corners, lerped along y
+ *         then z; likewise y over (x, z) and z over (x, y); |grad| = sqrt((gx gx + gy gy) + gz gz); row a of R n_w =
+ *         (R[a][0] n0 + R[a][1] n1) + R[a][2] n2): the camera frame, towards free space, hence facing the camera; 0 where |grad| is
+ *         not positive;
+ *       rgb = trilinear(sum w c) / trilinear(sum w), 0 where the denominator is not positive (diner_surface_extract_f32's rule);
+ *       weight = trilinear(wsum).
+ *   A miss writes 0 to every output.  zdepth_out (V,H,W); normal_out (V,3,H,W), rgb_out (V,3,H,W), weight_out (V,H,W) or NULL; rgb_out
+ *   needs color4.  A NaN interpolant is not negative and does not end a march; as f_(n-1) it makes the hit's depth a NaN.
+ *     Only the sample positions are fixed: a thread starts at the first lattice index that can be inside the box (a slab test widened
+ *   by its own rounding), may stop past the exit, and -- given `bricks` -- jumps over lattice samples whose cell lies in a 0-brick,
+ *   landing at or before the first sample outside it.  The terminating sample's predecessor is evaluated afresh, so the outputs with
+ *   and without `bricks` are the same bits.  The loop is bounded by a trip count computed on the host: a call with more than 2^20
+ *   lattice samples on any ray (zfar |d_c| / step at the steepest pixel) is refused, as are V outside 1 .. 16, a dimension outside
+ *   2 .. 1024, voxel <= 0, step <= 0 or not finite, znear < 0, zfar not finite or <= znear, and a null required pointer.
+ * diner_tsdf_bricks: bricks_out (device bytes, diner_tsdf_bricks_bytes of them) = one byte per brick of 8^3 cells, brick (bx, by, bz) at
+ *   (bz nby + by) nbx + bx with nb_a = ceil((N_a - 1) / 8): 1 iff some cell of the brick has all 8 corners observed and at least one
+ *   negative.  It must be built from the same planes and min_weight as the ray-cast that is given it.
+ * diner_tsdf_bricks_bytes: the size of that buffer (0 for dimensions the entries refuse). */
+size_t diner_tsdf_bricks_bytes(int Nx, int Ny, int Nz);
+int diner_tsdf_bricks(const float* tsdf, const float* wsum, int Nx, int Ny, int Nz, float min_weight, unsigned char* bricks_out,
+                      void* stream);
+int diner_tsdf_raycast_f32(const float* tsdf, const float* wsum, const float* color4, int Nx, int Ny, int Nz, const float* origin,
+                           float voxel, const unsigned char* bricks, const float* intrinsics, const float* extrinsics, int V, int H, int W,
+                           float znear, float zfar, float step, float min_weight, float* zdepth_out, float* normal_out, float* rgb_out,
+                           float* weight_out, void* stream);
+
 /* ---- measurement aid (bench.py): per-kernel durations of the two field kernels ------------------
  * With profiling enabled every field call brackets k_field_pre / k_field_post with HIP events on the
  * launch stream; diner_profile_collect waits for them, returns the summed durations (ms), the number

@@ -17,6 +17,7 @@
 #   cull-time [args]           tools/time_cull.py: an 800 x 600 K = 128 frame with and without cull_empty, alternating, at the scene's own and at half the focal length (stdout; keep it as profiles/cull_frame_ab.txt)
 #   geometry-time [args]       tools/time_geometry.py: an 800 x 600 K = 128 frame through predict_geometry and through predict_image(return_alpha=True), alternating, and the two geometry kernels on their own (stdout)
 #   surface-time [args]        tools/time_surface.py: a 256^3 colour volume fused from sixteen 800 x 600 views (one call / sixteen), count + extract on it, and one 800 x 600 mesh_from_sources (stdout)
+#   raycast-time [args]        tools/time_raycast.py: that 256^3 volume cast back into one and into sixteen 800 x 600 cameras, with and without the brick mask, and the brick build alone (stdout)
 #   smoke                      __graft_entry__.smoke()
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}" || exit 1
 mkdir -p gpurun_out
@@ -79,6 +80,9 @@ PY
   surface-time)
     set -o pipefail
     timeout -k 10 500 python tools/time_surface.py "$@" 2>&1 | grep -v amdgpu.ids ;;
+  raycast-time)
+    set -o pipefail
+    timeout -k 10 500 python tools/time_raycast.py "$@" 2>&1 | grep -v amdgpu.ids ;;
   smoke) python __graft_entry__.py smoke ;;
   *) echo "unknown job '$job' (see the header of tools/job.sh)"; exit 2 ;;
 esac
