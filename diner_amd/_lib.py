@@ -186,6 +186,15 @@ SIGNATURES = {
     "diner_tsdf_raycast_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_float, C.c_void_p,
                                          C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float,
                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "diner_cloud_grid_bytes": (C.c_size_t, [C.c_longlong, C.c_int, C.c_int, C.c_int]),
+    "diner_cloud_grid_order_offset": (C.c_size_t, [C.c_longlong, C.c_int, C.c_int, C.c_int]),
+    "diner_cloud_grid_build_f32": (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_float, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                             C.c_void_p]),
+    "diner_cloud_nearest_f32": (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_float, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                          C.c_longlong, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "diner_cloud_reduce_workspace_bytes": (C.c_size_t, [C.c_longlong]),
+    "diner_cloud_reduce_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_float, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                         C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 ABI_VERSION = 6          # DINER_ABI_VERSION of include/diner_hip.h

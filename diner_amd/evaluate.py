@@ -33,6 +33,9 @@ VNORMAL_SUFFIX = "-vnormal.png"
 AVERAGE_SCORE_FILENAME = "average_scores.json"
 REPORT_DETAIL_FILENAME = "detailed_report.json"
 EXAMPLE_PLOT_FILENAME = "examples.png"
+GT_PLY_SUFFIX = "-gt.ply"
+GEOMETRY_SCORE_FILENAME = "geometry_scores.json"
+GEOMETRY_REPORT_FILENAME = "geometry_report.json"
 N_EXAMPLE_PLOTS = 5
 BATCH = 16                       # same-sized pairs scored per kernel call
 
@@ -214,11 +217,90 @@ def evaluate_folder(source_dir, outdir, device=None, pred_suffix=PRED_SUFFIX, gt
     return avg
 
 
-def main(argv=None):
+def _check_geometry_args(max_dist, thresholds, thin):
+    max_dist = float(max_dist)
+    if not max_dist > 0.0:
+        raise ValueError(f"evaluate_geometry_folder: max_dist {max_dist} must be > 0 (inf: no cap)")
+    thresholds = tuple(float(t) for t in thresholds)
+    if len(thresholds) > 8 or not all(t >= 0.0 for t in thresholds):
+        raise ValueError(f"evaluate_geometry_folder: at most 8 thresholds, each >= 0, got {thresholds}")
+    if thin is not None and not (float(thin) > 0.0 and np.isfinite(float(thin))):
+        raise ValueError(f"evaluate_geometry_folder: thin {thin} must be > 0 and finite")
+    return max_dist, thresholds
+
+
+@torch.no_grad()
+def evaluate_geometry_folder(source_dir, outdir, pred_suffix=PLY_SUFFIX, gt_suffix=GT_PLY_SUFFIX, max_dist=float("inf"), thresholds=(),
+                             thin=None, device=None, mesh_suffix=MESH_SUFFIX):
+    """Score every <x>{gt_suffix} / <x>{pred_suffix} pair of point clouds in `source_dir` (sorted by file name; geometry.read_ply) with
+    diner_amd.cloudmetrics.cloud_scores on the HIP device `device` (None: the current one); where <x>{mesh_suffix} exists
+    (surface.read_mesh_ply) it is scored by its vertices as well, under keys prefixed "mesh_".  Normals take part where both files carry
+    them.  Writes GEOMETRY_SCORE_FILENAME (the averages over the pairs that have the key; nan scores are averaged as nan) and
+    GEOMETRY_REPORT_FILENAME (per pair) into `outdir` and returns the averages."""
+    max_dist, thresholds = _check_geometry_args(max_dist, thresholds, thin)
+    source_dir, outdir = Path(source_dir), Path(outdir)
+    gt_paths = [p for p in sorted(source_dir.iterdir()) if p.name.endswith(gt_suffix)]
+    if not gt_paths:
+        raise FileNotFoundError(f"evaluate_geometry_folder: no *{gt_suffix} files in {source_dir}")
+    device = _hip_device(device)
+    from .cloudmetrics import cloud_scores
+    from .geometry import read_ply
+    from .surface import read_mesh_ply
+    os.makedirs(outdir, exist_ok=True)
+
+    def up(a):
+        return None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to(device)
+
+    def numbers(s, prefix=""):
+        return {prefix + k: v for k, v in s.items() if isinstance(v, (int, float))}
+
+    report = []
+    for gp in gt_paths:
+        stem = gp.name[:-len(gt_suffix)]
+        pp = gp.parent / (stem + pred_suffix)
+        gt_xyz, _, gt_n = read_ply(gp)
+        xyz, _, nrm = read_ply(pp)
+        kw = dict(max_dist=max_dist, thresholds=thresholds, thin=thin)
+        both = gt_n is not None and nrm is not None
+        row = dict(path=str(pp), **numbers(cloud_scores(up(xyz), up(gt_xyz), pred_normals=up(nrm) if both else None,
+                                                        gt_normals=up(gt_n) if both else None, **kw)))
+        mp = gp.parent / (stem + mesh_suffix)
+        if mp.exists():
+            mesh = read_mesh_ply(mp)
+            both = gt_n is not None and mesh.normals is not None
+            row.update(numbers(cloud_scores(up(mesh.vertices), up(gt_xyz), pred_normals=up(mesh.normals) if both else None,
+                                            gt_normals=up(gt_n) if both else None, **kw), "mesh_"))
+        report.append(row)
+    keys = sorted({k for row in report for k in row if k != "path"})
+    avg = {k: float(np.mean([row[k] for row in report if k in row])) for k in keys}
+    with open(outdir / GEOMETRY_SCORE_FILENAME, "w") as f:
+        json.dump(avg, f, indent="\t")
+    with open(outdir / GEOMETRY_REPORT_FILENAME, "w") as f:
+        json.dump(report, f, indent="\t")
+    return avg
+
+
+def _parser():
     ap = argparse.ArgumentParser(description="Score the predictions of DIR/visualizations on the device; reports go to DIR.")
     ap.add_argument("--eval_path", type=Path, required=True)
-    args = ap.parse_args(argv)
-    avg = evaluate_folder(args.eval_path / "visualizations", args.eval_path, show_tqdm=True)
+    ap.add_argument("--geometry", action="store_true",
+                    help="also score the <stem>.ply / <stem>-mesh.ply geometry against <stem>-gt.ply (instead, where there are no images)")
+    ap.add_argument("--max_dist", type=float, default=float("inf"), help="--geometry: distances beyond it are outliers")
+    ap.add_argument("--threshold", type=float, action="append", default=[], help="--geometry: a precision / recall / F-score distance")
+    ap.add_argument("--thin", type=float, default=None, help="--geometry: keep one point per cell of this size")
+    return ap
+
+
+def main(argv=None):
+    args = _parser().parse_args(argv)
+    source = args.eval_path / "visualizations"
+    if not args.geometry:
+        avg = evaluate_folder(source, args.eval_path, show_tqdm=True)
+    else:
+        avg = {}
+        if any(p.name.endswith(GT_SUFFIX) for p in source.iterdir()):
+            avg.update(evaluate_folder(source, args.eval_path, show_tqdm=True))
+        avg.update(evaluate_geometry_folder(source, args.eval_path, max_dist=args.max_dist, thresholds=args.threshold, thin=args.thin))
     print(json.dumps(avg, indent="\t"))
 
 

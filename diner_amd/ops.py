@@ -960,6 +960,131 @@ def tsdf_raycast(tsdf, wsum, color4, origin, voxel, intrinsics, extrinsics, W, H
     return TsdfRaycast(zdepth, normal, rgb, weight)
 
 
+CLOUD_MAX_DIM = 1024
+CLOUD_MAX_CELLS = 1 << 26
+CLOUD_MAX_THRESHOLDS = 8
+CLOUD_REDUCE_OUT = 3 + CLOUD_MAX_THRESHOLDS
+# xyz: the target cloud the grid was built over; ws: its workspace; lo: the box corner (3 host floats); order: the target's indices in cell order
+CloudGridData = collections.namedtuple("CloudGridData", "xyz ws lo cell dims order")
+
+
+def _check_cloud(who, name, xyz):
+    if not torch.is_tensor(xyz) or xyz.dim() != 2 or xyz.shape[1] != 3:
+        raise ValueError(f"diner_amd: {who} expects {name} (N,3), got {tuple(xyz.shape) if torch.is_tensor(xyz) else type(xyz).__name__}")
+    if not 1 <= xyz.shape[0] < 2 ** 31:
+        raise ValueError(f"diner_amd: {who} takes 1 .. 2^31 - 1 points, {name} has {xyz.shape[0]}")
+    if xyz.dtype != torch.float32:
+        raise ValueError(f"diner_amd: {who} expects {name} float32, got {xyz.dtype}")
+    return int(xyz.shape[0])
+
+
+def _check_max_dist(who, max_dist):
+    max_dist = float(max_dist)
+    if not max_dist > 0.0:
+        raise ValueError(f"diner_amd: {who} max_dist {max_dist} must be > 0 (inf: no cap)")
+    return max_dist
+
+
+def _check_cloud_grid_args(xyz_b, lo, cell, dims):
+    """The argument checks of cloud_grid that need no device: -> (NB, lo as three host floats, cell, (Gx, Gy, Gz))."""
+    NB = _check_cloud("cloud_grid", "xyz_b", xyz_b)
+    o = torch.as_tensor(lo, dtype=torch.float32).detach().to("cpu").reshape(-1)
+    if o.numel() != 3 or not bool(torch.isfinite(o).all()):
+        raise ValueError(f"diner_amd: cloud_grid lo must be three finite values, got {o.tolist()}")
+    cell = float(cell)
+    if not (cell > 0.0 and np.isfinite(cell)):
+        raise ValueError(f"diner_amd: cloud_grid cell size {cell} must be > 0 and finite")
+    dims = tuple(int(g) for g in dims)
+    if len(dims) != 3 or not all(1 <= g <= CLOUD_MAX_DIM for g in dims) or dims[0] * dims[1] * dims[2] > CLOUD_MAX_CELLS:
+        raise ValueError(f"diner_amd: cloud_grid dims (Gx,Gy,Gz) must be 1 .. {CLOUD_MAX_DIM} a side and at most 2^26 cells, got {dims}")
+    return NB, (C.c_float * 3)(*o.tolist()), cell, dims
+
+
+def cloud_grid(xyz_b, lo, cell, dims):
+    """A uniform grid over the target cloud xyz_b (NB,3) float32 on the HIP device (diner_cloud_grid_build_f32): a box at `lo` of
+    dims = (Gx,Gy,Gz) cubic cells of side `cell`; points outside fall into the outermost cells, points with a non-finite coordinate into
+    none.  -> CloudGridData for cloud_nearest; .order (NB,) int32 are the target's indices sorted by cell (a permutation)."""
+    NB, o, cell, dims = _check_cloud_grid_args(xyz_b, lo, cell, dims)
+    _require_hip(xyz_b)
+    xyz_b = xyz_b.detach().contiguous()
+    dev = xyz_b.device
+    with torch.cuda.device(dev):
+        ws = _workspace(lib.diner_cloud_grid_bytes(NB, *dims), dev)
+        _lib.check(lib.diner_cloud_grid_build_f32(_ptr(xyz_b), NB, o, cell, *dims, _ptr(ws), _stream()))
+    at = lib.diner_cloud_grid_order_offset(NB, *dims)
+    return CloudGridData(xyz_b, ws, o, cell, dims, ws[at:at + 4 * NB].view(torch.int32))
+
+
+def _check_cloud_nearest_args(grid, xyz_a, max_dist, order):
+    if not isinstance(grid, CloudGridData):
+        raise ValueError(f"diner_amd: cloud_nearest expects the CloudGridData of cloud_grid, got {type(grid).__name__}")
+    NA = _check_cloud("cloud_nearest", "xyz_a", xyz_a)
+    if order is not None and (not torch.is_tensor(order) or order.dtype != torch.int32 or tuple(order.shape) != (NA,)):
+        raise ValueError(f"diner_amd: cloud_nearest expects order int32 ({NA},), a permutation of the queries")
+    return NA, _check_max_dist("cloud_nearest", max_dist)
+
+
+def cloud_nearest(grid, xyz_a, max_dist=float("inf"), order=None):
+    """The nearest target point of every query (diner_cloud_nearest_f32, one launch): xyz_a (NA,3) float32 on the grid's device ->
+    (d2 (NA,) float32, idx (NA,) int32).  d2 = (dx dx + dy dy) + dz dz in fp32; only targets with d2 <= max_dist^2 (fp32) count; the smaller
+    d2 wins, equal d2 the smaller index; nothing within max_dist, or a non-finite query: idx -1, d2 inf.  The result equals exhaustive
+    search bit for bit.  order (NA,) int32, a permutation: the order in which the threads take the queries (the .order of a grid over
+    xyz_a makes neighbouring threads walk the same cells); it changes no output."""
+    NA, max_dist = _check_cloud_nearest_args(grid, xyz_a, max_dist, order)
+    _require_hip(xyz_a)
+    if xyz_a.device != grid.xyz.device or (order is not None and order.device != grid.xyz.device):
+        raise RuntimeError("diner_amd: cloud_nearest expects the queries and their order on the grid's device")
+    xyz_a = xyz_a.detach().contiguous()
+    order = None if order is None else order.contiguous()
+    dev = xyz_a.device
+    with torch.cuda.device(dev):
+        d2 = torch.empty(NA, dtype=torch.float32, device=dev)
+        idx = torch.empty(NA, dtype=torch.int32, device=dev)
+        _lib.check(lib.diner_cloud_nearest_f32(_ptr(grid.xyz), grid.xyz.shape[0], grid.lo, grid.cell, *grid.dims, _ptr(grid.ws), _ptr(xyz_a),
+                                               NA, _ptr(order), max_dist, _ptr(d2), _ptr(idx), _stream()))
+    return d2, idx
+
+
+def _check_cloud_reduce_args(d2, idx, max_dist, thresholds, normals_a, normals_b):
+    if not (torch.is_tensor(d2) and torch.is_tensor(idx)) or d2.dim() != 1 or d2.shape[0] < 1 or tuple(idx.shape) != tuple(d2.shape):
+        raise ValueError("diner_amd: cloud_reduce expects d2 (n,) and idx (n,) with n >= 1, as cloud_nearest returns them")
+    if d2.dtype != torch.float32 or idx.dtype != torch.int32:
+        raise ValueError(f"diner_amd: cloud_reduce expects d2 float32 and idx int32, got {d2.dtype}, {idx.dtype}")
+    taus = [float(t) for t in thresholds]
+    if len(taus) > CLOUD_MAX_THRESHOLDS or not all(t >= 0.0 for t in taus):
+        raise ValueError(f"diner_amd: cloud_reduce takes at most {CLOUD_MAX_THRESHOLDS} thresholds, each >= 0, got {taus}")
+    if (normals_a is None) != (normals_b is None):
+        raise ValueError("diner_amd: cloud_reduce takes the normals of both clouds or of neither")
+    if normals_a is not None:
+        if tuple(normals_a.shape) != (d2.shape[0], 3) or normals_b.dim() != 2 or normals_b.shape[1] != 3 or normals_b.shape[0] < 1:
+            raise ValueError(f"diner_amd: cloud_reduce expects normals_a ({d2.shape[0]},3) and normals_b (NB,3), got "
+                             f"{tuple(normals_a.shape)}, {tuple(normals_b.shape)}")
+        if normals_a.dtype != torch.float32 or normals_b.dtype != torch.float32:
+            raise ValueError("diner_amd: cloud_reduce expects float32 normals")
+    return int(d2.shape[0]), _check_max_dist("cloud_reduce", max_dist), taus
+
+
+def cloud_reduce(d2, idx, max_dist=float("inf"), thresholds=(), normals_a=None, normals_b=None):
+    """The sums of the distance scores over one direction (diner_cloud_reduce_f32): d2, idx (n,) of cloud_nearest -> a (11,) float64
+    device tensor {matched, sum of sqrt(d2) in double, sum of |n_a . n_b[idx]|, count with d2 <= tau^2 per threshold}.  An entry is matched
+    iff idx >= 0 and d2 <= max_dist^2.  Fixed summation order: two calls give the same bits."""
+    n, max_dist, taus = _check_cloud_reduce_args(d2, idx, max_dist, thresholds, normals_a, normals_b)
+    _require_hip(d2, normals_a, normals_b)
+    if not idx.is_cuda:
+        raise RuntimeError("diner_amd: cloud_reduce expects idx on the HIP device; there is no CPU fallback")
+    dev = d2.device
+    d2, idx = d2.contiguous(), idx.contiguous()
+    normals_a = None if normals_a is None else normals_a.detach().contiguous()
+    normals_b = None if normals_b is None else normals_b.detach().contiguous()
+    t = (C.c_float * CLOUD_MAX_THRESHOLDS)(*taus)
+    with torch.cuda.device(dev):
+        ws = _workspace(lib.diner_cloud_reduce_workspace_bytes(n), dev)
+        out = torch.empty(CLOUD_REDUCE_OUT, dtype=torch.float64, device=dev)
+        _lib.check(lib.diner_cloud_reduce_f32(_ptr(d2), _ptr(idx), n, max_dist, t, len(taus), _ptr(normals_a), _ptr(normals_b),
+                                              0 if normals_b is None else normals_b.shape[0], _ptr(ws), _ptr(out), _stream()))
+    return out
+
+
 def gen_rays(extrinsics, intrinsics, W, H, z_near, z_far, device, ray0=0, n_rays=None):
     """Reference src/util/cam_geometry.py:5-48 on the device: rays [ray0, ray0+n_rays) of each camera's row-major
     (H, W) list -> (B, n_rays, 8).  Camera tensors may live anywhere (they are read on the host: B x 27 floats)."""

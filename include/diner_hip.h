@@ -700,6 +700,49 @@ int diner_tsdf_raycast_f32(const float* tsdf, const float* wsum, const float* co
                            float znear, float zfar, float step, float min_weight, float* zdepth_out, float* normal_out, float* rgb_out,
                            float* weight_out, void* stream);
 
+/* ---- scoring clouds: nearest neighbour between two clouds through a uniform grid, and the sums the distance scores need ------------------
+ * New symbols without an ABI bump (cloud.hip); no allocation, enqueue-only; no floating-point atomics: every output byte is a function of
+ * the inputs alone (the order of the points inside a cell, which the integer atomics of the build decide, is never visible); bad
+ * arguments return DINER_E_INVALID with a message naming the argument before any device work.
+ *
+ * The grid is built over a TARGET cloud xyz_b (NB,3) fp32 on the device, 1 <= NB < 2^31: a box at lo (3 floats on the HOST) of
+ *   (Gx, Gy, Gz) cubic cells of side h, each side 1 .. DINER_CLOUD_MAX_DIM cells and at most DINER_CLOUD_MAX_CELLS in all.  The cell of a
+ *   point is clamp(floor((p_a - lo_a) / h), 0, G_a - 1) per axis, each operation rounded in fp32; cell (i, j, k) is number
+ *   (k Gy + j) Gx + i.  A target point with a non-finite coordinate goes into no cell and is never anybody's neighbour.
+ * diner_cloud_grid_bytes: the size of the grid's workspace (0 for sizes the entries refuse).
+ * diner_cloud_grid_build_f32: a counting sort of the target's indices by cell into `workspace` (16-byte aligned): count (32-bit integer
+ *   atomics), exclusive scan, scatter through per-cell cursors.  The non-finite points are sorted behind the last cell, so the sorted
+ *   indices -- NB int32 at byte diner_cloud_grid_order_offset of the workspace -- are a permutation of 0 .. NB - 1 in cell order.
+ * diner_cloud_nearest_f32: one thread per query of xyz_a (NA,3), 1 <= NA < 2^31, against the grid built from the same xyz_b, lo, h and
+ *   dims.  The squared distance to a target point is d2 = (dx dx + dy dy) + dz dz, every operation rounded in fp32.  A target point is a
+ *   CANDIDATE iff d2 <= max_dist max_dist (the product rounded in fp32; max_dist > 0 or +inf).  Of two candidates the smaller d2 wins,
+ *   equal d2 the smaller index.  d2_out (NA) is the winner's d2, idx_out (NA) its index in xyz_b; no candidate, or a query with a
+ *   non-finite coordinate: idx -1, d2 +inf.  The search walks Chebyshev rings of cells around the query's (unclamped) cell and stops
+ *   once no unvisited cell can hold a candidate that beats the best found -- a bound evaluated in double and shrunk by more than the
+ *   binning's rounding -- so the outputs equal exhaustive search bit for bit whatever the box and the cell size.  `order` (NA int32 on
+ *   the device, or NULL) is the order in which the threads take the queries: thread t answers query order[t] (entries outside
+ *   0 .. NA - 1 are skipped); it must be a permutation and changes no output.
+ * diner_cloud_reduce_f32: over the n entries of (d2, idx) that are MATCHED -- idx >= 0 and d2 <= max_dist max_dist -- out (device,
+ *   DINER_CLOUD_REDUCE_OUT doubles) = { the number matched, the sum of sqrt((double)d2), the sum of |n_a[i] . n_b[idx[i]]| (the dot
+ *   product in double, (x + y) + z; 0 unless both normal arrays, (n,3) and (nb_rows,3), are given; an index >= nb_rows adds 0), then per threshold
+ *   t < T <= 8 the number matched with d2 <= tau_t tau_t (fp32 product; thresholds: T floats on the HOST) }.  Sums run per thread in index
+ *   order, then over the workgroup, then over the workgroups in a fixed order: two runs give the same bits.  workspace:
+ *   diner_cloud_reduce_workspace_bytes(n) bytes (0 for n < 1). */
+#define DINER_CLOUD_MAX_DIM 1024
+#define DINER_CLOUD_MAX_CELLS (1 << 26)
+#define DINER_CLOUD_MAX_THRESHOLDS 8
+#define DINER_CLOUD_REDUCE_OUT (3 + DINER_CLOUD_MAX_THRESHOLDS)
+size_t diner_cloud_grid_bytes(long long NB, int Gx, int Gy, int Gz);
+size_t diner_cloud_grid_order_offset(long long NB, int Gx, int Gy, int Gz);
+int diner_cloud_grid_build_f32(const float* xyz_b, long long NB, const float* lo, float h, int Gx, int Gy, int Gz, void* workspace,
+                               void* stream);
+int diner_cloud_nearest_f32(const float* xyz_b, long long NB, const float* lo, float h, int Gx, int Gy, int Gz, const void* workspace,
+                            const float* xyz_a, long long NA, const int* order, float max_dist, float* d2_out, int* idx_out, void* stream);
+size_t diner_cloud_reduce_workspace_bytes(long long n);
+int diner_cloud_reduce_f32(const float* d2, const int* idx, long long n, float max_dist, const float* thresholds, int T,
+                           const float* normals_a, const float* normals_b, long long nb_rows, void* workspace, double* out,
+                           void* stream);
+
 /* ---- measurement aid (bench.py): per-kernel durations of the two field kernels ------------------
  * With profiling enabled every field call brackets k_field_pre / k_field_post with HIP events on the
  * launch stream; diner_profile_collect waits for them, returns the summed durations (ms), the number
