@@ -19,8 +19,7 @@ namespace diner {
 namespace train {
 
 constexpr int BM = 64, BN = 64, BK = 16, PAD = 4;
-enum : int { kTA = 1, kTB = 2, kReluA = 4, kReluB = 8, kAccum = 16, kAtomic = 32, kExact = 64,
-             kNoXcdOrder = 128 /* internal: plain blockIdx tile order (A/B measurement, DINER_TRAIN_NO_XCD=1) */ };
+enum : int { kTA = 1, kTB = 2, kReluA = 4, kReluB = 8, kAccum = 16, kAtomic = 32, kExact = 64 };
 
 struct GemmArgs {
   const float* A;       // op(A) is M x K: stored [M][lda] (or [K][lda] with kTA)
@@ -373,7 +372,7 @@ __global__ __launch_bounds__(256, 2) void k_gemm_bf16x6(GemmArgs g) {
   unsigned bx = blockIdx.x, by = blockIdx.y, bz = blockIdx.z;
   {
     const unsigned total = gridDim.x * gridDim.y * gridDim.z;
-    if (!(g.flags & kNoXcdOrder) && (total & 7) == 0) {
+    if ((total & 7) == 0) {
       const unsigned lin = (blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
       const unsigned logical = (lin & 7) * (total >> 3) + (lin >> 3);
       bx = logical % gridDim.x;
@@ -546,9 +545,9 @@ __global__ __launch_bounds__(256) void k_scatter_latent(const float* __restrict_
 // block of d_lat into LDS, (3) per distinct texel sums w * d_lat over that texel's taps -- independent LDS reads, no read-modify-write
 // chain (a first version accumulated into a (slot, channel) table in LDS: one dependent LDS round trip per tap) -- and adds the sum to the
 // texel with one atomic per channel.
-// round 6: COLS columns per workgroup as a template parameter (DINER_TRAIN_SCATTER_COLS: 64 columns stage 128 KB of d_lat in LDS = one
-// workgroup per CU, 32 / 16 columns let 2 / 4 share a CU); the map-space lin_z adjoint hands the columns over SORTED by texel (perm), where
-// 64 neighbours share a handful of texels.
+// round 6: COLS columns per workgroup as a template parameter (kScatterCols: 64 columns stage 128 KB of d_lat in LDS = one workgroup per
+// CU; 32 / 16 columns, 2 / 4 workgroups sharing a CU, measured slower); the map-space lin_z adjoint hands the columns over SORTED by texel
+// (perm), where 64 neighbours share a handful of texels.
 #ifdef DINER_L512_PROF
 __device__ unsigned long long g_scat_prof[8];      // clocks of thread 0 per phase: [0] load issue + taps, [1] wait for the block, [2] leaders .. sort, [3] sums + atomics, [4] workgroups
 #define SCAT_T(i) do { if (t == 0) { const unsigned long long now_ = __builtin_readcyclecounter(); atomicAdd(&g_scat_prof[i], now_ - pt_); pt_ = now_; } } while (0)
@@ -746,28 +745,28 @@ __global__ __launch_bounds__(256) void k_scatter_latent_merged(const float* __re
   __syncthreads();                                           // the block and the lists are free for the next trip
   }
 }
-template <int COLS>
+// same-box A/B, SB 4 step, round 6 (profiles/r06_train_scatter_*): 64 / 32 / 16 columns with the one-block workgroups of the first version 123.6 /
+// 121.9 / 122.2 ms; with sorted columns and the rewritten phases 102.2 / 102.7 / 108.5; 64 columns + one walking workgroup per CU 101.8
+constexpr int kScatterCols = 64;                        // columns per workgroup: 128 KB of d_lat in LDS
+constexpr int kScatterWgPerCu = 64 / kScatterCols;      // workgroups per CU walking the blocks (what LDS holds)
 static int scatter_merged_launch(const float* d_lat, const int* tap_row, const float* tap_w, long long cols, float* d_latent_cl, hipStream_t st,
                                  const int* perm) {
   static std::atomic<int> attr_set[64];
+  static std::atomic<int> cus[64];
   int dev = 0;
   DINER_HIP_OK(hipGetDevice(&dev));
   dev &= 63;
-  constexpr int lds = COLS * kLatent * (int)sizeof(float);      // the COLS x 512 block of d_lat
+  constexpr int lds = kScatterCols * kLatent * (int)sizeof(float);      // the block of d_lat
   if (!attr_set[dev].load()) {
-    DINER_HIP_OK(hipFuncSetAttribute((const void*)k_scatter_latent_merged<COLS>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    attr_set[dev].store(1);
-  }
-  static const int per_cu = [] { const char* e = getenv("DINER_TRAIN_SCATTER_WG_PER_CU"); return e ? atoi(e) : 64 / COLS; }();      // workgroups per CU walking the blocks (what LDS holds); 0: a workgroup per block (no walk)
-  static std::atomic<int> cus[64];
-  if (per_cu > 0 && !cus[dev].load()) {
+    DINER_HIP_OK(hipFuncSetAttribute((const void*)k_scatter_latent_merged<kScatterCols>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
     int c = 0;
     DINER_HIP_OK(hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, dev));
     cus[dev].store(c > 0 ? c : 256);
+    attr_set[dev].store(1);
   }
-  const long long nblk = (cols + COLS - 1) / COLS;
-  const long long grid = per_cu > 0 && (long long)per_cu * cus[dev].load() < nblk ? (long long)per_cu * cus[dev].load() : nblk;
-  hipLaunchKernelGGL(k_scatter_latent_merged<COLS>, dim3((unsigned)grid), dim3(256), lds, st, d_lat, tap_row, tap_w, cols, d_latent_cl, perm);
+  const long long nblk = (cols + kScatterCols - 1) / kScatterCols, walkers = (long long)kScatterWgPerCu * cus[dev].load();
+  const long long grid = walkers < nblk ? walkers : nblk;
+  hipLaunchKernelGGL(k_scatter_latent_merged<kScatterCols>, dim3((unsigned)grid), dim3(256), lds, st, d_lat, tap_row, tap_w, cols, d_latent_cl, perm);
   DINER_LAUNCH_OK();
   return 0;
 }
@@ -828,15 +827,7 @@ static int sort_columns_by_texel(const int* tap_row, long long cols, long long r
 }
 int scatter_latent_launch(const float* d_lat, const int* tap_row, const float* tap_w, long long cols, float* d_latent_cl, hipStream_t st,
                           const int* perm = nullptr) {
-  static const bool merged = [] { const char* e = getenv("DINER_TRAIN_SCATTER_MERGED"); return !(e && *e == '0'); }();
-  // same-box A/B, SB 4 step, round 6 (profiles/r06_train_scatter_*): 64 / 32 / 16 columns with the one-block workgroups of the first version 123.6 /
-  // 121.9 / 122.2 ms; with sorted columns and the rewritten phases 102.2 / 102.7 / 108.5; 64 columns + one walking workgroup per CU 101.8
-  static const int ncols = [] { const char* e = getenv("DINER_TRAIN_SCATTER_COLS"); return e ? atoi(e) : 64; }();
-  if (merged && (reinterpret_cast<size_t>(d_lat) & 15) == 0) {
-    if (ncols == 16) return scatter_merged_launch<16>(d_lat, tap_row, tap_w, cols, d_latent_cl, st, perm);
-    if (ncols == 32) return scatter_merged_launch<32>(d_lat, tap_row, tap_w, cols, d_latent_cl, st, perm);
-    return scatter_merged_launch<64>(d_lat, tap_row, tap_w, cols, d_latent_cl, st, perm);
-  }
+  if ((reinterpret_cast<size_t>(d_lat) & 15) == 0) return scatter_merged_launch(d_lat, tap_row, tap_w, cols, d_latent_cl, st, perm);
   hipLaunchKernelGGL(k_scatter_latent, dim3((unsigned)((cols + 3) / 4)), dim3(256), 0, st, d_lat, tap_row, tap_w, cols, d_latent_cl);
   DINER_LAUNCH_OK();
   return 0;
@@ -1255,8 +1246,6 @@ static int gemm_launch(const float* A, const float* B, float* C, long long M, in
   DINER_CHECK_ARG(!(resid && rowsum), "gemm: resid and rowsum are separate epilogues");
   int chunk = (K + k_split - 1) / k_split;
   chunk = (chunk + XK - 1) / XK * XK;               // (a multiple of every kernel's k-tile)
-  static const bool no_xcd = [] { const char* e = getenv("DINER_TRAIN_NO_XCD"); return e && *e == '1'; }();
-  if (no_xcd) flags |= kNoXcdOrder;
   DINER_CHECK_ARG(!k_dev || !(flags & kExact), "gemm: a device-side contraction length runs on the bf16x6 kernel");
   GemmArgs g{A, B, C, bias, mask, resid, rowsum, M, N, K, lda, ldb, ldc, flags, chunk, gate, k_dev};
   if (!(flags & kExact)) {
@@ -1264,7 +1253,7 @@ static int gemm_launch(const float* A, const float* B, float* C, long long M, in
     // its adjoints: K = 4 / M = 4) ride along zero-padded -- a partly empty 128 x 128 tile is still faster than the fp32 kernels
     dim3 grid((N + XN - 1) / XN, (unsigned)((M + XM - 1) / XM), (K + chunk - 1) / chunk);
     if (k_dev) {                                                // chunk walkers (see the kernel's chunk loop)
-      static const int walkers = [] { const char* e = getenv("DINER_TRAIN_GEMM_WALKERS"); const int v = e ? atoi(e) : 32; return v < 1 ? 1 : v; }();      // same-box A/B chunk x walkers, SB 4 step: one workgroup per 512-row chunk 102.7 ms, 128 x 64 100.5, 64 x 96 101.0, 256 x 32 100.1, 512 x 24 100.3, 128 x 128 101.6
+      constexpr int walkers = 32;      // same-box A/B chunk x walkers, SB 4 step: one workgroup per 512-row chunk 102.7 ms, 128 x 64 100.5, 64 x 96 101.0, 256 x 32 100.1, 512 x 24 100.3, 128 x 128 101.6
       if (grid.z > (unsigned)walkers) grid.z = walkers;
     }
     if (resid) hipLaunchKernelGGL(k_gemm_bf16x6<1>, grid, dim3(256), 0, stream, g);
@@ -1467,38 +1456,18 @@ TrainWs train_ws(long long P, int nv) {
 // base pointer for the work buffers' offsets: `scratch` (a buffer of its own, diner_field_train_workspace_split) or the workspace itself
 float* scratch_base(float* ws, void* scratch, const TrainWs& w) { return scratch ? (float*)scratch : ws + w.saved_total; }
 int check_train_params(const DinerMlpParams* p, bool poscode) { return check_mlp_config(p, "field_train", poscode); }
-// DINER_TRAIN_LIN512=0 routes the 512 x 512 layer products back to the general kernel (A/B measurement)
-bool use_lin512() {
-  static const bool on = [] { const char* e = getenv("DINER_TRAIN_LIN512"); return !(e && *e == '0'); }();
-  return on;
-}
-bool use_lin_out() {            // DINER_TRAIN_LINOUT=0: lin_out and its adjoints back on the general kernel (A/B measurement)
-  static const bool on = [] { const char* e = getenv("DINER_TRAIN_LINOUT"); return !(e && *e == '0'); }();
-  return on;
-}
-// The forward products of the 512 x 512 layers in the f16x3 arithmetic of the inference kernels (two fp16 planes per operand, three product
+// The forward products of the 512 x 512 layers run in the f16x3 arithmetic of the inference kernels (two fp16 planes per operand, three product
 // terms: half the MFMAs of bf16x6, same fp32-class accuracy on activations) with a bf16x6 launch behind each that does nothing unless the
-// f16x3 one met an operand beyond the fp16 range.  DINER_TRAIN_FWD_F16X3=0: bf16x6 forward (A/B measurement).
-bool use_fwd_f16() {
-  static const bool on = [] { const char* e = getenv("DINER_TRAIN_FWD_F16X3"); return !(e && *e == '0'); }();
-  return on;
-}
+// f16x3 one met an operand beyond the fp16 range.
 // Round 4: the data- and weight-gradient products of the 512 x 512 layers in the f16x3 arithmetic as well (3 MFMAs per fp32 product instead of
 // bf16x6's 6, on two thirds of the step's FLOPs).  Loss gradients span many decades, so dy is staged times a power of two taken from its
 // maximum (tracked by the epilogue of the product that wrote it): nothing leaves the fp16 range, no repeat is needed for the operand.  What
 // can still not fit: the weights (16 |w| beyond fp16, kFlagWBad) and an activation operand of a weight gradient (the forward flag of that
-// layer) -- those launches return at once and their bf16x6 twins, issued behind them, do the work.  DINER_TRAIN_BWD_F16X3=0: bf16x6 backward.
-bool use_bwd_f16() {
-  static const bool on = [] { const char* e = getenv("DINER_TRAIN_BWD_F16X3"); return !(e && *e == '0'); }();
-  return on;
-}
-bool use_wgrad512() {          // DINER_TRAIN_WGRAD512=0: weight gradients back on the general kernel (A/B measurement)
-  static const bool on = [] { const char* e = getenv("DINER_TRAIN_WGRAD512"); return !(e && *e == '0'); }();
-  return on;
-}
+// layer) -- those launches return at once and their bf16x6 twins, issued behind them, do the work.
+// What the 512-kernels ask of a product's operands (else: the general kernel)
 bool lin512_ok(const float* x, int ldx, const float* y, int ldy, const float* resid, const float* mask) {
   auto al = [](const void* p) { return (reinterpret_cast<size_t>(p) & 15) == 0; };
-  return use_lin512() && (ldx & 3) == 0 && (ldy & 3) == 0 && al(x) && al(y) && al(resid) && al(mask);
+  return (ldx & 3) == 0 && (ldy & 3) == 0 && al(x) && al(y) && al(resid) && al(mask);
 }
 void* wpack_slot(float* ws, const TrainWs& w, int slot, bool transposed, bool f16 = false) {
   return reinterpret_cast<char*>(ws + w.wpack) + (size_t)(slot + (transposed ? 13 : 0) + (f16 ? 26 : 0)) * kL512PackBytes;
@@ -1519,17 +1488,15 @@ int linear_bwd(const float* dy, int ldy, const float* x, int ldx, bool relu_in, 
   // split-K so that the 16 output tiles of a 512 x 512 weight gradient become 500-1000 workgroups of >= 15 k-tiles each (measured:
   // 128 / 512 / 2048-ray steps 5.70 / 15.6 / 53.1 ms with M / 1024 capped at 32, 5.07 / 14.5 / 51.8 ms with M / 480 capped at 64);
   // round 3: M / 640 -- the row-sum instance of the kernel runs two workgroups per CU, 16 tiles x 32 chunks fill the chip once for the
-  // reference batch (128 / 512 / 2048-ray steps 4.37 / 10.56 / 37.6 ms with 480, 4.00 / 10.31 / 37.5 ms with 640);
-  // DINER_TRAIN_WGRAD_ROWS / _CAP override (measurement aid)
-  static const long long rows_per_chunk = [] { const char* e = getenv("DINER_TRAIN_WGRAD_ROWS"); return e ? atoll(e) : 640LL; }();
-  static const long long cap = [] { const char* e = getenv("DINER_TRAIN_WGRAD_CAP"); return e ? atoll(e) : 64LL; }();
+  // reference batch (128 / 512 / 2048-ray steps 4.37 / 10.56 / 37.6 ms with 480, 4.00 / 10.31 / 37.5 ms with 640)
+  constexpr long long rows_per_chunk = 640, cap = 64;
   long long split = M / rows_per_chunk;
   split = split < 1 ? 1 : (split > cap ? cap : split);
   // a dx produced by the general GEMM keeps no maximum of its own: one pass over it fills the slot the f16x3 consumers scale by
   auto dx_amax = [&]() {
     if (f16 && f16->amax_dx && dx) hipLaunchKernelGGL(k_absmax, dim3(grid1d(M * (long long)K)), dim3(256), 0, st, dx, M * (long long)K, f16->amax_dx);
   };
-  if (N == 512 && K == 512 && M >= 256 && use_wgrad512() && (ldy & 1) == 0 && (ldx & 3) == 0 &&
+  if (N == 512 && K == 512 && M >= 256 && (ldy & 1) == 0 && (ldx & 3) == 0 &&
       (reinterpret_cast<size_t>(dy) & 7) == 0 && (reinterpret_cast<size_t>(x) & 15) == 0 &&
       (reinterpret_cast<size_t>(dW) & 15) == 0 && (reinterpret_cast<size_t>(db) & 15) == 0) {      // (the summing pass stores dW / db as 16-byte vectors)
     // the 512 x 512 layers: persistent feature-sliced kernel (train_wgrad512.hip), bias gradient = row sums of its dy operand
@@ -1539,11 +1506,10 @@ int linear_bwd(const float* dy, int ldy, const float* x, int ldx, bool relu_in, 
       DINER_HIP_OK(hipMemsetAsync(db, 0, (size_t)N * sizeof(float), st));
     }
     // the data gradient of the layer rides in the same launch (train_512.hip): dx = dy W on k_lin512's bodies, W packed transposed
-    static const bool one_launch = [] { const char* e = getenv("DINER_TRAIN_BWD_FUSED"); return !(e && *e == '0'); }();
     const bool dgrad512 = dx && Wt_packed && lin512_ok(dy, ldy, dx, K, nullptr, dx_mask);
     Lin512Args da{dy, Wt_packed, dx, nullptr, nullptr, dx_mask, M, ldy, K, dx_accum ? kL512Accum : 0};
     if (dx_maskbits) { da.mask = nullptr; da.maskbits = dx_maskbits; }
-    if (f16 && wgpart && defer && one_launch && (dgrad512 || !dx)) {
+    if (f16 && wgpart && defer && (dgrad512 || !dx)) {
       // the f16x3 launch (works unless a flag is up) and its bf16x6 twin (works only then); an accumulating data gradient is safe: exactly
       // one of the two runs, decided by a flag that does not change during the step
       Lin512Args dh = da;
@@ -1561,10 +1527,9 @@ int linear_bwd(const float* dy, int ldy, const float* x, int ldx, bool relu_in, 
     }
     if (f16) da.amax_out = f16->amax_dx;          // (bf16x6 here, but a later product may still want the maximum)
     int rcw = wgrad512_launch(dy, ldy, x, ldx, relu_in, dW, db, M, st, wgpart, wgpart != nullptr, wgpart ? defer : nullptr,
-                              dgrad512 && one_launch ? &da : nullptr);
+                              dgrad512 ? &da : nullptr);
     if (rcw) return rcw;
-    if (dgrad512) return one_launch ? 0 : lin512_launch(da, st);
-    if (dx) {
+    if (dx && !dgrad512) {
       int rcd = gemm_launch(dy, W, dx, M, K, N, ldy, K, K, dx_accum ? kAccum : 0, nullptr, dx_mask, 1, st);
       if (rcd) return rcd;
       dx_amax();
@@ -1642,13 +1607,12 @@ static int forward_layerwise(const DinerScene* scene, const DinerMlpParams* p, c
   }
   // the 512 x 512 layers: weights packed once per step (three bf16 planes in the consuming wave's order; one launch for the 13 matrices
   // in both orientations -- the backward call of the step reads the transposed ones from the workspace), products on k_lin512
-  if (use_lin512() && !gate && pack) {
+  if (!gate && pack) {
     PackMany pm;
     for (int b = 0; b < 5; ++b) { pm.W[kSlotFc0 + b] = p->fc0_w[b]; pm.W[kSlotFc1 + b] = p->fc1_w[b]; }
     for (int b = 0; b < 3; ++b) pm.W[kSlotLinZ + b] = p->lin_z_w[b];
-    const bool f16_packs = use_fwd_f16() || use_bwd_f16();
-    if (f16_packs) DINER_HIP_OK(hipMemsetAsync(ws + w.flags, 0, 16 * sizeof(int), st));
-    if ((rc = lin512_pack_many(pm, 13, ws + w.wpack, st, f16_packs ? 4 : 2, reinterpret_cast<int*>(ws + w.flags) + kFlagWBad))) return rc;
+    DINER_HIP_OK(hipMemsetAsync(ws + w.flags, 0, 16 * sizeof(int), st));
+    if ((rc = lin512_pack_many(pm, 13, ws + w.wpack, st, 4, reinterpret_cast<int*>(ws + w.flags) + kFlagWBad))) return rc;
   }
   // seg2_slot >= 0: a second contraction segment in the same product (Lin512Args.X2: + x2 W[seg2_slot]^T + bias2, no relu on x2)
   auto lin = [&](const float* x, int ldx, const float* W, const float* b, float* y, long long M, int N, int K, bool relu,
@@ -1665,7 +1629,7 @@ static int forward_layerwise(const DinerScene* scene, const DinerMlpParams* p, c
         a.bias2 = bias2;
         a.relu2 = 0;
       }
-      if (use_fwd_f16() && !accum) {             // (an accumulating product cannot be run twice: lin_z stays on bf16x6)
+      if (!accum) {           // (an accumulating product cannot be run twice: lin_z stays on bf16x6)
         int* flag = reinterpret_cast<int*>(ws + w.flags) + slot;
         Lin512Args h = a;
         h.Wp = wpack_slot(ws, w, slot, false, true);
@@ -1690,9 +1654,9 @@ static int forward_layerwise(const DinerScene* scene, const DinerMlpParams* p, c
   };
   // The lin_z term of block b, Z_b = lat Wz_b^T + bz_b, is a product of its own into a scratch buffer (d_lat is free in the forward) and
   // enters the residual stream through the epilogue of fc_1 of block b - 1, the product that writes X[b] (second residual; block 0: below): no accumulating product is left in the forward, so every 512 x 512 product can run in the f16x3 arithmetic with
-  // its gated bf16x6 repeat.  (Without the 512-kernels: lin_z accumulates onto X[b] as before.)
+  // its gated bf16x6 repeat.  (Off the 512-kernels -- a workspace that is not 16-byte aligned: lin_z accumulates onto X[b] as before.)
   float* Z = sc + w.d_lat;
-  const bool z_sep = use_lin512() && lin512_ok(ws + w.lat, kLatent, Z, kHidden, nullptr, nullptr);
+  const bool z_sep = lin512_ok(ws + w.lat, kLatent, Z, kHidden, nullptr, nullptr);
   auto lin_z = [&](int b, float* dst) { return lin(ws + w.lat, kLatent, p->lin_z_w[b], p->lin_z_b[b], dst, cols, kHidden, kLatent, false, false, nullptr, kSlotLinZ + b); };
   // block 0: lin_in (general kernel, plain instance, runs once) writes into the scratch buffer and the lin_z product of block 0 takes it as its
   // residual: X[0] = lat Wz_0^T + bz_0 + lin_in(feat).  (lin_in accumulating onto a Z_0 written first cost 0.88 ms for the 2048-ray batch --
@@ -1710,9 +1674,8 @@ static int forward_layerwise(const DinerScene* scene, const DinerMlpParams* p, c
     const bool z_next = z_sep && b + 1 < 3;
     // round 4: the lin_z term of block b + 1 as a SECOND CONTRACTION SEGMENT of this block's fc_1 product (K = 512 + 512: relu(H) W1^T +
     // lat Wz^T + both biases + X in one pass over the rows) -- no Z tensor written and read back (2 of this block's ~8 tensor passes).
-    // DINER_TRAIN_FUSE_Z=0: Z_{b+1} as a product of its own into the scratch buffer, entering through the second residual (round 3)
-    static const bool fuse_z = [] { const char* e = getenv("DINER_TRAIN_FUSE_Z"); return !(e && *e == '0'); }();
-    const bool fused = z_next && fuse_z && use_fwd_f16() && (reinterpret_cast<size_t>(p->lin_z_b[b + 1]) & 15) == 0;
+    // A lin_z bias that is not 16-byte aligned: Z_{b+1} as a product of its own into the scratch buffer, entering through the second residual (round 3)
+    const bool fused = z_next && (reinterpret_cast<size_t>(p->lin_z_b[b + 1]) & 15) == 0;
     if (z_next && !fused && (rc = lin_z(b + 1, Z))) return rc;
     // (the residual enters through the product's epilogue: no copy of X)
     if (fused) {
@@ -1722,7 +1685,7 @@ static int forward_layerwise(const DinerScene* scene, const DinerMlpParams* p, c
     if (b == 2)
       hipLaunchKernelGGL(k_view_mean, dim3(grid1d(P * kHidden)), dim3(256), 0, st, nx, scene->nv, P * kHidden, ws + w.X[3], gate);
   }
-  if (use_lin_out() && (reinterpret_cast<size_t>(p->lin_out_w) & 15) == 0 && (reinterpret_cast<size_t>(p->lin_out_b) & 15) == 0 &&
+  if ((reinterpret_cast<size_t>(p->lin_out_w) & 15) == 0 && (reinterpret_cast<size_t>(p->lin_out_b) & 15) == 0 &&
       (reinterpret_cast<size_t>(out) & 15) == 0) {
     hipLaunchKernelGGL(k_lin_out_fwd, dim3(grid1d(P, 4, 1024)), dim3(256), 0, st, ws + w.x_last, p->lin_out_w, p->lin_out_b, P, ws + w.raw, out, gate);
   } else {
@@ -1895,7 +1858,6 @@ extern "C" int diner_field_train_forward_fused_f32(const DinerScene* scene, cons
   if (rc) return rc;
   rc = check_train_params(p, true);
   if (rc) return rc;
-  DINER_CHECK_ARG(use_lin512() && (use_fwd_f16() || use_bwd_f16()), "field_train_forward_fused: needs the 512-layer kernels of the backward");
   float* ws = (float*)workspace;
   const TrainWs w = train_ws(P, scene->nv);
   return fused_forward_core(scene, mlp, p, xyz, viewdirs, P, out, ws, scratch_base(ws, scratch, w), w, latent_proj_out, (hipStream_t)stream, true);
@@ -1944,14 +1906,12 @@ static int backward_core(const DinerScene* const* scenes, int n_obj, const Diner
     jobs.job[n_jobs] = WgReduceJob{nullptr, nullptr, nullptr, 0};
     return &jobs.job[n_jobs++];
   };
-  auto wt = [&](const float*, int slot) -> const void* {      // W packed transposed by the forward call of the step (k_lin512), or null
-    return use_lin512() ? wpack_slot(ws, w, slot, true) : nullptr;
-  };
-  // f16x3 backward (use_bwd_f16): every dy operand carries the maximum of its magnitudes in an amax slot, written by its producer
+  auto wt = [&](const float*, int slot) -> const void* { return wpack_slot(ws, w, slot, true); };      // W packed transposed by the forward call of the step
+  // f16x3 backward (bwd16): every dy operand carries the maximum of its magnitudes in an amax slot, written by its producer
   int* flags = reinterpret_cast<int*>(ws + w.flags);
   unsigned* amax = reinterpret_cast<unsigned*>(flags) + kAmax0;
-  const bool z_sep = use_lin512() && lin512_ok(ws + w.lat, kLatent, sc + w.d_lat, kHidden, nullptr, nullptr);   // as the forward decided
-  const bool bwd16 = use_bwd_f16() && use_fwd_f16() && use_lin512() && use_wgrad512() && z_sep && (reinterpret_cast<size_t>(ws) & 15) == 0;
+  const bool z_sep = lin512_ok(ws + w.lat, kLatent, sc + w.d_lat, kHidden, nullptr, nullptr);   // as the forward decided
+  const bool bwd16 = z_sep && (reinterpret_cast<size_t>(ws) & 15) == 0;
   if (bwd16) DINER_HIP_OK(hipMemsetAsync(amax, 0, 64 * sizeof(unsigned), st));
   int a_cur = 0, a_next = 1;                                  // slot of the current dx; next free slot
   BwdArith ar_store;
@@ -1960,7 +1920,7 @@ static int backward_core(const DinerScene* const* scenes, int n_obj, const Diner
     ar_store = BwdArith{amax + a_dy, a_dx >= 0 ? amax + a_dx : nullptr, flags + kFlagWBad, flags + slot, wpack_slot(ws, w, slot, true, true)};
     return &ar_store;
   };
-  if (use_lin_out() && (reinterpret_cast<size_t>(p->lin_out_w) & 15) == 0 && (reinterpret_cast<size_t>(d_out) & 15) == 0) {
+  if ((reinterpret_cast<size_t>(p->lin_out_w) & 15) == 0 && (reinterpret_cast<size_t>(d_out) & 15) == 0) {
     DINER_HIP_OK(hipMemsetAsync((void*)grads->lin_out_w, 0, (size_t)4 * kHidden * sizeof(float), st));
     DINER_HIP_OK(hipMemsetAsync((void*)grads->lin_out_b, 0, 4 * sizeof(float), st));
     hipLaunchKernelGGL(k_lin_out_bwd, dim3(grid1d(P, 4, 256)), dim3(256), 0, st, ws + w.x_last, ws + w.raw, d_out, p->lin_out_w, P, dx,
@@ -1972,10 +1932,8 @@ static int backward_core(const DinerScene* const* scenes, int n_obj, const Diner
     // (lin_out off its skinny kernel -- a weight or d_out that is not 16-byte aligned: the general path keeps no maximum of dx)
     if (bwd16) hipLaunchKernelGGL(k_absmax, dim3(grid1d(P * (long long)kHidden)), dim3(256), 0, st, dx, P * (long long)kHidden, amax + 0);
   }
-  // round 5: the data gradients of the 512-kernels read the relu decisions as bits (64 B per row instead of 2 KB; DINER_TRAIN_MASKBITS=0: the
-  // saved pre-activations themselves, A/B measurement)
-  static const bool maskbits_on = [] { const char* e = getenv("DINER_TRAIN_MASKBITS"); return !(e && *e == '0'); }();
-  auto bits = [&](size_t off) { return maskbits_on ? reinterpret_cast<const unsigned*>(ws + off) : nullptr; };
+  // round 5: the data gradients of the 512-kernels read the relu decisions as bits (64 B per row instead of the 2 KB of the saved pre-activations)
+  auto bits = [&](size_t off) { return reinterpret_cast<const unsigned*>(ws + off); };
   // ---- round 6: the adjoint of the three lin_z terms in MAP space ------------------------------------------------------------------------
   // X_b = in_b + interp(lin_z[b](latent map)) (the forward's hoist), so with D_b = the gradient of X_b scattered through the bilinear taps into
   // map shape:  dWz_b = D_b^T L,  dbz_b = column sums of D_b,  d latent = sum_b D_b Wz_b  -- over the TEXEL rows the batch touches (2.4 % of a
@@ -1987,7 +1945,7 @@ static int backward_core(const DinerScene* const* scenes, int n_obj, const Diner
   // `cap` rows (what the object's share of the d_lat region holds in three buffers) cover any count without a host decision.
   // DINER_TRAIN_LINZ_MAPSPACE=0: the round-5 products over the sample rows.
   const char* e_ms = getenv("DINER_TRAIN_LINZ_MAPSPACE");
-  bool mapspace = map_scratch && !(e_ms && *e_ms == '0') && use_lin512() && cols_obj >= 4096;
+  bool mapspace = map_scratch && !(e_ms && *e_ms == '0') && cols_obj >= 4096;
   for (int o = 0; o < n_obj && mapspace; ++o)
     mapspace = scenes[o]->latent_cl && scenes[o]->C == kLatent && (long long)scenes[o]->nv * scenes[o]->Hf * scenes[o]->Wf < (1ll << 30) &&
                (!d_latent_cl || !d_latent_cl[o] || (reinterpret_cast<size_t>(d_latent_cl[o]) & 15) == 0);
@@ -2057,7 +2015,7 @@ static int backward_core(const DinerScene* const* scenes, int n_obj, const Diner
         // dWz_b (512 f x 512 k) += Dc^T Lc over the segment's rows, dbz_b += column sums of Dc: op(A) = Dc^T (kTA), contraction length on the device
         // (contraction chunks of `linz_chunk` rows: the list holds ~11 k of the segment's 200 k rows, so the chunk sets how many workgroups have
         // work -- 512 rows: 1.4 per CU, each waiting for its operand tiles alone, 0.24 ms per product)
-        static const int linz_chunk = [] { const char* e = getenv("DINER_TRAIN_LINZ_CHUNK"); const int v = e ? atoi(e) : 256; return v < 16 ? 16 : v; }();
+        constexpr int linz_chunk = 256;
         long long split = (L.cap + linz_chunk - 1) / linz_chunk;
         split = split < 1 ? 1 : (split > 8192 ? 8192 : split);
         if ((r = gemm_launch(L.Dc, L.Lc, (float*)grads->lin_z_w[b], kHidden, kLatent, (int)L.cap, kHidden, kLatent, kLatent, kTA | kAtomic, nullptr, nullptr,
@@ -2084,7 +2042,7 @@ static int backward_core(const DinerScene* const* scenes, int n_obj, const Diner
     // (k_mask_views) -- a quarter of the rows of this data gradient; the weight gradient keeps all rows.  DINER_TRAIN_VIEW_SHARED=0: as every block
     const char* e_vs = getenv("DINER_TRAIN_VIEW_SHARED");
     const bool view_shared_on = !(e_vs && *e_vs == '0');
-    const bool view_shared = b == 2 && view_shared_on && bwd16 && maskbits_on && scene->nv > 1 && P_obj >= 256 &&
+    const bool view_shared = b == 2 && view_shared_on && bwd16 && scene->nv > 1 && P_obj >= 256 &&
                              lin512_ok(dx, kHidden, dH, kHidden, nullptr, nullptr);
     if (view_shared) {
       // the weight gradient: dW = sum over (v, p) of (g[p] / nv)^T relu(H[v][p]) = g^T S with S = mean_v relu(H[v]) -- one pass over H (HBM-bound)
@@ -2142,9 +2100,8 @@ static int backward_core(const DinerScene* const* scenes, int n_obj, const Diner
     }
   }
   // lin_in's weight / bias gradient: round 6 on a kernel of its own in the f16x3 arithmetic (dy scaled from its maximum; the encoded inputs are
-  // O(1): no range flag needed) -- DINER_TRAIN_WGRAD_IN=0: the general bf16x6 product (A/B measurement)
-  static const bool wgrad_in_on = [] { const char* e = getenv("DINER_TRAIN_WGRAD_IN"); return !(e && *e == '0'); }();
-  if (bwd16 && wgrad_in_on && cols >= 4096 && (reinterpret_cast<size_t>(dx) & 15) == 0) {
+  // O(1): no range flag needed); fewer than 4096 rows or an odd alignment: the general bf16x6 product
+  if (bwd16 && cols >= 4096 && (reinterpret_cast<size_t>(dx) & 15) == 0) {
     DINER_HIP_OK(hipMemsetAsync((void*)grads->lin_in_w, 0, (size_t)kHidden * kDIn * sizeof(float), st));
     DINER_HIP_OK(hipMemsetAsync((void*)grads->lin_in_b, 0, (size_t)kHidden * sizeof(float), st));
     if ((rc = wgrad_in_launch(dx, kHidden, ws + w.feat, kDInPad, kDIn, cols, (float*)grads->lin_in_w, (float*)grads->lin_in_b, amax + a_cur, st))) return rc;
@@ -2231,7 +2188,6 @@ extern "C" int diner_field_train_forward_batch_f32(const DinerScene* const* scen
   if (rc) return rc;
   DINER_CHECK_ARG(mlp && xyz && viewdirs && out && saved && scratch && latent_proj_scratch, "field_train_forward_batch: null pointer argument");
   if ((rc = check_train_params(p, true))) return rc;
-  DINER_CHECK_ARG(use_lin512() && (use_fwd_f16() || use_bwd_f16()), "field_train_forward_batch: needs the 512-layer kernels of the backward");
   for (int o = 0; o < n_obj; ++o)
     if ((rc = field_forward_save_supported(scenes[o], mlp))) return rc;
   if ((rc = diner_mlp_update(mlp, p, DINER_MLP_UPDATE_TRAIN_ONLY, stream))) return rc;

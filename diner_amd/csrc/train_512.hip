@@ -39,26 +39,13 @@ __global__ __launch_bounds__(256, 1) void k_fwd512_f16x3(Run512 r) {
   if (b < r.n[0]) return lin512_part_f16(r.part[0], r.shape[0], b, r.n[0]);
   lin512_part_f16(r.part[1], r.shape[1], b - r.n[0], r.n[1]);
 }
-// round 5 experiment (DINER_L512_W2=1): the forward products with TWO workgroups per CU (two waves per SIMD, 256 registers each): 64- and
-// 32-row tiles only (128 accumulator registers), 66 KB of LDS per workgroup -- one workgroup's epilogue and staging stalls under the other's MFMAs
-__device__ __forceinline__ void lin512_part_f16_w2(const Lin512Args& a, int shape, int bid, int nblk) {
-  if (shape == kShape64) lin512_body<kL512Ring, 2, 1, 1>(a, bid, nblk);
-  else if (shape == kShape32) lin512_body<kL512Ring, 1, 1, 1>(a, bid, nblk);
-  else lin512_body<kL512Ring, 1, 2, 1>(a, bid, nblk);
-}
-__global__ __launch_bounds__(256, 2) void k_fwd512_f16x3_w2(Run512 r) {
-  int b = blockIdx.x;
-  if (b < r.n[0]) return lin512_part_f16_w2(r.part[0], r.shape[0], b, r.n[0]);
-  lin512_part_f16_w2(r.part[1], r.shape[1], b - r.n[0], r.n[1]);
-}
-// round 4: the backward's launch (data gradient in its shapes + the weight gradient of the same layer) in the f16x3 arithmetic
+// The backward's data gradient in its shapes, in the f16x3 arithmetic.  (Round 4 ran the weight gradient of the layer as a third part of this
+// launch; since round 5 it is the eight-wave k_wgrad512_w8 behind it.  The symbol stays apart from k_fwd512_f16x3: profiles and tools tell
+// the forward from the backward by it.)
 __global__ __launch_bounds__(256, 1) void k_run512_f16x3(Run512 r) {
   int b = blockIdx.x;
   if (b < r.n[0]) return lin512_part_f16(r.part[0], r.shape[0], b, r.n[0]);
-  b -= r.n[0];
-  if (b < r.n[1]) return lin512_part_f16(r.part[1], r.shape[1], b, r.n[1]);
-  if (r.wg.wide) wgrad512_body_wide(r.wg, b - r.n[1]);
-  else wgrad512_body<1>(r.wg, b - r.n[1]);
+  lin512_part_f16(r.part[1], r.shape[1], b - r.n[0], r.n[1]);
 }
 
 __global__ __launch_bounds__(256, 1) void k_run512(Run512 r) {
@@ -66,26 +53,14 @@ __global__ __launch_bounds__(256, 1) void k_run512(Run512 r) {
   if (b < r.n[0]) return lin512_part(r.part[0], r.shape[0], b, r.n[0]);
   b -= r.n[0];
   if (b < r.n[1]) return lin512_part(r.part[1], r.shape[1], b, r.n[1]);
-  wgrad512_body<0>(r.wg, b - r.n[1]);
+  wgrad512_body(r.wg, b - r.n[1]);
 }
 
 // round 6: a product over a row list whose length lives on the device (Lin512Args.m_dev: the latent rows a training batch touches): 32-row
 // tiles on every CU, AR = 1 (f16x3) or 0 (its bf16x6 twin)
 template <int AR>
 __global__ __launch_bounds__(256, 1) void k_lin512_rows(Lin512Args a, int nblk) {
-  lin512_body<kL512Ring, 1, 1, AR, 4, true>(a, blockIdx.x, nblk);
-}
-// round 5: the data gradient of an f16x3 launch on eight waves (lin512_body<.., NW = 8>: two waves per SIMD, 64 features and half the staging
-// rows per wave; the shared 32-row shape of a plan runs as plain 32-row tiles -- its second workgroups find no tile)
-__global__ __launch_bounds__(512, 1) void k_dgrad512_w8(Run512 r) {
-  int b = blockIdx.x;
-  const int i = b < r.n[0] ? 0 : 1;
-  if (i) b -= r.n[0];
-  const Lin512Args& a = r.part[i];
-  const int shape = r.shape[i], nblk = r.n[i];
-  if (shape == kShape128) lin512_body<kL512Ring, 4, 1, 1, 8>(a, b, nblk);
-  else if (shape == kShape64) lin512_body<kL512Ring, 2, 1, 1, 8>(a, b, nblk);
-  else lin512_body<kL512Ring, 1, 1, 1, 8>(a, b, nblk);
+  lin512_body<kL512Ring, 1, 1, AR, true>(a, blockIdx.x, nblk);
 }
 // round 5: the weight gradient of an f16x3 launch on eight waves (wgrad512_body_w8), a launch of its own behind the data gradient's
 __global__ __launch_bounds__(512, 1) void k_wgrad512_w8(Wgrad512Args a) { wgrad512_body_w8(a, blockIdx.x); }
@@ -102,10 +77,8 @@ int device_cus(int* cus) {                                   // per device: dyna
   if (!attr_set[dev].load()) {
     DINER_HIP_OK(hipFuncSetAttribute((const void*)k_run512, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBytesRun));
     DINER_HIP_OK(hipFuncSetAttribute((const void*)k_fwd512_f16x3, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBytes512F16));
-    DINER_HIP_OK(hipFuncSetAttribute((const void*)k_fwd512_f16x3_w2, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBytes512F16W2));
     DINER_HIP_OK(hipFuncSetAttribute((const void*)k_run512_f16x3, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBytesRun));
     DINER_HIP_OK(hipFuncSetAttribute((const void*)k_wgrad512_w8, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBytesRun));
-    DINER_HIP_OK(hipFuncSetAttribute((const void*)k_dgrad512_w8, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBytesRun));
     DINER_HIP_OK(hipFuncSetAttribute((const void*)k_wgrad_in_f16x3, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBytesWgradIn));
     DINER_HIP_OK(hipFuncSetAttribute((const void*)k_lin512_rows<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBytesRun));
     DINER_HIP_OK(hipFuncSetAttribute((const void*)k_lin512_rows<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBytesRun));
@@ -122,7 +95,6 @@ int device_cus(int* cus) {                                   // per device: dyna
 // twice the MFMAs there), and the ragged rest in the shape that costs least -- 32-row tiles, or 32-row tiles shared by two workgroups
 // (half the features each).  Costs in units of one round of 32-row tiles, measured on the reference training batch (20480 rows = 2.5
 // rounds of 32-row tiles: three rounds as 32-row tiles, 1.85 + 0.55 as one 64-row round + one round of shared tiles).
-// DINER_L512_CT = 1 | 2 forces one shape for everything, DINER_L512_HALF = 0 keeps the shared tiles out (measurement aids).
 void plan_lin512(const Lin512Args& a, int cus, Run512* r, bool f16 = false) {
   auto part = [&](long long row0, long long rows) {
     Lin512Args b = a;
@@ -145,22 +117,17 @@ void plan_lin512(const Lin512Args& a, int cus, Run512* r, bool f16 = false) {
   r->n[0] = r->n[1] = 0;
   r->part[1] = a;
   r->shape[1] = kShape32;
-  static const int forced = [] { const char* e = getenv("DINER_L512_CT"); return e ? atoi(e) : 0; }();
-  static const bool halves = [] { const char* e = getenv("DINER_L512_HALF"); return !(e && *e == '0'); }();
-  if (forced == 1 || forced == 2) return set(0, 0, a.M, forced == 2 ? kShape64 : kShape32);
   // f16x3 at 64-row tiles is bound by the weight stream through the vector-memory path (1 MB per tile for 24.7 k clocks of MFMAs: the
-  // path's 64 B/clk; MfmaUtil 0.38, profiles/r04_train_1x4096_pmc_summary.md): whole rounds of 128-row tiles first (DINER_L512_T128=0: off)
-  static const bool t128 = [] { const char* e = getenv("DINER_L512_T128"); return !(e && *e == '0'); }();
-  if (f16 && t128 && a.M >= 128ll * cus) {
+  // path's 64 B/clk; MfmaUtil 0.38, profiles/r04_train_1x4096_pmc_summary.md): whole rounds of 128-row tiles first
+  if (f16 && a.M >= 128ll * cus) {
     const long long round128 = 128ll * cus, main128 = a.M / round128 * round128;
     set(0, 0, main128, kShape128);
     if (a.M > main128) {
       const long long rest = a.M - main128;
-      int shape_rest = kShape32;
       const double c32r = 1.0, c64r = 1.85;
       auto rounds2 = [&](long long units) { return (double)((units + cus - 1) / cus); };
       const double r64 = rounds2((rest + 63) / 64) * c64r, r32 = rounds2((rest + 31) / 32) * c32r;
-      set(1, main128, rest, r64 <= r32 ? kShape64 : shape_rest);
+      set(1, main128, rest, r64 <= r32 ? kShape64 : kShape32);
     }
     return;
   }
@@ -169,7 +136,7 @@ void plan_lin512(const Lin512Args& a, int cus, Run512* r, bool f16 = false) {
   auto rest_cost = [&](long long rows, int* shape) {         // cheapest 32-row shape for `rows` rows
     const long long t32 = (rows + 31) / 32;
     const double whole = rounds(t32) * c32, shared = rounds(2 * t32) * chalf;
-    *shape = halves && shared < whole ? kShape32Shared : kShape32;
+    *shape = shared < whole ? kShape32Shared : kShape32;
     return *shape == kShape32Shared ? shared : whole;
   };
   const long long round64 = 64ll * cus;
@@ -196,7 +163,7 @@ int plan_wgrad512(const float* dY, int ldy, const float* X, int ldx, bool relu_x
   while (n_chunks > 1 && (M + n_chunks - 1) / n_chunks < 128) n_chunks >>= 1;
   long long rows = (M + n_chunks - 1) / n_chunks;
   rows = (rows + 31) / 32 * 32;
-  *a = Wgrad512Args{dY, X, dW, db, part, M, ldy, ldx, relu_x ? 1 : 0, (int)n_chunks, rows, nullptr, nullptr, nullptr, wide ? 1 : 0};
+  *a = Wgrad512Args{dY, X, dW, db, part, M, ldy, ldx, relu_x ? 1 : 0, (int)n_chunks, rows, nullptr, nullptr, nullptr};
   *used = (int)((M + rows - 1) / rows);
   return (wide ? 4 : 8) * (int)(n_chunks <= 8 ? 8 : n_chunks);   // the block -> (tile, chunk) map needs whole groups of 8 chunks
 }
@@ -234,11 +201,7 @@ int lin512_launch(const Lin512Args& a, hipStream_t stream, int arith) {
   Run512 r;
   plan_lin512(a, cus, &r, arith == 1);
   memset(&r.wg, 0, sizeof(r.wg));
-  static const bool w2 = [] { const char* e = getenv("DINER_L512_W2"); return e && *e == '1'; }();
-  if (arith == 1 && w2) {
-    plan_lin512(a, 2 * cus, &r, false);      // (no 128-row shape: 256 accumulator registers do not fit two waves per SIMD)
-    hipLaunchKernelGGL(k_fwd512_f16x3_w2, dim3(r.n[0] + r.n[1]), dim3(256), kLdsBytes512F16W2, stream, r);
-  } else if (arith == 1) hipLaunchKernelGGL(k_fwd512_f16x3, dim3(r.n[0] + r.n[1]), dim3(256), kLdsBytes512F16, stream, r);
+  if (arith == 1) hipLaunchKernelGGL(k_fwd512_f16x3, dim3(r.n[0] + r.n[1]), dim3(256), kLdsBytes512F16, stream, r);
   else hipLaunchKernelGGL(k_run512, dim3(r.n[0] + r.n[1]), dim3(256), kLdsBytesRun, stream, r);
   DINER_LAUNCH_OK();
   return 0;
@@ -262,10 +225,9 @@ int wgrad512_launch(const float* dY, int ldy, const float* X, int ldx, bool relu
     r.shape[0] = r.shape[1] = kShape32;
   }
   int used = 0;
-  // f16x3: 256 x 256 tiles over up to 64 row chunks (DINER_WGRAD_WIDE=0: the 128 x 256-tile body); the bf16x6 twin of such a launch keeps the
-  // same chunks (its partial tiles go where the summing pass of the pair expects them), as 8 tiles x 64 chunks
-  static const bool wide_on = [] { const char* e = getenv("DINER_WGRAD_WIDE"); return !(e && *e == '0'); }();
-  const bool pair = ar && part && (ar->wg_skip || ar->wg_gate) && wide_on;
+  // f16x3: 256 x 256 tiles over up to 64 row chunks; the bf16x6 twin of such a launch keeps the same chunks (its partial tiles go where the
+  // summing pass of the pair expects them), as 8 tiles x 64 chunks
+  const bool pair = ar && part && (ar->wg_skip || ar->wg_gate);
   const bool wide = pair && ar->arith == 1;
   const int n_wg = plan_wgrad512(dY, ldy, X, ldx, relu_x, dW, db, M, part, &r.wg, &used, pair ? kWgPlanChunksWide : kWgPlanChunks, wide);
   if (ar) {
@@ -273,25 +235,12 @@ int wgrad512_launch(const float* dY, int ldy, const float* X, int ldx, bool relu
     r.wg.skip = ar->wg_skip;
     r.wg.gate = ar->wg_gate;
   }
-  // DINER_TRAIN_BWD_SPLIT=1 (measurement aid): the data-gradient parts and the weight-gradient part as two launches of the same kernel
-  static const bool split = [] { const char* e = getenv("DINER_TRAIN_BWD_SPLIT"); return e && *e == '1'; }();
-  // DINER_WGRAD_W8=0: the four-wave weight gradient inside the data gradient's launch (round 4; A/B measurement)
-  static const bool w8 = [] { const char* e = getenv("DINER_WGRAD_W8"); return !(e && *e == '0'); }();
-  if (w8 && wide && n_wg > 0) {
-    // DINER_DGRAD_W8=1: the data gradient on eight waves too (round 5 experiment)
-    static const bool d8 = [] { const char* e = getenv("DINER_DGRAD_W8"); return e && *e == '1'; }();
-    if (r.n[0] + r.n[1] > 0) {
-      if (d8) hipLaunchKernelGGL(k_dgrad512_w8, dim3(r.n[0] + r.n[1]), dim3(512), kLdsBytesRun, stream, r);
-      else hipLaunchKernelGGL(k_run512_f16x3, dim3(r.n[0] + r.n[1]), dim3(256), kLdsBytesRun, stream, r);
-    }
+  DINER_CHECK_ARG(wide || !(ar && ar->arith == 1), "wgrad512: the f16x3 weight gradient is one of a pair (scratch buffer + the flag that selects its bf16x6 twin)");
+  if (wide) {
+    // the weight gradient on eight waves, a launch of its own behind the data gradient's (round 5: profiles/r05_train_wgrad_w8.txt)
+    if (r.n[0] + r.n[1] > 0) hipLaunchKernelGGL(k_run512_f16x3, dim3(r.n[0] + r.n[1]), dim3(256), kLdsBytesRun, stream, r);
     hipLaunchKernelGGL(k_wgrad512_w8, dim3(n_wg), dim3(512), kLdsBytesRun, stream, r.wg);
-  } else if (split && ar && ar->arith == 1 && r.n[0] + r.n[1] > 0 && n_wg > 0) {
-    hipLaunchKernelGGL(k_run512_f16x3, dim3(r.n[0] + r.n[1]), dim3(256), kLdsBytesRun, stream, r);
-    Run512 w2 = r;
-    w2.n[0] = w2.n[1] = 0;
-    hipLaunchKernelGGL(k_run512_f16x3, dim3(n_wg), dim3(256), kLdsBytesRun, stream, w2);
-  } else if (ar && ar->arith == 1) hipLaunchKernelGGL(k_run512_f16x3, dim3(r.n[0] + r.n[1] + n_wg), dim3(256), kLdsBytesRun, stream, r);
-  else hipLaunchKernelGGL(k_run512, dim3(r.n[0] + r.n[1] + n_wg), dim3(256), kLdsBytesRun, stream, r);
+  } else hipLaunchKernelGGL(k_run512, dim3(r.n[0] + r.n[1] + n_wg), dim3(256), kLdsBytesRun, stream, r);
   if (part) {
     // chunks that start past M wrote nothing: only the chunks with rows are summed
     if (defer) *defer = WgReduceJob{part, dW, db, used};      // the caller sums (wgrad512_reduce_many)

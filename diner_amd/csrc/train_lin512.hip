@@ -35,7 +35,6 @@ constexpr int kStepsPerSlab = 8;                // k16 steps per staged slab (12
 constexpr int kSlabs = 512 / (16 * kStepsPerSlab);
 constexpr int kStepPad = 32;      // bytes between the k16 steps of a slab buffer beyond their fragments, see lin512_body (staging writes)
 constexpr size_t kLdsBytes512 = (size_t)2 * kStepsPerSlab * (2 * 3 * 1024 + kStepPad);  // two slab buffers of [step 8][row half CT][plane 3] 1 KB fragments: 96 KB at CT = 2
-constexpr size_t kLdsBytes512F16W2 = (size_t)2 * kStepsPerSlab * (2 * 2 * 1024 + kStepPad);  // f16x3 at CT = 2: 66 KB (two workgroups per CU, experiment)
 constexpr size_t kLdsBytes512F16 = (size_t)2 * kStepsPerSlab * (4 * 2 * 1024 + kStepPad);  // f16x3 (two planes) at CT = 4 (128-row tiles): 128 KB
 
 // fp32 -> three bf16 planes (round to nearest each time; the residuals are exact in fp32), 8 values at once
@@ -147,21 +146,20 @@ __device__ unsigned long long g_l512_prof[8];
 // AR: arithmetic -- 0 = bf16x6 (three bf16 planes per operand, six product terms: no range limit), 1 = f16x3 (two fp16 planes, three
 // terms, weights x16: the inference kernels' arithmetic; half the MFMAs; an operand beyond the fp16 range raises a.ovf and the caller
 // recomputes the product with AR = 0 -- the training FORWARD only, whose operands are activations)
-// NW (round 5): waves per workgroup.  8 = two waves per SIMD (512 threads, 256 registers per wave): wave w owns 64 features (the second half
-// of the wave slice w / 2 for odd w: the addressing of the shared 32-row shape, FH = 2, inside ONE workgroup) and stages half as many rows.
-template <int R, int CT, int FH, int AR = 0, int NW = 4, bool MDEV = false>
+// Four waves per workgroup, one per SIMD (an eight-wave data gradient, two waves per SIMD at 256 registers, measured no faster in round 5:
+// DESIGN_HISTORY.md).
+template <int R, int CT, int FH, int AR = 0, bool MDEV = false>
 __device__ __forceinline__ void lin512_body(const Lin512Args& a, const int bid, const int nblk) {
-  static_assert(NW == 4 || (NW == 8 && FH == 1), "eight waves: whole tiles only");
   constexpr int NP = AR == 1 ? 2 : 3, NT = AR == 1 ? 3 : 6;  // planes per operand, product terms
-  constexpr int kRows = 32 * CT, kSlabFrags = kStepsPerSlab * CT * NP, NQ = 16 * CT / NW;      // NQ: staging requests per wave and slab
-  constexpr int kStageRows = 32 * CT / NW;                   // rows of the tile this wave stages
+  constexpr int kRows = 32 * CT, kSlabFrags = kStepsPerSlab * CT * NP, NQ = 4 * CT;      // NQ: staging requests per wave and slab
+  constexpr int kStageRows = 8 * CT;                         // rows of the tile this wave stages
   // A staging write puts 8 bytes per lane into the fragments of EIGHT k16 steps at once (a lane holds 4 consecutive k of one row); with the
   // steps a multiple of 1 KB apart those are 8 lanes per LDS bank (PMC, round 4: 70 % of the kernel's LDS-active cycles were bank-conflict
   // cycles).  kStepPad = 32 bytes between the steps spreads them over the banks (2 lanes per bank are left: the two 8-row halves of a
   // fragment are 512 bytes apart by the MFMA layout); the fragment reads stay 1 KB contiguous per instruction.
   constexpr int kStepBytes = CT * NP * 1024 + kStepPad, kSlabBytes = kStepsPerSlab * kStepBytes;
-  constexpr int NRT = 16 / (FH * NW), NF = NP * NRT;         // MFMA row (= feature) tiles per wave, weight fragments per k16 step
-  constexpr bool kLdsEpi = CT == 4 && NW == 4 && FH == 1 && AR == 1;      // the epilogue leaves through LDS (below)
+  constexpr int NRT = 4 / FH, NF = NP * NRT;                 // MFMA row (= feature) tiles per wave, weight fragments per k16 step
+  constexpr bool kLdsEpi = CT == 4 && FH == 1 && AR == 1;      // the epilogue leaves through LDS (below)
   if (a.gate && *a.gate == 0) return;                        // fall-back launch of an f16x3 product that stayed in range: nothing to do
   if (a.gate2 && *a.gate2 == 0) return;
   long long Mrows = a.M;
@@ -273,8 +271,8 @@ __device__ __forceinline__ void lin512_body(const Lin512Args& a, const int bid, 
   // ---- weights: wave-private stream, NF fragments (NRT row tiles x 3 planes) per k16 step out of the 12 of the packed wave slice
   typedef const __attribute__((address_space(1))) char* gptr;
   const int half = FH == 2 ? (bid & 1) : 0;
-  const int wslice = NW == 8 ? (wave >> 1) : FH == 2 ? 2 * half + (wave >> 1) : wave;      // 128-feature slice of the packed weights
-  const int rt0 = (FH == 2 || NW == 8) ? 2 * (wave & 1) : 0;                 // first of this wave's row tiles inside the slice
+  const int wslice = FH == 2 ? 2 * half + (wave >> 1) : wave;      // 128-feature slice of the packed weights
+  const int rt0 = FH == 2 ? 2 * (wave & 1) : 0;                 // first of this wave's row tiles inside the slice
   const gptr wbase = (gptr)(reinterpret_cast<const char*>(a.Wp)) + ((size_t)wslice * 32 * (4 * NP) + NP * rt0) * 1024;
   const gptr wbase2 = (gptr)(reinterpret_cast<const char*>(a.Wp2 ? a.Wp2 : a.Wp)) + ((size_t)wslice * 32 * (4 * NP) + NP * rt0) * 1024;
   const int step_mask = 8 * n_slabs - 1;                     // k16 steps of a tile - 1 (the weight stream repeats per tile)

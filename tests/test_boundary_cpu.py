@@ -318,8 +318,10 @@ def test_no_spill_code_in_the_training_kernels(tmp_path):
     assert sum("v_mfma_f32_32x32x16_bf16" in l for l in found["k_run512"]) > 1000
     assert sum("v_mfma_f32_32x32x16_f16" in l for l in found["k_fwd512_f16x3"]) > 500
     assert not any("v_mfma_f32_32x32x16_bf16" in l for l in found["k_fwd512_f16x3"])
-    # round 4: the backward's launch in the f16x3 arithmetic (data gradient in its three shapes + the weight gradient)
-    assert sum("v_mfma_f32_32x32x16_f16" in l for l in found["k_run512_f16x3"]) >= 700
+    # round 4: the backward's launch in the f16x3 arithmetic: the data gradient in its four shapes.  The bound is a recount: the listing of
+    # the commit before the kernel lost its weight-gradient tail had 1584 of these MFMAs, 144 of them in the tail that no launch reached
+    # (96 in the four-wave 256 x 256-tile body, 48 in the f16x3 instance of the 128 x 256-tile body): 1584 - 144 = 1440
+    assert sum("v_mfma_f32_32x32x16_f16" in l for l in found["k_run512_f16x3"]) >= 1440
     assert not any("v_mfma_f32_32x32x16_bf16" in l for l in found["k_run512_f16x3"])
 
 
@@ -341,6 +343,39 @@ def test_kernel_sources_have_one_code_path():
                     for macro in tested - allowed:
                         found.setdefault(macro, f"{name}:{no}")
     assert not found, f"compile-time switches in the kernel sources: {found}"
+
+
+def test_env_switches_are_the_ones_the_tests_flip():
+    """The library and its Python host read a fixed set of environment variables.  On the training path those are the seven seams
+    tests/test_train_gpu.py flips to compare two routes inside one process (five read per call by the library, two by diner_amd/train.py);
+    the A/B aids of rounds 3-6 were fixed at their defaults once (profiles/train_switches_removed.txt), their measurements stand in the
+    comments beside the constexpr that replaced them.  A new getenv / os.environ read fails here: an experiment belongs in tools/ubench/
+    (a stand-alone .hip, or .hip.txt once it has lost), a tunable is a constexpr beside its measurement."""
+    csrc = os.path.join(ROOT, "diner_amd", "csrc")
+    in_lib = {}
+    for name in sorted(os.listdir(csrc)):
+        with open(os.path.join(csrc, name)) as f:
+            for no, line in enumerate(f, 1):
+                calls = re.findall(r"\bgetenv\s*\(\s*([^)]*)\)", line)
+                for arg in calls:
+                    m = re.fullmatch(r'"(\w+)"\s*', arg)
+                    assert m, f"{name}:{no}: getenv of something other than one string literal: {arg!r}"
+                    in_lib.setdefault(m.group(1), f"{name}:{no}")
+    hint = "; experiments go to tools/ubench/, tunables become a constexpr beside their measurement"
+    want_lib = {"DINER_TRAIN_PROJ_TOUCHED", "DINER_TRAIN_PROJ_CAP", "DINER_TRAIN_LINZ_MAPSPACE", "DINER_TRAIN_SCATTER_SORTED", "DINER_TRAIN_VIEW_SHARED"}
+    assert set(in_lib) == want_lib, f"getenv in the library: new {({k: in_lib[k] for k in set(in_lib) - want_lib})}, gone {sorted(want_lib - set(in_lib))}" + hint
+    in_py = {}
+    paths = [os.path.join(ROOT, "diner_amd", n) for n in sorted(os.listdir(os.path.join(ROOT, "diner_amd"))) if n.endswith(".py")]
+    for d, _, names in sorted(os.walk(os.path.join(ROOT, "src"))):
+        paths += [os.path.join(d, n) for n in sorted(names) if n.endswith(".py")]
+    for path in paths:
+        with open(path) as f:
+            for no, line in enumerate(f, 1):
+                if "environ" in line or "getenv" in line:
+                    for var in re.findall(r"""["'](DINER_\w+)["']""", line):
+                        in_py.setdefault(var, f"{os.path.relpath(path, ROOT)}:{no}")
+    want_py = {"DINER_AMD_LIB", "DINER_AMD_MAX_POINTS", "DINER_AMD_PRECISION", "DINER_AMD_VIEW_GROUPS", "DINER_TRAIN_FUSED_FWD", "DINER_TRAIN_BATCH"}
+    assert set(in_py) == want_py, f"os.environ in the Python host: new {({k: in_py[k] for k in set(in_py) - want_py})}, gone {sorted(want_py - set(in_py))}" + hint
 
 
 def test_bench_line_contract():
