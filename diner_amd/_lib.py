@@ -195,6 +195,20 @@ SIGNATURES = {
     "diner_cloud_reduce_workspace_bytes": (C.c_size_t, [C.c_longlong]),
     "diner_cloud_reduce_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_float, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                          C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "diner_conv3x3_pack_floats": (C.c_size_t, [C.c_int, C.c_int]),
+    "diner_conv3x3_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                    C.c_int, C.c_int, C.c_void_p]),
+    "diner_maxpool2_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "diner_maxpool2_bwd_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                         C.c_void_p]),
+    "diner_image_in_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "diner_image_in_bwd_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "diner_feature_l1_workspace_bytes": (C.c_size_t, [C.c_longlong]),
+    "diner_feature_l1_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p]),
+    "diner_lpips_layer_workspace_bytes": (C.c_size_t, [C.c_int, C.c_longlong]),
+    "diner_lpips_layer_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                        C.c_void_p]),
 }
 
 ABI_VERSION = 6          # DINER_ABI_VERSION of include/diner_hip.h

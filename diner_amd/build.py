@@ -13,7 +13,7 @@ ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(ROOT, "build", "obj")
 LIB = os.path.join(HERE, "libdiner_hip.so")
-SOURCES = ["api.cpp", "sampler.hip", "composite.hip", "stage_ops.hip", "prep.hip", "train.hip", "train_512.hip", "mlp.hip", "mlp_h3n.hip", "generic.hip", "metrics.hip", "objective.hip", "cull.hip", "geometry.hip", "surface.hip", "raycast.hip", "cloud.hip"]
+SOURCES = ["api.cpp", "sampler.hip", "composite.hip", "stage_ops.hip", "prep.hip", "train.hip", "train_512.hip", "mlp.hip", "mlp_h3n.hip", "generic.hip", "metrics.hip", "objective.hip", "cull.hip", "geometry.hip", "surface.hip", "raycast.hip", "cloud.hip", "perceptual.hip"]
 # -ffp-contract=off: every fp32 op of the geometry path rounds where the reference's torch ops round;
 # fused multiply-adds are written explicitly (fmaf / MFMA) where they are wanted.
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-Wno-unused-value",
@@ -22,7 +22,10 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fP
 
 # per-source additions: beside MFMAs packed fp32 VALU instructions (v_pk_add_f32 / v_pk_mul_f32, which -O3's SLP vectoriser forms from
 # adjacent scalar operations) are an anti-lever (MI355X_MICROARCH.md, "price of one filler beside MFMAs")
-EXTRA_FLAGS = {}
+EXTRA_FLAGS = {
+    # prints each kernel's registers, scratch, LDS and occupancy at build time: k_conv3x3 must stay free of scratch
+    "perceptual.hip": ["-Rpass-analysis=kernel-resource-usage"],
+}
 
 
 def _hipcc():

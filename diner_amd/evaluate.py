@@ -6,7 +6,8 @@ evaluate_folder (eval_suite.py:44-118), with the per-image scores computed by th
 write_prediction_folder renders the sample dicts of diner_amd.datasets and writes <stem>-pred.png, -depth.png, -ref.png and -gt.png
 per sample (the reference's suffixes); evaluate_folder pairs the -gt / -pred files of a folder, scores them on the device and writes
 average_scores.json, detailed_report.json and examples.png.  LPIPS needs network weights that are not part of this project: it is
-computed by a caller-supplied `lpips_fn` or by the `lpips` package when that is importable, and otherwise left out with a warning."""
+computed by a caller-supplied `lpips_fn`, by diner_amd.perceptual.Lpips on the device from a weights file (`lpips_weights`,
+--lpips_weights FILE), or by the `lpips` package when that is importable, and otherwise left out with a warning."""
 import argparse
 import json
 import os
@@ -135,13 +136,20 @@ def _lpips_from_package(device):
 
 @torch.no_grad()
 def evaluate_folder(source_dir, outdir, device=None, pred_suffix=PRED_SUFFIX, gt_suffix=GT_SUFFIX, ref_suffix=REF_SUFFIX,
-                    depth_suffix=DEPTH_SUFFIX, show_tqdm=False, lpips_fn=None):
+                    depth_suffix=DEPTH_SUFFIX, show_tqdm=False, lpips_fn=None, lpips_weights=None):
     """Score every <x>{gt_suffix} / <x>{pred_suffix} pair of `source_dir` (sorted by file name) on the HIP device `device` (None:
     the current one) and write AVERAGE_SCORE_FILENAME, REPORT_DETAIL_FILENAME and EXAMPLE_PLOT_FILENAME into `outdir`.  Returns the
     averages {ssim, psnr, l2, l1[, lpips]}; an average over an infinite psnr stays inf.  `lpips_fn(pred, gt)` receives (1,3,H,W)
-    float32 device tensors in [-1, 1], as the reference calls lpips_vgg; without it the lpips package is used when importable."""
+    float32 device tensors in [-1, 1], as the reference calls lpips_vgg; without it the lpips package is used when importable.
+    `lpips_weights`: a torch.load-able file holding a mapping as diner_amd.perceptual.Lpips takes it (an lpips.LPIPS(net="vgg")
+    state dict); LPIPS then runs on the device through Lpips, ahead of the lpips package."""
     from .metrics import image_metrics
+    if lpips_fn is not None and lpips_weights is not None:
+        raise ValueError("evaluate_folder: pass lpips_fn or lpips_weights, not both")
     device = _hip_device(device)
+    if lpips_weights is not None:
+        from .perceptual import Lpips
+        lpips_fn = Lpips(torch.load(lpips_weights, map_location="cpu"), device=device)
     outdir = Path(outdir)
     os.makedirs(outdir, exist_ok=True)
     source_dir = Path(source_dir)
@@ -283,6 +291,8 @@ def evaluate_geometry_folder(source_dir, outdir, pred_suffix=PLY_SUFFIX, gt_suff
 def _parser():
     ap = argparse.ArgumentParser(description="Score the predictions of DIR/visualizations on the device; reports go to DIR.")
     ap.add_argument("--eval_path", type=Path, required=True)
+    ap.add_argument("--lpips_weights", type=Path, default=None,
+                    help="a torch.load-able lpips.LPIPS(net='vgg') state dict: LPIPS is computed on the device from it")
     ap.add_argument("--geometry", action="store_true",
                     help="also score the <stem>.ply / <stem>-mesh.ply geometry against <stem>-gt.ply (instead, where there are no images)")
     ap.add_argument("--max_dist", type=float, default=float("inf"), help="--geometry: distances beyond it are outliers")
@@ -294,12 +304,13 @@ def _parser():
 def main(argv=None):
     args = _parser().parse_args(argv)
     source = args.eval_path / "visualizations"
+    lp = {} if args.lpips_weights is None else dict(lpips_weights=args.lpips_weights)
     if not args.geometry:
-        avg = evaluate_folder(source, args.eval_path, show_tqdm=True)
+        avg = evaluate_folder(source, args.eval_path, show_tqdm=True, **lp)
     else:
         avg = {}
         if any(p.name.endswith(GT_SUFFIX) for p in source.iterdir()):
-            avg.update(evaluate_folder(source, args.eval_path, show_tqdm=True))
+            avg.update(evaluate_folder(source, args.eval_path, show_tqdm=True, **lp))
         avg.update(evaluate_geometry_folder(source, args.eval_path, max_dist=args.max_dist, thresholds=args.threshold, thin=args.thin))
     print(json.dumps(avg, indent="\t"))
 

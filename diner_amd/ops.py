@@ -1085,6 +1085,212 @@ def cloud_reduce(d2, idx, max_dist=float("inf"), thresholds=(), normals_a=None, 
     return out
 
 
+CONV3X3_CIN_CHUNK = 8            # DINER_CONV3X3_CIN_CHUNK
+CONV3X3_COUT_TILE = 64           # DINER_CONV3X3_COUT_TILE
+
+
+def _pad_to(n, m):
+    return -(-int(n) // m) * m
+
+
+def pack_conv3x3(weight, transpose=False):
+    """A torch Conv2d weight (Cout,Cin,3,3) in the layout diner_conv3x3_f32 reads: [ceil(Cin / 8)][tap][8][Cout rounded up to 64], zeros
+    beyond Cin and Cout.  transpose: the weight set of the data gradient instead (taps flipped, Cin and Cout swapped).  Plain torch on
+    the weight's own device (done once at load), so it needs no HIP device."""
+    if not torch.is_tensor(weight) or weight.dim() != 4 or tuple(weight.shape[2:]) != (3, 3) or weight.shape[0] < 1 or weight.shape[1] < 1:
+        raise ValueError(f"diner_amd: pack_conv3x3 expects a (Cout,Cin,3,3) weight, got "
+                         f"{tuple(weight.shape) if torch.is_tensor(weight) else type(weight).__name__}")
+    if weight.dtype != torch.float32:
+        raise ValueError(f"diner_amd: pack_conv3x3 expects float32, got {weight.dtype}")
+    w = weight.detach()
+    if transpose:
+        w = w.flip(2, 3).transpose(0, 1)
+    Cout, Cin = w.shape[:2]
+    cp, op = _pad_to(Cin, CONV3X3_CIN_CHUNK), _pad_to(Cout, CONV3X3_COUT_TILE)
+    p = w.new_zeros(cp, 9, op)
+    p[:Cin, :, :Cout] = w.reshape(Cout, Cin, 9).permute(1, 2, 0)
+    return p.view(cp // CONV3X3_CIN_CHUNK, CONV3X3_CIN_CHUNK, 9, op).permute(0, 2, 1, 3).contiguous()
+
+
+def _check_nhwc(who, name, t, shape=None, min_hw=1):
+    """A channels-last activation (N,H,W,C): float32, 4-D, contiguous -> its shape."""
+    if not torch.is_tensor(t) or t.dim() != 4:
+        raise ValueError(f"diner_amd: {who} expects {name} channels-last (N,H,W,C), got "
+                         f"{tuple(t.shape) if torch.is_tensor(t) else type(t).__name__}")
+    if t.dtype != torch.float32:
+        raise ValueError(f"diner_amd: {who} expects {name} float32, got {t.dtype}")
+    if not t.is_contiguous():
+        raise ValueError(f"diner_amd: {who} expects {name} contiguous in (N,H,W,C) order, got strides {t.stride()}")
+    if min(t.shape) < 1 or t.shape[1] < min_hw or t.shape[2] < min_hw:
+        raise ValueError(f"diner_amd: {who} expects {name} with N, C >= 1 and H, W >= {min_hw}, got {tuple(t.shape)}")
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise ValueError(f"diner_amd: {who} expects {name} {tuple(shape)}, got {tuple(t.shape)}")
+    return tuple(int(s) for s in t.shape)
+
+
+def _check_conv3x3_args(x, wpack, bias, Cout, addend, mask):
+    """The argument checks of conv3x3 that need no device -> (N, H, W, Cin)."""
+    N, H, W, Cin = _check_nhwc("conv3x3", "x", x)
+    Cout = int(Cout)
+    want = (_pad_to(Cin, CONV3X3_CIN_CHUNK) // CONV3X3_CIN_CHUNK, 9, CONV3X3_CIN_CHUNK, _pad_to(max(Cout, 1), CONV3X3_COUT_TILE))
+    if Cout < 1 or not torch.is_tensor(wpack) or wpack.dtype != torch.float32 or tuple(wpack.shape) != want or not wpack.is_contiguous():
+        raise ValueError(f"diner_amd: conv3x3 expects wpack float32 {want} (pack_conv3x3) for Cin {Cin}, Cout {Cout}, got "
+                         f"{tuple(wpack.shape) if torch.is_tensor(wpack) else type(wpack).__name__}")
+    if bias is not None and (not torch.is_tensor(bias) or bias.dtype != torch.float32 or tuple(bias.shape) != (want[3],)
+                             or not bias.is_contiguous()):
+        raise ValueError(f"diner_amd: conv3x3 expects bias float32 ({want[3]},) (zero-padded to the packed width)")
+    if N > 65535:
+        raise ValueError(f"diner_amd: conv3x3 takes at most 65535 images a call, got {N}")
+    for name, t in (("addend", addend), ("mask", mask)):
+        if t is not None:
+            _check_nhwc("conv3x3", name, t, (N, H, W, Cout))
+    return N, H, W, Cin
+
+
+def conv3x3(x, wpack, bias, Cout, relu=False, addend=None, mask=None):
+    """3 x 3 convolution, stride 1, zero padding 1 (diner_conv3x3_f32): x (N,H,W,Cin) channels-last -> (N,H,W,Cout), = conv + bias, then
+    + addend, ReLU, and zero where !(mask > 0), each if given.  wpack / bias: pack_conv3x3's layout and the bias zero-padded to its
+    width.  With the transposed weight set this is the data gradient; addend and mask are then the loss gradient entering below and the
+    saved activation."""
+    N, H, W, Cin = _check_conv3x3_args(x, wpack, bias, Cout, addend, mask)
+    _require_hip(x, wpack, bias, addend, mask)
+    dev = x.device
+    with torch.cuda.device(dev):
+        y = torch.empty(N, H, W, int(Cout), dtype=torch.float32, device=dev)
+        _lib.check(lib.diner_conv3x3_f32(_ptr(x), _ptr(wpack), _ptr(bias), _ptr(addend), _ptr(mask), _ptr(y), N, H, W, Cin, int(Cout),
+                                         int(bool(relu)), _stream()))
+    return y
+
+
+def maxpool2(x):
+    """torch's MaxPool2d(2, 2) on a channels-last activation (diner_maxpool2_f32): (N,H,W,C) -> (N, H // 2, W // 2, C)."""
+    N, H, W, Cc = _check_nhwc("maxpool2", "x", x, min_hw=2)
+    _require_hip(x)
+    with torch.cuda.device(x.device):
+        y = torch.empty(N, H // 2, W // 2, Cc, dtype=torch.float32, device=x.device)
+        _lib.check(lib.diner_maxpool2_f32(_ptr(x), _ptr(y), N, H, W, Cc, _stream()))
+    return y
+
+
+def maxpool2_bwd(x, gy, addend=None, relu_mask=False):
+    """The adjoint of maxpool2 (diner_maxpool2_bwd_f32): the saved input x (N,H,W,C) and gy (N, H // 2, W // 2, C) -> gx (N,H,W,C); the
+    gradient goes to each window's first maximum in row-major order.  Then + addend (N,H,W,C) and zero where !(x > 0) (relu_mask)."""
+    N, H, W, Cc = _check_nhwc("maxpool2_bwd", "x", x, min_hw=2)
+    _check_nhwc("maxpool2_bwd", "gy", gy, (N, H // 2, W // 2, Cc))
+    if addend is not None:
+        _check_nhwc("maxpool2_bwd", "addend", addend, (N, H, W, Cc))
+    _require_hip(x, gy, addend)
+    with torch.cuda.device(x.device):
+        gx = torch.empty_like(x)
+        _lib.check(lib.diner_maxpool2_bwd_f32(_ptr(x), _ptr(gy), _ptr(addend), int(bool(relu_mask)), _ptr(gx), N, H, W, Cc, _stream()))
+    return gx
+
+
+def _check_affine(who, shift, scale):
+    out = []
+    for name, v in (("shift", shift), ("scale", scale)):
+        v = [float(a) for a in v]
+        if len(v) != 3 or not all(np.isfinite(a) for a in v) or (name == "scale" and not all(a != 0.0 for a in v)):
+            raise ValueError(f"diner_amd: {who} expects three finite {name} values (scale != 0), got {v}")
+        out.append((C.c_float * 3)(*v))
+    return out
+
+
+def _check_image_in_args(x, shift, scale, min_hw=1):
+    """The argument checks of image_in that need no device -> (N, H, W, shift, scale as host floats)."""
+    if not torch.is_tensor(x) or x.dim() != 4 or x.shape[1] != 3:
+        raise ValueError(f"diner_amd: image_in expects x (N,3,H,W), got {tuple(x.shape) if torch.is_tensor(x) else type(x).__name__}")
+    if x.dtype != torch.float32:
+        raise ValueError(f"diner_amd: image_in expects x float32, got {x.dtype}")
+    N, _, H, W = (int(s) for s in x.shape)
+    if N < 1 or H < min_hw or W < min_hw:
+        raise ValueError(f"diner_amd: image_in expects N >= 1 and H, W >= {min_hw}, got {tuple(x.shape)}")
+    return (N, H, W, *_check_affine("image_in", shift, scale))
+
+
+def image_in(x, shift, scale, pad=True):
+    """(N,3,H,W) -> channels-last (N,H,W,4 or 3) with y = (x - shift[c]) / scale[c] (diner_image_in_f32); pad: a zero fourth channel, so
+    that the first convolution reads whole 16-byte pixels."""
+    N, H, W, sh, sc = _check_image_in_args(x, shift, scale)
+    _require_hip(x)
+    x = x.detach().contiguous()
+    Cs = 4 if pad else 3
+    with torch.cuda.device(x.device):
+        y = torch.empty(N, H, W, Cs, dtype=torch.float32, device=x.device)
+        _lib.check(lib.diner_image_in_f32(_ptr(x), sh, sc, _ptr(y), N, H, W, Cs, _stream()))
+    return y
+
+
+def image_in_bwd(g, scale):
+    """The adjoint of image_in (diner_image_in_bwd_f32): g (N,H,W,3 or 4) -> (N,3,H,W), = g[..., c] / scale[c]."""
+    N, H, W, Cs = _check_nhwc("image_in_bwd", "g", g)
+    if Cs not in (3, 4):
+        raise ValueError(f"diner_amd: image_in_bwd expects g with 3 or 4 channels, got {Cs}")
+    _, sc = _check_affine("image_in_bwd", (0.0, 0.0, 0.0), scale)
+    _require_hip(g)
+    with torch.cuda.device(g.device):
+        gx = torch.empty(N, 3, H, W, dtype=torch.float32, device=g.device)
+        _lib.check(lib.diner_image_in_bwd_f32(_ptr(g), sc, _ptr(gx), N, H, W, Cs, _stream()))
+    return gx
+
+
+def _check_feature_l1_args(fx, fy, weight):
+    if not (torch.is_tensor(fx) and torch.is_tensor(fy)) or fx.shape != fy.shape or fx.numel() < 1:
+        raise ValueError("diner_amd: feature_l1 expects fx and fy of one shape with at least one element")
+    if fx.dtype != torch.float32 or fy.dtype != torch.float32:
+        raise ValueError(f"diner_amd: feature_l1 expects float32, got {fx.dtype}, {fy.dtype}")
+    if not (fx.is_contiguous() and fy.is_contiguous()):
+        raise ValueError("diner_amd: feature_l1 expects contiguous tensors")
+    weight = float(weight)
+    if not np.isfinite(weight):
+        raise ValueError(f"diner_amd: feature_l1 weight {weight} must be finite")
+    return int(fx.numel()), weight
+
+
+def feature_l1(fx, fy, weight=1.0, want_grad=True, mask_by_fx=False):
+    """mean |fx - fy| of one tap layer (diner_feature_l1_f32) -> ((1,) float64 device tensor, the gradient plane for the x side
+    weight * sign(fx - fy) / numel, or None).  mask_by_fx: the plane is zero where !(fx > 0).  The sum runs in double in a fixed order."""
+    n, weight = _check_feature_l1_args(fx, fy, weight)
+    _require_hip(fx, fy)
+    dev = fx.device
+    with torch.cuda.device(dev):
+        ws = _workspace(lib.diner_feature_l1_workspace_bytes(n), dev)
+        out = torch.empty(1, dtype=torch.float64, device=dev)
+        grad = torch.empty_like(fx) if want_grad else None
+        _lib.check(lib.diner_feature_l1_f32(_ptr(fx), _ptr(fy), n, weight, int(bool(mask_by_fx)), _ptr(grad), _ptr(ws), _ptr(out), _stream()))
+    return out, grad
+
+
+def _check_lpips_layer_args(fx, fy, lin, out):
+    N, H, W, Cc = _check_nhwc("lpips_layer", "fx", fx)
+    _check_nhwc("lpips_layer", "fy", fy, (N, H, W, Cc))
+    if not torch.is_tensor(lin) or lin.dtype != torch.float32 or lin.numel() != Cc or not lin.is_contiguous():
+        raise ValueError(f"diner_amd: lpips_layer expects lin float32 with {Cc} values (the layer's width), got "
+                         f"{tuple(lin.shape) if torch.is_tensor(lin) else type(lin).__name__}")
+    if N > 65535:
+        raise ValueError(f"diner_amd: lpips_layer takes at most 65535 images a call, got {N}")
+    if out is not None and (not torch.is_tensor(out) or out.dtype != torch.float64 or tuple(out.shape) != (N,) or not out.is_contiguous()):
+        raise ValueError(f"diner_amd: lpips_layer expects out float64 ({N},)")
+    return N, H * W, Cc
+
+
+def lpips_layer(fx, fy, lin, out=None):
+    """One layer's LPIPS term per image (diner_lpips_layer_f32): fx, fy (N,H,W,C), lin (C) -> (N,) float64 device tensor: the spatial mean
+    of sum_c lin[c] (fx_c / (|fx| + 1e-10) - fy_c / (|fy| + 1e-10))^2.  out: accumulate into it instead (the sum over the layers)."""
+    N, HW, Cc = _check_lpips_layer_args(fx, fy, lin, out)
+    _require_hip(fx, fy, lin)
+    dev = fx.device
+    if out is not None and out.device != dev:
+        raise RuntimeError("diner_amd: lpips_layer expects out on the features' device; there is no CPU fallback")
+    with torch.cuda.device(dev):
+        ws = _workspace(lib.diner_lpips_layer_workspace_bytes(N, HW), dev)
+        acc = out is not None
+        if not acc:
+            out = torch.empty(N, dtype=torch.float64, device=dev)
+        _lib.check(lib.diner_lpips_layer_f32(_ptr(fx), _ptr(fy), _ptr(lin), N, HW, Cc, int(acc), _ptr(ws), _ptr(out), _stream()))
+    return out
+
+
 def gen_rays(extrinsics, intrinsics, W, H, z_near, z_far, device, ray0=0, n_rays=None):
     """Reference src/util/cam_geometry.py:5-48 on the device: rays [ray0, ray0+n_rays) of each camera's row-major
     (H, W) list -> (B, n_rays, 8).  Camera tensors may live anywhere (they are read on the host: B x 27 floats)."""

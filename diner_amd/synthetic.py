@@ -355,3 +355,30 @@ def patch_case(H, W, s, seed):
     fg[5] = frac
     u = np.array([0.37, 0.5, 0.25, 0.99999994, 0.0, 0.81], np.float32)
     return fg, u
+
+
+VGG_WIDTHS = {"vgg16": (64, 64, 128, 128, 256, 256, 256, 512, 512, 512, 512, 512, 512),
+              "vgg19": (64, 64, 128, 128, 256, 256, 256, 256, 512)}          # vgg19 up to relu4_1, all that vggloss.py reads
+
+
+def make_vgg_state_dict(arch, seed, width_div=1, with_lins=False):
+    """Seeded stand-in for the VGG weights (which are not part of this project): {"features.N.weight", "features.N.bias"} at
+    torchvision's feature indices of `arch` (diner_amd.perceptual.ARCHS), He-normal weights and small biases from an explicit CPU
+    generator, every width divided by width_div (narrow stacks for tests).  with_lins ("vgg16" only): also the five
+    "lin{k}.model.1.weight" tensors (1,C,1,1) of an lpips state dict, non-negative as the trained ones are."""
+    from .perceptual import ARCHS
+    spec = ARCHS[arch]
+    if with_lins and arch != "vgg16":
+        raise ValueError("make_vgg_state_dict: the lin layers belong to LPIPS, which is vgg16")
+    g = torch.Generator().manual_seed(seed)
+    sd, cin = {}, 3
+    for i, width in zip(spec["convs"], VGG_WIDTHS[arch]):
+        cout = max(1, width // width_div)
+        sd[f"features.{i}.weight"] = torch.randn(cout, cin, 3, 3, generator=g) * math.sqrt(2.0 / (9 * cin))
+        sd[f"features.{i}.bias"] = torch.randn(cout, generator=g) * 0.05
+        cin = cout
+    if with_lins:
+        for k, i in enumerate(spec["taps"]):
+            c = sd[f"features.{i}.weight"].shape[0]
+            sd[f"lin{k}.model.1.weight"] = torch.rand(1, c, 1, 1, generator=g) * (2.0 / c)
+    return sd

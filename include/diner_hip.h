@@ -743,6 +743,51 @@ int diner_cloud_reduce_f32(const float* d2, const int* idx, long long n, float m
                            const float* normals_a, const float* normals_b, long long nb_rows, void* workspace, double* out,
                            void* stream);
 
+/* ---- the perceptual network: the VGG convolution stack behind LPIPS and the VGG loss ----------------------------------------------------
+ * New symbols without an ABI bump (perceptual.hip); no allocation, enqueue-only, everything fp32; activations are channels-last
+ * (N,H,W,C) on the device; no floating-point atomics: every sum runs in an order the sizes alone fix, so two runs give the same bits
+ * and an image's values do not depend on its place in the batch.  Bad arguments return DINER_E_INVALID before any device work.
+ * Non-finite inputs are the caller's error: the result is unspecified, nothing faults.
+ *
+ * diner_conv3x3_f32: y = conv(x, w) + bias, 3 x 3, stride 1, zero padding 1, any Cin, Cout >= 1, N <= 65535; then, in this order,
+ *   + addend (N,H,W,Cout) if given, ReLU if relu != 0, zero where !(mask > 0) if mask (N,H,W,Cout) is given.  An implicit GEMM on
+ *   v_mfma_f32_16x16x4_f32: every output is one fp32 fmaf chain that starts at the bias and runs over the input channels in chunks of
+ *   DINER_CONV3X3_CIN_CHUNK, inside a chunk over the nine taps row-major, inside a tap over the chunk's channels.
+ *   wpack: diner_conv3x3_pack_floats(Cin, Cout) floats, 16-byte aligned, [ceil(Cin / 8)][tap ky 3 + kx][8][CoutPad] with CoutPad = Cout
+ *   rounded up to DINER_CONV3X3_COUT_TILE and element = w[cout][cin][ky][kx] of a torch Conv2d weight, zeros beyond Cin and Cout; bias:
+ *   CoutPad floats or NULL.  The data gradient of that convolution is the same call on the gradient with the weight set packed from
+ *   w'[cin][cout][ky][kx] = w[cout][cin][2 - ky][2 - kx]; addend and mask are its epilogue: the loss gradient that enters at the
+ *   activation below, and that activation's ReLU mask.  A call with Cin = 4 on a weight packed for Cin = 3 is valid (same layout).
+ * diner_maxpool2_f32: torch's MaxPool2d(2, 2): y (N, H / 2, W / 2, C), odd sizes floored; H, W >= 2.
+ * diner_maxpool2_bwd_f32: gx (N,H,W,C) from gy (N, H / 2, W / 2, C) and the saved input x: the gradient goes to the first maximum of
+ *   each window in row-major order (a later value wins only if greater, or a NaN), everything else gets 0; then + addend (N,H,W,C) if
+ *   given, then zero where !(x > 0) if relu_mask != 0.
+ * diner_image_in_f32: x (N,3,H,W) -> y (N,H,W,Cs), y = (x - shift[c]) / scale[c], each operation rounded in fp32; Cs is 3, or 4 with
+ *   a zero fourth channel; shift and scale are three floats on the HOST.  diner_image_in_bwd_f32: its adjoint, gx (N,3,H,W) =
+ *   g (N,H,W,Cs)[..., c] / scale[c].
+ * diner_feature_l1_f32: out[0] (device double) = mean |fx - fy| over n elements, the differences (exact) and their sum in double: per
+ *   thread in index order, then over the workgroup, then over the workgroups in order.  grad (n floats, or NULL) = g sign(fx - fy) with
+ *   g = (float)(weight / n), and 0 where !(fx > 0) if mask_by_fx != 0.  workspace: diner_feature_l1_workspace_bytes(n) bytes.
+ * diner_lpips_layer_f32: per image i < N, out[i] (device doubles) = [out[i] +, if accumulate != 0] the mean over the HW pixels of
+ *   sum_c lin[c] (fx_c / (sqrt(sum fx^2) + 1e-10) - fy_c / (sqrt(sum fy^2) + 1e-10))^2, fx, fy (N,HW,C), all arithmetic in double, the
+ *   sums in a fixed order per image.  workspace: diner_lpips_layer_workspace_bytes(N, HW) bytes. */
+#define DINER_CONV3X3_CIN_CHUNK 8
+#define DINER_CONV3X3_COUT_TILE 64
+size_t diner_conv3x3_pack_floats(int Cin, int Cout);
+int diner_conv3x3_f32(const float* x, const float* wpack, const float* bias, const float* addend, const float* mask, float* y, int N, int H,
+                      int W, int Cin, int Cout, int relu, void* stream);
+int diner_maxpool2_f32(const float* x, float* y, int N, int H, int W, int C, void* stream);
+int diner_maxpool2_bwd_f32(const float* x, const float* gy, const float* addend, int relu_mask, float* gx, int N, int H, int W, int C,
+                           void* stream);
+int diner_image_in_f32(const float* x, const float* shift, const float* scale, float* y, int N, int H, int W, int Cs, void* stream);
+int diner_image_in_bwd_f32(const float* g, const float* scale, float* gx, int N, int H, int W, int Cs, void* stream);
+size_t diner_feature_l1_workspace_bytes(long long n);
+int diner_feature_l1_f32(const float* fx, const float* fy, long long n, double weight, int mask_by_fx, float* grad, void* workspace,
+                         double* out, void* stream);
+size_t diner_lpips_layer_workspace_bytes(int N, long long HW);
+int diner_lpips_layer_f32(const float* fx, const float* fy, const float* lin, int N, long long HW, int C, int accumulate, void* workspace,
+                          double* out, void* stream);
+
 /* ---- measurement aid (bench.py): per-kernel durations of the two field kernels ------------------
  * With profiling enabled every field call brackets k_field_pre / k_field_post with HIP events on the
  * launch stream; diner_profile_collect waits for them, returns the summed durations (ms), the number

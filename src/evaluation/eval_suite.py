@@ -4,7 +4,9 @@ the per-image scores (l1, l2, psnr, ssim as skimage / numpy compute them on 8-bi
 create_prediction_folder.py / evaluate_prediction_folder.py / DINER.on_validation_epoch_end call evaluate_folder.
 
 There is no CPU fallback: `device` None means the current HIP device and a CPU device raises RuntimeError.  LPIPS is computed when the
-`lpips` package is importable and its VGG weights can be built, and is otherwise left out of the scores with a warning.
+`lpips` package is importable and its VGG weights can be built, or on the device from the file LPIPS_WEIGHTS names (that network's state
+dict; `evaluate_folder` keeps the reference's signature, so the path is a module attribute that is passed on as
+diner_amd.evaluate.evaluate_folder's `lpips_weights`), and is otherwise left out of the scores with a warning.
 `compare_evaluations` (matplotlib comparison plots) is not provided."""
 from diner_amd import evaluate as _ev
 
@@ -19,6 +21,7 @@ PRED_SUFFIX = _ev.PRED_SUFFIX
 GT_SUFFIX = _ev.GT_SUFFIX
 REF_SUFFIX = _ev.REF_SUFFIX
 DEPTH_SUFFIX = _ev.DEPTH_SUFFIX
+LPIPS_WEIGHTS = None          # a torch.load-able lpips.LPIPS(net="vgg") state dict: LPIPS then runs on the device (diner_amd.perceptual)
 
 
 def evaluate_folder(source_dir, outdir, device=None, pred_suffix=PRED_SUFFIX, gt_suffix=GT_SUFFIX,
@@ -27,7 +30,7 @@ def evaluate_folder(source_dir, outdir, device=None, pred_suffix=PRED_SUFFIX, gt
     """Scores the -gt / -pred pairs of `source_dir` on the device and writes average_scores.json, detailed_report.json and
     examples.png into `outdir`; returns the averages (see diner_amd.evaluate.evaluate_folder)."""
     return _ev.evaluate_folder(source_dir, outdir, device=device, pred_suffix=pred_suffix, gt_suffix=gt_suffix,
-                               ref_suffix=ref_suffix, depth_suffix=depth_suffix, show_tqdm=show_tqdm)
+                               ref_suffix=ref_suffix, depth_suffix=depth_suffix, show_tqdm=show_tqdm, lpips_weights=LPIPS_WEIGHTS)
 
 
 def compare_evaluations(eval_dirs, outdir):
