@@ -27,6 +27,25 @@ class DinerMlpParams(C.Structure):
                 ("lin_z_w", C.POINTER(C.c_void_p)), ("lin_z_b", C.POINTER(C.c_void_p))]
 
 
+class DinerOptimTensor(C.Structure):
+    _fields_ = [("param", C.c_void_p), ("grad", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p), ("numel", C.c_longlong)]
+
+
+class DinerOptimChunk(C.Structure):
+    _fields_ = [("param", C.c_void_p), ("grad", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p), ("numel", C.c_int32),
+                ("tensor", C.c_int32), ("offset", C.c_longlong)]
+
+
+class DinerOptimState(C.Structure):
+    _fields_ = [("step", C.c_longlong * 2), ("skipped", C.c_longlong * 2), ("grad_norm_sq", C.c_double), ("nonfinite", C.c_longlong),
+                ("clip", C.c_double), ("reserved", C.c_longlong)]
+
+
+class DinerAdamHyper(C.Structure):
+    _fields_ = [("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double), ("weight_decay", C.c_double),
+                ("max_norm", C.c_double), ("flags", C.c_uint32), ("slot", C.c_int32)]
+
+
 # name -> (restype, argtypes); must list every symbol include/diner_hip.h declares
 SIGNATURES = {
     "diner_abi_version": (C.c_int, []),
@@ -209,6 +228,10 @@ SIGNATURES = {
     "diner_lpips_layer_workspace_bytes": (C.c_size_t, [C.c_int, C.c_longlong]),
     "diner_lpips_layer_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                         C.c_void_p]),
+    "diner_optim_table_bytes": (C.c_size_t, [C.POINTER(DinerOptimTensor), C.c_int]),
+    "diner_optim_table_build": (C.c_int, [C.POINTER(DinerOptimTensor), C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_int)]),
+    "diner_optim_grad_stats": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "diner_adam_step_f32": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(DinerAdamHyper), C.c_void_p]),
 }
 
 ABI_VERSION = 6          # DINER_ABI_VERSION of include/diner_hip.h
@@ -241,6 +264,8 @@ def load():
 MLP_UPDATE_TRAIN_ONLY = 1      # DINER_MLP_UPDATE_TRAIN_ONLY
 E_INVALID, E_UNSUPPORTED, E_HIP = -1, -2, -3            # DINER_E_* of include/diner_hip.h
 MAX_VIEWS = 16                                          # DINER_MAX_VIEWS: source views a scene may have
+OPTIM_CHUNK = 4096                                      # DINER_OPTIM_CHUNK: elements of one tensor per chunk of the optimiser's table
+ADAM_DECOUPLED_WD, ADAM_CLIP, ADAM_SKIP_NONFINITE, ADAM_ZERO_GRADS = 1, 2, 4, 8       # DINER_ADAM_*
 
 
 def check(rc):

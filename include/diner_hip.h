@@ -788,6 +788,75 @@ size_t diner_lpips_layer_workspace_bytes(int N, long long HW);
 int diner_lpips_layer_f32(const float* fx, const float* fy, const float* lin, int N, long long HW, int C, int accumulate, void* workspace,
                           double* out, void* stream);
 
+/* ---- the optimiser step: Adam / AdamW over all parameter tensors in one launch -----------------------------------------------------------
+ * New symbols without an ABI bump (optim.hip); no allocation, everything fp32; the two device entries are enqueue-only, the two table
+ * entries are host-only arithmetic.  Bad arguments return DINER_E_INVALID (the byte count: 0) with a message before any device work.
+ *
+ * The chunk table.  n records DinerOptimTensor {param, grad, exp_avg, exp_avg_sq, numel} (device addresses; never dereferenced on the
+ *   host) become n_chunks records DinerOptimChunk: each covers at most DINER_OPTIM_CHUNK elements of ONE tensor, the chunks of a tensor
+ *   tile it once, in order, in record order, and every chunk but a tensor's last holds exactly DINER_OPTIM_CHUNK elements -- a multiple of
+ *   4, so a chunk's pointers are 16-byte aligned exactly where the tensor's base pointers are.  A record with numel == 0 contributes no
+ *   chunk; n <= 0, numel < 0 or a null pointer in a record with numel > 0 is refused.  The table buffer is the n_chunks chunk records
+ *   followed by n_chunks 16-byte slots {double sum of squares, int64 non-finite count} that the statistics pass writes (zeroed by the
+ *   build); the table-bytes entry gives the size of both together.  The build fills a caller-provided HOST buffer of that size, which
+ *   the caller uploads (a stream-ordered copy from pinned memory) to a device buffer of the same size.
+ * The state block.  DinerOptimState, 64 bytes on the device, zero before the first step.  step and skipped have two slots: a step launched
+ *   with DinerAdamHyper.slot = s reads slot s and writes slot s ^ 1 (no workgroup reads what the launch writes), so the caller passes
+ *   slot = (number of step launches so far) & 1 and reads the result from the other slot.  The step count lives here, not on the host,
+ *   because a skipped step does not advance it.
+ * diner_optim_grad_stats: grad_norm_sq = the sum of (double)g^2 over all gradients of the table, nonfinite = the number of gradient elements
+ *   that are inf or NaN (they enter the sum: the norm is then non-finite, as torch's).  Two launches: per-chunk partials (per thread in index
+ *   order, the lanes' xor tree, the waves in order), then one workgroup adds the partials in table order.  No atomics, no waiting between
+ *   workgroups: the bits are a function of the table and the values only.  Needed before a step with CLIP or SKIP_NONFINITE.
+ * diner_adam_step_f32: torch.optim.Adam's single-tensor update per element, each operation rounded in fp32 as torch's kernels round it,
+ *     g *= clip;  g += wd p  (or p *= 1 - lr wd with DINER_ADAM_DECOUPLED_WD: AdamW);  m += (1 - beta1)(g - m);  v = beta2 v + (1 - beta2) g g;
+ *     p -= (lr / (1 - beta1^t)) m / (sqrt(v) / sqrt(1 - beta2^t) + eps),      t = step[slot] + 1, the corrections in double on the device.
+ *   DINER_ADAM_CLIP: clip = min(1, max_norm / (sqrt(grad_norm_sq) + 1e-6)), torch's clip_grad_norm_; otherwise 1.
+ *   DINER_ADAM_SKIP_NONFINITE: with nonfinite != 0 nothing is written but skipped[slot ^ 1] = skipped[slot] + 1, step[slot ^ 1] = step[slot],
+ *     clip = 0 and, with DINER_ADAM_ZERO_GRADS, the zeroed gradients; p, m and v keep their bits.
+ *   DINER_ADAM_ZERO_GRADS: every gradient element is overwritten with 0 after it has been read.
+ *   Chunks whose four pointers are 16-byte aligned move 16 bytes per lane and access, with numel % 4 scalar elements at a tensor's end; a
+ *   chunk with a pointer off that boundary is processed element by element. */
+#define DINER_OPTIM_CHUNK 4096
+typedef struct DinerOptimTensor {
+  float* param;
+  float* grad;
+  float* exp_avg;
+  float* exp_avg_sq;
+  long long numel;
+} DinerOptimTensor;
+typedef struct DinerOptimChunk { /* 48 bytes */
+  float* param;                  /* the chunk's first element of each of the four arrays */
+  float* grad;
+  float* exp_avg;
+  float* exp_avg_sq;
+  int32_t numel;                 /* 1 .. DINER_OPTIM_CHUNK */
+  int32_t tensor;                /* index of the record the chunk belongs to */
+  long long offset;              /* of the chunk's first element in its tensor */
+} DinerOptimChunk;
+typedef struct DinerOptimState { /* 64 bytes, device */
+  long long step[2];             /* completed (not skipped) steps */
+  long long skipped[2];          /* steps skipped for a non-finite gradient */
+  double grad_norm_sq;           /* of the last statistics pass */
+  long long nonfinite;           /* of the last statistics pass */
+  double clip;                   /* factor the last step applied to the gradients (0: skipped) */
+  long long reserved;
+} DinerOptimState;
+#define DINER_ADAM_DECOUPLED_WD   1u
+#define DINER_ADAM_CLIP           2u
+#define DINER_ADAM_SKIP_NONFINITE 4u
+#define DINER_ADAM_ZERO_GRADS     8u
+#define DINER_ADAM_ALL_FLAGS      15u
+typedef struct DinerAdamHyper {  /* host */
+  double lr, beta1, beta2, eps, weight_decay, max_norm;
+  uint32_t flags;
+  int32_t slot;
+} DinerAdamHyper;
+size_t diner_optim_table_bytes(const DinerOptimTensor* t, int n);
+int diner_optim_table_build(const DinerOptimTensor* t, int n, void* host_out, size_t bytes, int* n_chunks);
+int diner_optim_grad_stats(void* table, int n_chunks, DinerOptimState* state, void* stream);
+int diner_adam_step_f32(const void* table, int n_chunks, DinerOptimState* state, const DinerAdamHyper* hyper, void* stream);
+
 /* ---- measurement aid (bench.py): per-kernel durations of the two field kernels ------------------
  * With profiling enabled every field call brackets k_field_pre / k_field_post with HIP events on the
  * launch stream; diner_profile_collect waits for them, returns the summed durations (ms), the number

@@ -19,6 +19,7 @@
 #   surface-time [args]        tools/time_surface.py: a 256^3 colour volume fused from sixteen 800 x 600 views (one call / sixteen), count + extract on it, and one 800 x 600 mesh_from_sources (stdout)
 #   raycast-time [args]        tools/time_raycast.py: that 256^3 volume cast back into one and into sixteen 800 x 600 cameras, with and without the brick mask, and the brick build alone (stdout)
 #   cloud-time [args]          tools/time_cloud.py: grid build, nearest neighbour in input and in own-grid order and the sums on 1 M x 1 M and 7.7 M x 5 M points, one child a size, and scipy's k-d tree on the host (stdout)
+#   optim-time [args]          tools/time_optim.py --loop: DeviceAdam.step against torch.optim.Adam (default and fused=True), alternating windows, and the whole fit step against the loop on torch's optimiser (stdout; keep it as profiles/optim_step_ab.txt)
 #   smoke                      __graft_entry__.smoke()
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}" || exit 1
 mkdir -p gpurun_out
@@ -87,6 +88,9 @@ PY
   cloud-time)
     set -o pipefail
     timeout -k 10 1500 python tools/time_cloud.py "$@" 2>&1 | grep -v amdgpu.ids ;;
+  optim-time)
+    set -o pipefail
+    timeout -k 10 900 python tools/time_optim.py --loop "$@" 2>&1 | grep -v amdgpu.ids ;;
   smoke) python __graft_entry__.py smoke ;;
   *) echo "unknown job '$job' (see the header of tools/job.sh)"; exit 2 ;;
 esac
