@@ -228,6 +228,14 @@ SIGNATURES = {
     "diner_lpips_layer_workspace_bytes": (C.c_size_t, [C.c_int, C.c_longlong]),
     "diner_lpips_layer_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                         C.c_void_p]),
+    "diner_conv2d_s2_pack_floats": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "diner_conv2d_s2_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                      C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "diner_maxpool3s2_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "diner_encoder_input_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                          C.c_void_p]),
+    "diner_pyramid_level_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                          C.c_void_p]),
     "diner_optim_table_bytes": (C.c_size_t, [C.POINTER(DinerOptimTensor), C.c_int]),
     "diner_optim_table_build": (C.c_int, [C.POINTER(DinerOptimTensor), C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_int)]),
     "diner_optim_grad_stats": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),

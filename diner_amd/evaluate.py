@@ -56,7 +56,7 @@ def _hip_device(device):
 
 @torch.no_grad()
 def write_prediction_folder(nerf, renderer, batches, outdir, znear, zfar, ray_batch_size=8192, write_alpha=False, cull_empty=False,
-                            write_geometry=False, write_mesh=False, write_volume_view=False):
+                            write_geometry=False, write_mesh=False, write_volume_view=False, device_trunk=False):
     """Render every target view of `batches` (collated sample dicts of diner_amd.datasets) with `nerf` / `renderer` and write
     <sample_name>{-pred,-depth,-ref,-gt}.png into `outdir`: the render and its colour-mapped depth, the source views side by side and
     the target, each quantised as save_image does.  Returns {"sample_name": [...], "l1", "l2", "psnr", "ssim": float64 (N,)} -- the
@@ -71,7 +71,9 @@ def write_prediction_folder(nerf, renderer, batches, outdir, znear, zfar, ray_ba
     sample's source depth maps and colours at its defaults (the prior's surface: no MLP involved, the renders are untouched).
     write_volume_view (off by default): also <sample_name>-vdepth.png and <sample_name>-vnormal.png, that volume ray-cast into the target
     camera (TsdfVolume.raycast): its z-depth through the depth colour map and its camera-frame normals encoded as -normal.png is --
-    the prior's surface as the target camera sees it, no MLP involved.  With write_mesh the two share one volume."""
+    the prior's surface as the target camera sees it, no MLP involved.  With write_mesh the two share one volume.
+    device_trunk (off by default): encode the source views with diner_amd.encoder.DeviceTrunk for this run (SpatialEncoder.device_trunk;
+    it takes effect with `nerf` in eval mode) and put the switch back afterwards."""
     from .datasets import encode_args
     from .imageio import depth_to_uint8, gray_to_uint8, to_uint8
     from .metrics import KEYS, image_metrics
@@ -79,6 +81,14 @@ def write_prediction_folder(nerf, renderer, batches, outdir, znear, zfar, ray_ba
     os.makedirs(outdir, exist_ok=True)
     dev = next(nerf.parameters()).device
     names, scores = [], defaultdict(list)
+    if device_trunk:
+        before = nerf.encoder.device_trunk
+        nerf.encoder.device_trunk = True
+        try:
+            return write_prediction_folder(nerf, renderer, batches, outdir, znear, zfar, ray_batch_size, write_alpha, cull_empty, write_geometry,
+                                           write_mesh, write_volume_view)
+        finally:
+            nerf.encoder.device_trunk = before
     for batch in batches:
         nerf.encode(**encode_args(batch, dev))
         gt = batch["target_rgb"].to(dev)
@@ -298,11 +308,16 @@ def _parser():
     ap.add_argument("--max_dist", type=float, default=float("inf"), help="--geometry: distances beyond it are outliers")
     ap.add_argument("--threshold", type=float, action="append", default=[], help="--geometry: a precision / recall / F-score distance")
     ap.add_argument("--thin", type=float, default=None, help="--geometry: keep one point per cell of this size")
+    ap.add_argument("--device_trunk", action="store_true",
+                    help="encoders of this process compute their latent on the device (SpatialEncoder.device_trunk = True for the run)")
     return ap
 
 
 def main(argv=None):
     args = _parser().parse_args(argv)
+    if args.device_trunk:
+        from src.models.image_encoder import SpatialEncoder
+        SpatialEncoder.device_trunk = True
     source = args.eval_path / "visualizations"
     lp = {} if args.lpips_weights is None else dict(lpips_weights=args.lpips_weights)
     if not args.geometry:

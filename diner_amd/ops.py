@@ -1147,16 +1147,18 @@ def _check_conv3x3_args(x, wpack, bias, Cout, addend, mask):
     return N, H, W, Cin
 
 
-def conv3x3(x, wpack, bias, Cout, relu=False, addend=None, mask=None):
+def conv3x3(x, wpack, bias, Cout, relu=False, addend=None, mask=None, out=None):
     """3 x 3 convolution, stride 1, zero padding 1 (diner_conv3x3_f32): x (N,H,W,Cin) channels-last -> (N,H,W,Cout), = conv + bias, then
     + addend, ReLU, and zero where !(mask > 0), each if given.  wpack / bias: pack_conv3x3's layout and the bias zero-padded to its
     width.  With the transposed weight set this is the data gradient; addend and mask are then the loss gradient entering below and the
-    saved activation."""
+    saved activation.  out (N,H,W,Cout): write there instead of a new tensor (it may be the addend, not x)."""
     N, H, W, Cin = _check_conv3x3_args(x, wpack, bias, Cout, addend, mask)
-    _require_hip(x, wpack, bias, addend, mask)
+    if out is not None:
+        _check_nhwc("conv3x3", "out", out, (N, H, W, int(Cout)))
+    _require_hip(x, wpack, bias, addend, mask, out)
     dev = x.device
     with torch.cuda.device(dev):
-        y = torch.empty(N, H, W, int(Cout), dtype=torch.float32, device=dev)
+        y = out if out is not None else torch.empty(N, H, W, int(Cout), dtype=torch.float32, device=dev)
         _lib.check(lib.diner_conv3x3_f32(_ptr(x), _ptr(wpack), _ptr(bias), _ptr(addend), _ptr(mask), _ptr(y), N, H, W, Cin, int(Cout),
                                          int(bool(relu)), _stream()))
     return y
@@ -1184,6 +1186,156 @@ def maxpool2_bwd(x, gy, addend=None, relu_mask=False):
         gx = torch.empty_like(x)
         _lib.check(lib.diner_maxpool2_bwd_f32(_ptr(x), _ptr(gy), _ptr(addend), int(bool(relu_mask)), _ptr(gx), N, H, W, Cc, _stream()))
     return gx
+
+
+# ---- the image encoder's trunk (encoder.hip) ---------------------------------------------------------------------------------------------
+CONV_S2_KERNELS = (1, 3, 7)      # the kernel sizes diner_conv2d_s2_f32 is built for
+
+
+def pack_conv_s2(weight, Cin=None):
+    """A torch Conv2d weight (Cout,Cin,R,R), R in {1, 3, 7}, in the layout diner_conv2d_s2_f32 reads: [ceil(Cin / 8)][ky R + kx][8][Cout
+    rounded up to 64], zeros beyond Cin and Cout.  Cin: pack for that many input channels (>= the weight's; the added ones are zero), for
+    an input that encoder_input widened.  Plain torch on the weight's own device (done once at load), so it needs no HIP device."""
+    if not torch.is_tensor(weight) or weight.dim() != 4 or weight.shape[2] != weight.shape[3] or weight.shape[2] not in CONV_S2_KERNELS \
+            or weight.shape[0] < 1 or weight.shape[1] < 1:
+        raise ValueError(f"diner_amd: pack_conv_s2 expects a (Cout,Cin,R,R) weight with R in {CONV_S2_KERNELS}, got "
+                         f"{tuple(weight.shape) if torch.is_tensor(weight) else type(weight).__name__}")
+    if weight.dtype != torch.float32:
+        raise ValueError(f"diner_amd: pack_conv_s2 expects float32, got {weight.dtype}")
+    w = weight.detach()
+    Cout, Cw, R = int(w.shape[0]), int(w.shape[1]), int(w.shape[2])
+    Cin = Cw if Cin is None else int(Cin)
+    if Cin < Cw:
+        raise ValueError(f"diner_amd: pack_conv_s2: Cin = {Cin} is less than the weight's {Cw} input channels")
+    cp, op = _pad_to(Cin, CONV3X3_CIN_CHUNK), _pad_to(Cout, CONV3X3_COUT_TILE)
+    p = w.new_zeros(cp, R * R, op)
+    p[:Cw, :, :Cout] = w.reshape(Cout, Cw, R * R).permute(1, 2, 0)
+    return p.view(cp // CONV3X3_CIN_CHUNK, CONV3X3_CIN_CHUNK, R * R, op).permute(0, 2, 1, 3).contiguous()
+
+
+def conv_s2_out_size(n, R):
+    """Output size of a stride-2 convolution with kernel R and zero padding R // 2 along an axis of n pixels."""
+    return (int(n) + 2 * (R // 2) - R) // 2 + 1
+
+
+def _check_conv_s2_args(x, wpack, bias, Cout, R, out, coff):
+    """The argument checks of conv_s2 that need no device -> (N, H, W, Cin, Ho, Wo, ldy)."""
+    N, H, W, Cin = _check_nhwc("conv_s2", "x", x)
+    Cout, R, coff = int(Cout), int(R), int(coff)
+    if R not in CONV_S2_KERNELS:
+        raise NotImplementedError(f"diner_amd: conv_s2 is built for kernel sizes {CONV_S2_KERNELS}, got {R}")
+    want = (_pad_to(Cin, CONV3X3_CIN_CHUNK) // CONV3X3_CIN_CHUNK, R * R, CONV3X3_CIN_CHUNK, _pad_to(max(Cout, 1), CONV3X3_COUT_TILE))
+    if Cout < 1 or not torch.is_tensor(wpack) or wpack.dtype != torch.float32 or tuple(wpack.shape) != want or not wpack.is_contiguous():
+        raise ValueError(f"diner_amd: conv_s2 expects wpack float32 {want} (pack_conv_s2) for Cin {Cin}, Cout {Cout}, R {R}, got "
+                         f"{tuple(wpack.shape) if torch.is_tensor(wpack) else type(wpack).__name__}")
+    if bias is not None and (not torch.is_tensor(bias) or bias.dtype != torch.float32 or bias.dim() != 1 or bias.shape[0] < Cout
+                             or not bias.is_contiguous()):
+        raise ValueError(f"diner_amd: conv_s2 expects bias float32 with at least Cout = {Cout} elements")
+    if N > 65535:
+        raise ValueError(f"diner_amd: conv_s2 takes at most 65535 images a call, got {N}")
+    Ho, Wo = conv_s2_out_size(H, R), conv_s2_out_size(W, R)
+    ldy = Cout
+    if out is not None:
+        No, Hy, Wy, ldy = _check_nhwc("conv_s2", "out", out)
+        if (No, Hy, Wy) != (N, Ho, Wo) or coff < 0 or coff + Cout > ldy:
+            raise ValueError(f"diner_amd: conv_s2 expects out ({N},{Ho},{Wo},>= {coff + Cout}) for channels {coff} .. {coff + Cout - 1}, got "
+                             f"{tuple(out.shape)}")
+    elif coff != 0:
+        raise ValueError("diner_amd: conv_s2: a channel offset needs the output buffer it refers to (out=)")
+    return N, H, W, Cin, Ho, Wo, ldy
+
+
+def conv_s2(x, wpack, bias, Cout, R, relu=False, out=None, coff=0):
+    """R x R convolution, stride 2, zero padding R // 2 (diner_conv2d_s2_f32): x (N,H,W,Cin) channels-last -> (N,Ho,Wo,Cout), = conv +
+    bias, then ReLU if asked.  out (N,Ho,Wo,C >= coff + Cout): write channels coff .. coff + Cout - 1 of it instead (the rest of it is
+    not touched) and return it."""
+    N, H, W, Cin, Ho, Wo, ldy = _check_conv_s2_args(x, wpack, bias, Cout, R, out, coff)
+    _require_hip(x, wpack, bias, out)
+    with torch.cuda.device(x.device):
+        y = out if out is not None else torch.empty(N, Ho, Wo, int(Cout), dtype=torch.float32, device=x.device)
+        _lib.check(lib.diner_conv2d_s2_f32(_ptr(x), _ptr(wpack), _ptr(bias), _ptr(y), N, H, W, Cin, int(Cout), int(R), int(bool(relu)), ldy,
+                                           int(coff), _stream()))
+    return y
+
+
+def _check_maxpool3s2_args(x, C, out):
+    """-> (N, H, W, C, ldx, Ho, Wo); x (N,H,W,ldx) of which channels 0 .. C - 1 are pooled (C None: all)."""
+    N, H, W, ldx = _check_nhwc("maxpool3s2", "x", x)
+    C = ldx if C is None else int(C)
+    if not 1 <= C <= ldx:
+        raise ValueError(f"diner_amd: maxpool3s2: C = {C} channels of an input with {ldx}")
+    Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    if out is not None:
+        _check_nhwc("maxpool3s2", "out", out, (N, Ho, Wo, C))
+    return N, H, W, C, ldx, Ho, Wo
+
+
+def maxpool3s2(x, C=None, out=None):
+    """torch's MaxPool2d(3, 2, 1) on a channels-last activation (diner_maxpool3s2_f32): channels 0 .. C - 1 of x (N,H,W,ldx) ->
+    (N, (H - 1) // 2 + 1, (W - 1) // 2 + 1, C)."""
+    N, H, W, C, ldx, Ho, Wo = _check_maxpool3s2_args(x, C, out)
+    _require_hip(x, out)
+    with torch.cuda.device(x.device):
+        y = out if out is not None else torch.empty(N, Ho, Wo, C, dtype=torch.float32, device=x.device)
+        _lib.check(lib.diner_maxpool3s2_f32(_ptr(x), _ptr(y), N, H, W, C, ldx, _stream()))
+    return y
+
+
+def _check_encoder_input_args(x, ring, pad, C, out):
+    """-> (N, H, W, pad, Cring, C)."""
+    if not torch.is_tensor(x) or x.dim() != 4 or x.shape[1] != 3 or min(x.shape) < 1:
+        raise ValueError(f"diner_amd: encoder_input expects x (N,3,H,W), got {tuple(x.shape) if torch.is_tensor(x) else type(x).__name__}")
+    if x.dtype != torch.float32 or not x.is_contiguous():
+        raise ValueError(f"diner_amd: encoder_input expects x float32 and contiguous, got {x.dtype}, strides {x.stride()}")
+    N, _, H, W = (int(s) for s in x.shape)
+    pad = int(pad)
+    if pad < 0:
+        raise ValueError(f"diner_amd: encoder_input: pad = {pad}")
+    Cring = 0
+    if ring is not None:
+        if not torch.is_tensor(ring) or ring.dtype != torch.float32 or ring.dim() != 3 or tuple(ring.shape[:2]) != (H + 2 * pad, W + 2 * pad) \
+                or ring.shape[2] < 1 or not ring.is_contiguous():
+            raise ValueError(f"diner_amd: encoder_input expects ring float32 ({H + 2 * pad},{W + 2 * pad},Cring), got "
+                             f"{tuple(ring.shape) if torch.is_tensor(ring) else type(ring).__name__}")
+        Cring = int(ring.shape[2])
+    C = 3 + Cring if C is None else int(C)
+    if C < 3 + Cring:
+        raise ValueError(f"diner_amd: encoder_input: C = {C} output channels do not hold 3 + {Cring}")
+    if out is not None:
+        _check_nhwc("encoder_input", "out", out, (N, H + 2 * pad, W + 2 * pad, C))
+    return N, H, W, pad, Cring, C
+
+
+def encoder_input(x, ring=None, pad=0, C=None, out=None):
+    """(N,3,H,W) -> channels-last (N, H + 2 pad, W + 2 pad, C) (diner_encoder_input_f32): the image replication-padded by pad, then the
+    channels of ring (H + 2 pad, W + 2 pad, Cring) -- the positional encoding of the padding ring --, then zeros up to C (default
+    3 + Cring)."""
+    N, H, W, pad, Cring, C = _check_encoder_input_args(x, ring, pad, C, out)
+    _require_hip(x, ring, out)
+    with torch.cuda.device(x.device):
+        y = out if out is not None else torch.empty(N, H + 2 * pad, W + 2 * pad, C, dtype=torch.float32, device=x.device)
+        _lib.check(lib.diner_encoder_input_f32(_ptr(x), _ptr(ring), _ptr(y), N, H, W, pad, Cring, C, _stream()))
+    return y
+
+
+def _check_pyramid_level_args(x, out, c0):
+    """-> (N, h, w, c, Hf, Wf, Ctot)."""
+    N, h, w, c = _check_nhwc("pyramid_level", "x", x)
+    No, Hf, Wf, Ctot = _check_nhwc("pyramid_level", "out", out)
+    c0 = int(c0)
+    if No != N or c0 < 0 or c0 + c > Ctot:
+        raise ValueError(f"diner_amd: pyramid_level expects out ({N},Hf,Wf,>= {c0 + c}) for channels {c0} .. {c0 + c - 1}, got {tuple(out.shape)}")
+    return N, h, w, c, Hf, Wf, Ctot
+
+
+def pyramid_level(x, out, c0):
+    """Bilinear align_corners=True resampling of the level x (N,h,w,c) to out's size, written into channels c0 .. c0 + c - 1 of out
+    (N,Hf,Wf,Ctot) (diner_pyramid_level_f32); the other channels of out are not touched.  -> out."""
+    N, h, w, c, Hf, Wf, Ctot = _check_pyramid_level_args(x, out, c0)
+    _require_hip(x, out)
+    with torch.cuda.device(x.device):
+        _lib.check(lib.diner_pyramid_level_f32(_ptr(x), _ptr(out), N, h, w, c, Hf, Wf, Ctot, int(c0), _stream()))
+    return out
 
 
 def _check_affine(who, shift, scale):

@@ -857,6 +857,42 @@ int diner_optim_table_build(const DinerOptimTensor* t, int n, void* host_out, si
 int diner_optim_grad_stats(void* table, int n_chunks, DinerOptimState* state, void* stream);
 int diner_adam_step_f32(const void* table, int n_chunks, DinerOptimState* state, const DinerAdamHyper* hyper, void* stream);
 
+/* ---- the image encoder's trunk: the ResNet feature pyramid behind DinerScene.latent_cl ---------------------------------------------------
+ * New symbols without an ABI bump (encoder.hip); no allocation, enqueue-only, everything fp32; activations are channels-last (N,H,W,C) on
+ * the device.  Every output is computed in an order the shape alone fixes and no tile crosses images, so an image's values are the same
+ * bits at any place in the batch.  Bad arguments return DINER_E_INVALID (a kernel size that is not built: DINER_E_UNSUPPORTED) with a
+ * message before any device work.  Together with diner_conv3x3_f32 (addend = the block's identity) these are SpatialEncoder.forward in
+ * eval mode, BatchNorm folded into the convolutions: w' = w s, b' = beta - mean s, s = gamma / sqrt(var + eps).
+ *
+ * diner_conv2d_s2_f32: y[..., coff + o] = conv(x, w)[o] + bias[o], R x R with R in {1, 3, 7}, stride 2, zero padding R / 2, any Cin,
+ *   Cout >= 1, N <= 65535; then ReLU if relu != 0.  x (N,H,W,Cin); y (N,Ho,Wo,ldy) with Ho = (H + 2 (R / 2) - R) / 2 + 1 (Wo likewise), of
+ *   which only channels coff .. coff + Cout - 1 are written (ldy = Cout, coff = 0: a dense output).  An implicit GEMM on
+ *   v_mfma_f32_16x16x4_f32: every output is one fp32 fmaf chain that starts at the bias and runs over the input channels in chunks of
+ *   DINER_CONV3X3_CIN_CHUNK, inside a chunk over the kernel rows, inside a row over the kernel columns, inside a tap over the chunk's
+ *   channels.  wpack: diner_conv2d_s2_pack_floats(Cin, Cout, R) floats (0 for arguments the convolution refuses), 16-byte aligned,
+ *   [ceil(Cin / 8)][tap ky R + kx][8][CoutPad], CoutPad = Cout rounded up to DINER_CONV3X3_COUT_TILE, element = w[cout][cin][ky][kx] of a
+ *   torch Conv2d weight, zeros beyond Cin and Cout -- for R = 3 the layout of diner_conv3x3_pack_floats.  bias: Cout floats or NULL.
+ *   With Cin a multiple of 4 and x 16-byte aligned the input is read 16 bytes at a time, else element by element: a caller with 21 (or 3)
+ *   input channels does better to let diner_encoder_input_f32 write 24 (4) and to pack the weights for that Cin -- the zero channels add
+ *   exact zeros, the result is the same bits.
+ * diner_maxpool3s2_f32: torch's MaxPool2d(3, 2, 1): y (N, (H - 1) / 2 + 1, (W - 1) / 2 + 1, C) dense, from x (N,H,W,ldx) of which channels
+ *   0 .. C - 1 are read (ldx >= C; ldx = C: a dense input).  The padding is -inf, not 0; a NaN in a window is its result.
+ * diner_encoder_input_f32: x (N,3,H,W) -> y (N, H + 2 pad, W + 2 pad, C): channels 0 .. 2 the image, replication-padded by pad;
+ *   channels 3 .. 3 + Cring - 1 a copy of ring (H + 2 pad, W + 2 pad, Cring), the positional encoding of the padding ring (zero inside
+ *   the image), the same for every image; channels beyond that zero.  C >= 3 + Cring; pad = 0, Cring = 0, C = 3 is a plain relayout.
+ * diner_pyramid_level_f32: bilinear resampling with align_corners = True (torch's F.interpolate; evaluated in double, rounded once) of x (N,h,w,c) to
+ *   Hf x Wf, written to channels c0 .. c0 + c - 1 of y (N,Hf,Wf,Ctot); no other channel is touched.  Source coordinate
+ *   dst (h - 1) / (Hf - 1), scale 0 when Hf = 1.  h = Hf and w = Wf is a copy, bit for bit.  N, Hf <= 65535.  With c, Ctot and c0 multiples
+ *   of 4 and both pointers 16-byte aligned it moves 16 bytes per access, else 4.
+ *
+ * A torch-free caller's sequence from four normalised images to DinerScene.latent_cl is in INTEGRATION.md ("Encoding source views"). */
+size_t diner_conv2d_s2_pack_floats(int Cin, int Cout, int R);
+int diner_conv2d_s2_f32(const float* x, const float* wpack, const float* bias, float* y, int N, int H, int W, int Cin, int Cout, int R, int relu,
+                        int ldy, int coff, void* stream);
+int diner_maxpool3s2_f32(const float* x, float* y, int N, int H, int W, int C, int ldx, void* stream);
+int diner_encoder_input_f32(const float* x, const float* ring, float* y, int N, int H, int W, int pad, int Cring, int C, void* stream);
+int diner_pyramid_level_f32(const float* x, float* y, int N, int h, int w, int c, int Hf, int Wf, int Ctot, int c0, void* stream);
+
 /* ---- measurement aid (bench.py): per-kernel durations of the two field kernels ------------------
  * With profiling enabled every field call brackets k_field_pre / k_field_post with HIP events on the
  * launch stream; diner_profile_collect waits for them, returns the summed durations (ms), the number

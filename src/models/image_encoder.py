@@ -8,6 +8,8 @@ state-dict keys (`model.*` = torchvision ResNet names, `positional_encoding._fre
 * `forward` (the ResNet34 trunk, :225-291) is per-image setup, not part of the hot path: plain torch ops
   (MIOpen convolutions on ROCm).  torchvision is not in the MI355X image, so the trunk is defined here with
   torchvision's module names; torchvision is used instead when it is importable (e.g. for pretrained weights).
+  With `device_trunk = True` (off by default) inference computes the latent in this library's own kernels instead
+  (diner_amd/encoder.py: BatchNorm folded, fp32 MFMA convolutions); training keeps the torch ops.
 """
 import functools
 
@@ -75,6 +77,11 @@ def _make_backbone(backbone, pretrained, norm_layer):
 
 
 class SpatialEncoder(nn.Module):
+    # opt-in (an attribute, not a constructor argument of the reference): in eval mode, with grad mode off and the images on the HIP device,
+    # forward() computes the latent with diner_amd.encoder.DeviceTrunk instead of the torch ops
+    device_trunk = False
+    _device_trunk = None
+
     def __init__(self, backbone="resnet34", pretrained=True, num_layers=4, index_interp="bilinear",
                  index_padding="border", upsample_interp="bilinear", use_first_pool=True, image_padding=0,
                  padding_pe=-1):
@@ -169,6 +176,14 @@ class SpatialEncoder(nn.Module):
         self._scene_cache = {}                       # new maps: nothing cached for the previous ones may be served
         self.depths, self.depths_std, self.normals = depths, depths_std, normals
         self.nviews, self.nobjects = NV, SB
+        if self.device_trunk and not self.training and not torch.is_grad_enabled() and imgs.is_cuda:
+            # inference: the trunk in this library's own kernels (diner_amd/encoder.py), BatchNorm folded; everything else -- training,
+            # grad mode, CPU tensors -- takes the torch ops below
+            if self._device_trunk is None:
+                from diner_amd import encoder
+                self._device_trunk = encoder.DeviceTrunk(self)
+            self.latent = self._device_trunk(imgs)
+            return
         x = self.pad_layer(imgs.view(SB * NV, Cin, H, W))
         if self.padding_pe >= 0 and self.feature_padding > 0:
             p = self.image_padding
