@@ -343,6 +343,15 @@ struct ARing {
   unsigned avoff;
   __device__ __forceinline__ void load_a2(h8 (&dst)[8], int pair) {      // fragments 2 pair, 2 pair + 1 of the half-step at abase
     asm volatile("" : "+s"(abase));
+    // The lane offset is made opaque HERE as well, as a 32-bit value: the load can take `SGPR pair + 32-bit VGPR + immediate` only where
+    // instruction selection sees the offset being widened in the block of the load.  Left alone, the widened offset was hoisted out of the
+    // tile loop as a 64-bit value in the per-view kernels (their rings start blocks ahead of the GEMM) and every pair of fragments paid a
+    // v_lshl_add_u64: 397 of them between the MFMAs of k_field_pre_h3n, 20 % of a fc_0 GEMM's vector-ALU instructions, against 2 in the
+    // post kernel.  Without them: 1913.9 -> 1877.5 ms per 800 x 600 frame (-1.9 %, parent spread 0.23 %; profiles/weight_ring_ab_runs.txt);
+    // a buffer descriptor as ARing8's would reach the same form for 4 more scalar registers per live ring.
+    // Cache policy: default.  Non-temporal weight loads (they bypass the L1, which the stream can never hit) LOSE 16.6 % --
+    // 2230.5 ms, same file; the arm is kept in tools/ubench/weight_ring_nt.hip.txt.
+    asm volatile("" : "+v"(avoff));
 #pragma unroll
     for (int i = 2 * pair; i < 2 * pair + 2; ++i)
       dst[i] = *(const __attribute__((address_space(1))) h8*)(abase + avoff + (i * 1024 - 4096));
@@ -709,12 +718,20 @@ __device__ __forceinline__ void save_block(float* __restrict__ dst, unsigned* __
                                            const f32x4 (&acc)[kSlice][kGroups]) {
   static_assert(kSlice == 8, "one dword of decisions per lane");
   const int q = lane >> 4, n = lane & 15;
+  // PER_VIEW (k_train_fwd_pre) forms its addresses as ARing does: the group's first row as a scalar base (wave-uniform: 64 bits on the scalar
+  // ALU), the lane's place inside the group's 16 rows as one 32-bit offset, the row tile as an immediate -- a per-lane 64-bit row address cost
+  // a v_lshl_add_u64 per group and plane (31 of them between the kernel's GEMMs) and two registers each: 228 -> 128 bytes of scratch per
+  // lane.  The post kernel keeps per-lane addresses: it has no scalar registers left for the bases (the same form there: 12 -> 16 bytes of
+  // scratch per lane, profiles/weight_ring_resources.txt).
+  unsigned row_off = (unsigned)n * (kHidden * 4) + (unsigned)(128 * wave + 4 * q) * 4, bit_off = (unsigned)n * 64 + (unsigned)(4 * wave + q) * 4;
 #pragma unroll
   for (int g = 0; g < kGroups; ++g) {
-    const long long p = PER_VIEW ? tile * kPtsPerWave + n : (tile * 4 + g) * kPtsPerWave + n;
-    if (p >= P) continue;
-    const size_t r = (PER_VIEW ? (size_t)g * P : (size_t)0) + (size_t)p;
-    float* row = dst + r * kHidden + 128 * wave + 4 * q;
+    const long long p0 = PER_VIEW ? tile * kPtsPerWave : (tile * 4 + g) * kPtsPerWave;
+    if (p0 + n >= P) continue;
+    const size_t r0 = (PER_VIEW ? (size_t)g * P : (size_t)0) + (size_t)p0;
+    gbytes rows = (gbytes)(reinterpret_cast<char*>(dst) + r0 * (kHidden * 4)), brows = (gbytes)(reinterpret_cast<char*>(bits) + r0 * 64);
+    if constexpr (PER_VIEW) asm volatile("" : "+s"(rows), "+v"(row_off));
+    float* row = dst + (r0 + n) * kHidden + 128 * wave + 4 * q;
     unsigned m = 0;
 #pragma unroll
     for (int mo = 0; mo < kSlice; ++mo) {
@@ -726,9 +743,17 @@ __device__ __forceinline__ void save_block(float* __restrict__ dst, unsigned* __
         v[i] = __int_as_float(xi) * kInvScale;
         m |= (v[i] > 0.0f ? 1u : 0u) << (4 * mo + i);
       }
-      *reinterpret_cast<f32x4*>(row + 16 * mo) = v;
+      if constexpr (PER_VIEW) *(gf32x4)(rows + row_off + mo * 64) = v;
+      else *reinterpret_cast<f32x4*>(row + 16 * mo) = v;
     }
-    if (bits) bits[r * 16 + 4 * wave + q] = m;
+    if (bits) {
+      if constexpr (PER_VIEW) {
+        asm volatile("" : "+s"(brows), "+v"(bit_off));
+        *(__attribute__((address_space(1))) unsigned*)(brows + bit_off) = m;
+      } else {
+        bits[(r0 + n) * 16 + 4 * wave + q] = m;
+      }
+    }
   }
 }
 
