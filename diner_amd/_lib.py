@@ -240,6 +240,12 @@ SIGNATURES = {
     "diner_optim_table_build": (C.c_int, [C.POINTER(DinerOptimTensor), C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_int)]),
     "diner_optim_grad_stats": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "diner_adam_step_f32": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(DinerAdamHyper), C.c_void_p]),
+    "diner_mvs_cost_volume_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "diner_mvs_select_depth_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                             C.c_int, C.c_void_p]),
+    "diner_mvs_hypotheses_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
+                                           C.c_void_p]),
 }
 
 ABI_VERSION = 6          # DINER_ABI_VERSION of include/diner_hip.h
@@ -273,6 +279,7 @@ MLP_UPDATE_TRAIN_ONLY = 1      # DINER_MLP_UPDATE_TRAIN_ONLY
 E_INVALID, E_UNSUPPORTED, E_HIP = -1, -2, -3            # DINER_E_* of include/diner_hip.h
 MAX_VIEWS = 16                                          # DINER_MAX_VIEWS: source views a scene may have
 OPTIM_CHUNK = 4096                                      # DINER_OPTIM_CHUNK: elements of one tensor per chunk of the optimiser's table
+MVS_PIXELWISE_FLOATS, MVS_MAX_DEPTHS, MVS_MAX_CHANNELS = 177, 256, 64   # DINER_MVS_*
 ADAM_DECOUPLED_WD, ADAM_CLIP, ADAM_SKIP_NONFINITE, ADAM_ZERO_GRADS = 1, 2, 4, 8       # DINER_ADAM_*
 
 

@@ -13,7 +13,7 @@ ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(ROOT, "build", "obj")
 LIB = os.path.join(HERE, "libdiner_hip.so")
-SOURCES = ["api.cpp", "sampler.hip", "composite.hip", "stage_ops.hip", "prep.hip", "train.hip", "train_512.hip", "mlp.hip", "mlp_h3n.hip", "generic.hip", "metrics.hip", "objective.hip", "cull.hip", "geometry.hip", "surface.hip", "raycast.hip", "cloud.hip", "perceptual.hip", "optim.hip", "encoder.hip"]
+SOURCES = ["api.cpp", "sampler.hip", "composite.hip", "stage_ops.hip", "prep.hip", "train.hip", "train_512.hip", "mlp.hip", "mlp_h3n.hip", "generic.hip", "metrics.hip", "objective.hip", "cull.hip", "geometry.hip", "surface.hip", "raycast.hip", "cloud.hip", "perceptual.hip", "optim.hip", "encoder.hip", "mvs.hip"]
 # -ffp-contract=off: every fp32 op of the geometry path rounds where the reference's torch ops round;
 # fused multiply-adds are written explicitly (fmaf / MFMA) where they are wanted.
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-Wno-unused-value",
@@ -27,6 +27,7 @@ EXTRA_FLAGS = {
     "perceptual.hip": ["-Rpass-analysis=kernel-resource-usage"],
     "optim.hip": ["-Rpass-analysis=kernel-resource-usage"],     # k_adam and k_grad_stats must stay free of scratch
     "encoder.hip": ["-Rpass-analysis=kernel-resource-usage"],   # k_conv_s2<1 | 3 | 7> must stay free of scratch
+    "mvs.hip": ["-Rpass-analysis=kernel-resource-usage"],       # k_mvs_cost_volume<1 .. 16> must stay free of scratch
 }
 
 

@@ -138,6 +138,29 @@ def read_transmvsnet_png(path, dtu_rescale=False):
     return out
 
 
+def write_transmvsnet_png(path, values, dtu_rescale=False):
+    """The inverse of read_transmvsnet_png: float (H,W) depth or confidence (array or tensor) -> 16-bit grey PNG with the estimator's
+    float32_2_uint16 (utils.py:21-23): clip at 6.5535, divide by 1e-4, round to nearest (ties to even), uint16.  dtu_rescale multiplies by
+    0.7 / 872 first, the factor the reader divides out.  -> the uint16 array written."""
+    a = values.detach().cpu().numpy() if hasattr(values, "detach") else np.asarray(values)
+    a = np.asarray(a, dtype=np.float32)
+    if a.ndim != 2:
+        raise ValueError(f"write_transmvsnet_png expects one (H,W) map, got shape {a.shape}")
+    if dtu_rescale:
+        a = a * np.float32(DTU_DEPTH_RESCALE)
+    q = (a.clip(max=65535 * TRANSMVSNET_SCALE) / TRANSMVSNET_SCALE).round().astype(np.uint16)
+    H, W = q.shape
+    raw = np.concatenate([np.zeros((H, 1), np.uint8), q.astype(">u2").view(np.uint8).reshape(H, 2 * W)], axis=1).tobytes()
+
+    def chunk(tag, data):
+        return struct.pack(">I", len(data)) + tag + data + struct.pack(">I", zlib.crc32(tag + data) & 0xffffffff)
+
+    with open(path, "wb") as f:
+        f.write(b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", struct.pack(">IIBBBBB", W, H, 16, 0, 0, 0, 0)) + chunk(b"IDAT", zlib.compress(raw, 6)) +
+                chunk(b"IEND", b""))
+    return q
+
+
 CONF_TO_STD = {"dtu": (-2.5679e-2, 3.2818e-2),          # dtu.py:68-70
                "facescape": (-1.582e-2, 1.649e-2),      # facescape.py:50-52
                "multiface": (-1.582e-2, 1.649e-2)}      # multiface.py:309, then clipped at 0 and zeroed where depth == 0

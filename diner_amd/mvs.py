@@ -1,0 +1,347 @@
+"""The matching stage of the multi-view depth estimator on the device: what TransMVSNet's DepthNet.forward (models/TransMVSNet.py:37-106)
+and the stage loop of TransMVSNet.forward do between the learned networks -- homography warping fused with the feature similarity, the
+pixelwise view weights, the weighted aggregation, the winner-take-all read-out of the regularised cost and the next stage's depth
+hypotheses -- on the kernels of csrc/mvs.hip.  FeatureNet, the FMT transformer and CostRegNet stay the caller's torch modules.
+
+Every thin function takes the reference's tensor layouts (NCHW).  On HIP tensors it runs the kernels; on CPU tensors it runs a torch
+restatement of the same mathematics with the reference's own operations in the reference's order (`*_torch`, any floating dtype),
+which is the host oracle of the tests and the baseline of tools/time_mvs.py.  Inference only: nothing here has a backward pass;
+DeviceDepthNet uses torch operations whenever gradients are enabled or the module is in training mode."""
+import numpy as np
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+from . import formats
+
+BN_EPS = 1e-5                      # torch.nn.BatchNorm3d's default, which the reference's ConvBnReLU3D keeps
+PIXELWISE_KEYS = ("conv0.conv.weight", "conv0.bn.weight", "conv0.bn.bias", "conv0.bn.running_mean", "conv0.bn.running_var",
+                  "conv1.conv.weight", "conv1.bn.weight", "conv1.bn.bias", "conv1.bn.running_mean", "conv1.bn.running_var",
+                  "conv2.weight", "conv2.bias")
+STAGE_SCALES = (4, 2, 1)           # stage1 .. stage3 of TransMVSNet.stage_infos
+
+
+def _ops():
+    from . import ops              # loads libdiner_hip.so; only the device route needs it
+    return ops
+
+
+# ---- the pixelwise view-weight net --------------------------------------------------------------------------------------------------
+class Pixelwise:
+    """PixelwiseNet's parameters: `raw`, the tensors under the reference's keys (what the restatement evaluates, BatchNorm unfolded like
+    the reference), and `folded`, the 177 float32 values w0[16] b0[16] w1[8][16] b1[8] w2[8] b2 of diner_mvs_cost_volume_f32 with
+    BatchNorm's running statistics folded in float64 and rounded once."""
+
+    def __init__(self, raw, folded):
+        self.raw, self.folded = raw, folded
+
+
+def fold_pixelwise(state_dict, prefix=""):
+    """DepthNet.pixel_wise_net's state dict (keys conv0.conv.weight, conv0.bn.*, conv1.conv.weight, conv1.bn.*, conv2.weight, conv2.bias
+    under `prefix`) -> Pixelwise.  Runs on the tensors' own device without a host read-back."""
+    missing = [k for k in PIXELWISE_KEYS if prefix + k not in state_dict]
+    if missing:
+        raise KeyError(f"diner_amd: fold_pixelwise misses {[prefix + k for k in missing]}")
+    raw = {k: state_dict[prefix + k].detach() for k in PIXELWISE_KEYS}
+    want = {"conv0.conv.weight": (16, 1, 1, 1, 1), "conv1.conv.weight": (8, 16, 1, 1, 1), "conv2.weight": (1, 8, 1, 1, 1), "conv2.bias": (1,)}
+    for k, shape in want.items():
+        if tuple(raw[k].shape) != shape:
+            raise ValueError(f"diner_amd: fold_pixelwise expects {prefix + k} of shape {shape}, got {tuple(raw[k].shape)}")
+    parts = []
+    for i, (cout, cin) in enumerate(((16, 1), (8, 16))):
+        p = f"conv{i}."
+        s = raw[p + "bn.weight"].double() / torch.sqrt(raw[p + "bn.running_var"].double() + BN_EPS)
+        parts.append(((raw[p + "conv.weight"].double().view(cout, cin) * s.view(-1, 1)).reshape(-1),
+                      raw[p + "bn.bias"].double() - raw[p + "bn.running_mean"].double() * s))
+    (w0, b0), (w1, b1) = parts
+    folded = torch.cat([w0, b0, w1, b1, raw["conv2.weight"].double().reshape(-1), raw["conv2.bias"].double().reshape(-1)]).to(torch.float32)
+    return Pixelwise(raw, folded)
+
+
+def pixelwise_torch(raw, similarity):
+    """PixelwiseNet.forward: similarity (B,1,D,H,W) -> view weight (B,1,H,W) = max_d sigmoid(conv2(conv1(conv0(similarity)))), each of
+    conv0 / conv1 a 1x1x1 convolution, BatchNorm on its running statistics and a ReLU, in the similarity's dtype."""
+    x, dt = similarity, similarity.dtype
+    for p in ("conv0.", "conv1."):
+        x = F.conv3d(x, raw[p + "conv.weight"].to(dt))
+        x = F.relu(F.batch_norm(x, raw[p + "bn.running_mean"].to(dt), raw[p + "bn.running_var"].to(dt), raw[p + "bn.weight"].to(dt),
+                                raw[p + "bn.bias"].to(dt), False, 0.0, BN_EPS))
+    x = F.conv3d(x, raw["conv2.weight"].to(dt), raw["conv2.bias"].to(dt)).squeeze(1)
+    return torch.max(torch.sigmoid(x), dim=1, keepdim=True)[0]
+
+
+# ---- the torch restatement ------------------------------------------------------------------------------------------------------------
+def _full_proj(pair):
+    """(B,2,4,4) camera pair -> the extrinsics with their top three rows replaced by K[:3,:3] E[:3,:4]."""
+    out = pair[:, 0].clone()
+    out[:, :3, :4] = torch.matmul(pair[:, 1, :3, :3], pair[:, 0, :3, :4])
+    return out
+
+
+def warp_torch(src_fea, src_proj, ref_proj, depth_values):
+    """homo_warping (models/module.py:284-322) in src_fea's dtype: the source features (B,C,H,W) sampled where the reference view's pixels
+    land at each depth hypothesis (B,D,H,W) -> (B,C,D,H,W).  Materialises the grid and the warped volume, as the reference does."""
+    B, C, H, W = src_fea.shape
+    D = depth_values.shape[1]
+    dt, dev = src_fea.dtype, src_fea.device
+    with torch.no_grad():                        # the sampling positions carry no gradient, as in the reference
+        proj = torch.matmul(src_proj, torch.inverse(ref_proj))
+        rot, trans = proj[:, :3, :3], proj[:, :3, 3:4]
+        y, x = torch.meshgrid(torch.arange(0, H, dtype=dt, device=dev), torch.arange(0, W, dtype=dt, device=dev), indexing="ij")
+        y, x = y.contiguous().view(H * W), x.contiguous().view(H * W)
+        xyz = torch.stack((x, y, torch.ones_like(x))).unsqueeze(0).repeat(B, 1, 1)
+        rot_xyz = torch.matmul(rot, xyz)
+        rot_depth_xyz = rot_xyz.unsqueeze(2).repeat(1, 1, D, 1) * depth_values.reshape(B, 1, D, -1)
+        proj_xyz = rot_depth_xyz + trans.view(B, 3, 1, 1)
+        invalid = (proj_xyz[:, 2:3] < 1e-6).squeeze(1)
+        proj_xy = proj_xyz[:, :2] / proj_xyz[:, 2:3]
+        gx = proj_xy[:, 0] / ((W - 1) / 2) - 1
+        gx[invalid] = -99.
+        gy = proj_xy[:, 1] / ((H - 1) / 2) - 1
+        gy[invalid] = -99.
+        grid = torch.stack((gx, gy), dim=3)
+    warped = F.grid_sample(src_fea, grid.view(B, D * H, W, 2), mode="bilinear", padding_mode="zeros", align_corners=True)
+    return warped.view(B, C, D, H, W)
+
+
+def cost_volume_torch(features, proj_matrices, depth_values, pixelwise=None, view_weights=None):
+    """Steps 1-2 of DepthNet.forward, in features[0]'s dtype -> (similarity (B,1,D,H,W), view weights (B,NS,H,W)).
+    pixelwise: a Pixelwise, or any callable similarity (B,1,D,H,W) -> weight (B,1,H,W) such as the module itself."""
+    dt = features[0].dtype
+    weight_of = pixelwise if callable(pixelwise) else (lambda s: pixelwise_torch(pixelwise.raw, s))
+    projs = torch.unbind(proj_matrices.to(dt), 1)
+    ref_feature, ref_proj = features[0], _full_proj(projs[0])
+    depth_values = depth_values.to(dt)
+    weights, sim_sum, w_sum = [], 0, 1e-5
+    for i, (src_fea, src_pair) in enumerate(zip(features[1:], projs[1:])):
+        warped = warp_torch(src_fea, _full_proj(src_pair), ref_proj, depth_values)
+        similarity = (warped * ref_feature.unsqueeze(2)).mean(1, keepdim=True)
+        del warped
+        if view_weights is None:
+            w = weight_of(similarity)
+            weights.append(w)
+        else:
+            w = view_weights[:, i:i + 1].to(dt)
+        sim_sum = sim_sum + similarity * w.unsqueeze(1)
+        w_sum = w_sum + w.unsqueeze(1)
+    return sim_sum / w_sum, (torch.cat(weights, dim=1) if view_weights is None else view_weights)
+
+
+def select_depth_torch(cost, depth_values, prob_init=None):
+    """Step 3 of DepthNet.forward after the regulariser -> (depth (B,H,W), confidence (B,H,W), prob volume (B,D,H,W))."""
+    pre = cost if prob_init is None else cost + prob_init
+    prob = torch.exp(F.log_softmax(pre, dim=1))
+    index = torch.argmax(prob, dim=1, keepdim=True)
+    return torch.gather(depth_values, 1, index).squeeze(1), torch.max(prob, dim=1)[0], prob
+
+
+def depth_hypotheses_torch(cur_depth, ndepth, interval, image_hw, stage_scale):
+    """The hypotheses of stages 2 and 3 as TransMVSNet.forward forms them: the previous depth (B,h,w) bilinearly resized to the image,
+    get_cur_depth_range_samples (models/module.py:590-599), then the trilinear resize to (ndepth, H // s, W // s)."""
+    H, W = (int(v) for v in image_hw)
+    s = int(stage_scale)
+    up = F.interpolate(cur_depth.unsqueeze(1), [H, W], mode="bilinear", align_corners=False).squeeze(1)
+    lo = up - ndepth / 2 * interval
+    hi = up + ndepth / 2 * interval
+    step = (hi - lo) / (ndepth - 1)
+    samples = lo.unsqueeze(1) + torch.arange(0, ndepth, device=up.device, dtype=up.dtype).reshape(1, -1, 1, 1) * step.unsqueeze(1)
+    return F.interpolate(samples.unsqueeze(1), [ndepth, H // s, W // s], mode="trilinear", align_corners=False).squeeze(1)
+
+
+# ---- the thin functions ---------------------------------------------------------------------------------------------------------------
+def _check_features(features, proj_matrices, depth_values):
+    if len(features) < 2 or any(f.dim() != 4 or f.shape != features[0].shape for f in features):
+        raise ValueError("diner_amd: cost_volume expects a list of at least two feature maps (B,C,H,W) of one shape, reference first")
+    B, _, H, W = features[0].shape
+    if proj_matrices.dim() != 5 or tuple(proj_matrices.shape) != (B, len(features), 2, 4, 4):
+        raise ValueError(f"diner_amd: cost_volume expects proj_matrices ({B},{len(features)},2,4,4), got {tuple(proj_matrices.shape)}")
+    if depth_values.dim() != 4 or depth_values.shape[0] != B or tuple(depth_values.shape[2:]) != (H, W):
+        raise ValueError(f"diner_amd: cost_volume expects depth_values ({B},D,{H},{W}), got {tuple(depth_values.shape)}")
+
+
+def cost_volume(features, proj_matrices, depth_values, pixelwise=None, view_weights=None):
+    """features: [reference, source 1, ...] each (B,C,H,W); proj_matrices (B,NV,2,4,4); depth_values (B,D,H,W); pixelwise: a Pixelwise
+    (fold_pixelwise) when the view weights are to be computed, else view_weights (B,NV-1,H,W)
+    -> (aggregated similarity (B,1,D,H,W), view weights (B,NV-1,H,W))."""
+    _check_features(features, proj_matrices, depth_values)
+    if (pixelwise is None) == (view_weights is None):
+        raise ValueError("diner_amd: cost_volume takes either pixelwise (a Pixelwise) or view_weights")
+    if not features[0].is_cuda:
+        B, Cf, H, W = features[0].shape
+        _ops()._check_mvs_limits(B, len(features) - 1, Cf, depth_values.shape[1], H, W)       # the device route's limits hold here too
+        return cost_volume_torch(features, proj_matrices, depth_values, pixelwise, view_weights)
+    ops = _ops()
+    cl = torch.stack([f.detach() for f in features], 0).to(torch.float32).permute(0, 1, 3, 4, 2).contiguous()      # the one repack
+    sim, weights = ops.mvs_cost_volume(cl[0], cl[1:], proj_matrices.detach().to(torch.float32), depth_values.detach().to(torch.float32),
+                                       None if pixelwise is None else pixelwise.folded,
+                                       None if view_weights is None else view_weights.detach().to(torch.float32))
+    return sim.unsqueeze(1), weights
+
+
+def select_depth(cost, depth_values, prob_init=None, return_prob=True):
+    """cost (B,D,H,W) or (B,1,D,H,W) from the regulariser [+ prob_init], depth_values (B,D,H,W)
+    -> (depth (B,H,W), confidence (B,H,W), prob volume (B,D,H,W) or None)."""
+    if cost.dim() == 5 and cost.shape[1] == 1:
+        cost = cost.squeeze(1)
+    if not cost.is_cuda:
+        depth, conf, prob = select_depth_torch(cost, depth_values, prob_init)
+        return depth, conf, (prob if return_prob else None)
+    return _ops().mvs_select_depth(cost.detach().to(torch.float32), depth_values.detach().to(torch.float32),
+                                   None if prob_init is None else prob_init.detach().to(torch.float32), return_prob)
+
+
+def depth_hypotheses(cur_depth, ndepth, interval, image_hw, stage_scale):
+    """The previous stage's depth (B,h,w) -> this stage's hypotheses (B, ndepth, H // s, W // s), spread over ndepth * interval around it.
+    interval: this stage's depth interval (ratio x the estimator's base interval), a host number."""
+    ops = _ops()
+    ops._check_mvs_hypotheses_args(cur_depth, ndepth, image_hw, stage_scale)
+    if not cur_depth.is_cuda:
+        return depth_hypotheses_torch(cur_depth, int(ndepth), float(interval), image_hw, stage_scale)
+    return ops.mvs_hypotheses(cur_depth.detach().to(torch.float32), int(ndepth), int(ndepth) / 2 * float(interval), image_hw, stage_scale)
+
+
+# ---- the drop-in for the reference's DepthNet ----------------------------------------------------------------------------------------
+class _ConvBnReLU3d(nn.Module):
+    def __init__(self, cin, cout):
+        super().__init__()
+        self.conv = nn.Conv3d(cin, cout, 1, bias=False)
+        self.bn = nn.BatchNorm3d(cout)
+
+    def forward(self, x):
+        return F.relu(self.bn(self.conv(x)))
+
+
+class _PixelwiseNet(nn.Module):
+    """The parameters of the reference's PixelwiseNet under its state-dict keys; forward() serves the torch route (in training mode on batch
+    statistics)."""
+
+    def __init__(self):
+        super().__init__()
+        self.conv0, self.conv1 = _ConvBnReLU3d(1, 16), _ConvBnReLU3d(16, 8)
+        self.conv2 = nn.Conv3d(8, 1, 1)
+
+    def forward(self, x):
+        return torch.max(torch.sigmoid(self.conv2(self.conv1(self.conv0(x))).squeeze(1)), dim=1, keepdim=True)[0]
+
+
+class DeviceDepthNet(nn.Module):
+    """A replacement for the reference's DepthNet: the same state-dict keys (pixel_wise_net.*), the same forward() signature and results.
+    On HIP tensors, in eval mode and with gradients disabled it runs the kernels; otherwise torch operations (which are
+    differentiable, so fine-tuning keeps working).  `model.DepthNet = DeviceDepthNet.from_module(model.DepthNet)` switches a loaded
+    TransMVSNet over."""
+
+    def __init__(self):
+        super().__init__()
+        self.pixel_wise_net = _PixelwiseNet()
+        self._folded, self._folded_key = None, None
+
+    @classmethod
+    def from_module(cls, depthnet):
+        new = cls()
+        new.load_state_dict(depthnet.state_dict())
+        p = next(depthnet.parameters())
+        new.to(p.device)
+        new.train(depthnet.training)
+        return new
+
+    def pixelwise(self):
+        """The Pixelwise of the current parameters; folded again only after a parameter or buffer changed (no host read-back either way)."""
+        sd = self.pixel_wise_net.state_dict()
+        key = tuple((k, v.data_ptr(), v._version, str(v.device)) for k, v in sd.items())
+        if key != self._folded_key:
+            self._folded, self._folded_key = fold_pixelwise(sd), key
+        return self._folded
+
+    def uses_kernels(self, features):
+        return features[0].is_cuda and not self.training and not torch.is_grad_enabled()
+
+    def forward(self, features, proj_matrices, depth_values, num_depth, cost_regularization, prob_volume_init=None, view_weights=None):
+        if len(features) != proj_matrices.shape[1]:
+            raise ValueError("diner_amd: DeviceDepthNet: different number of images and projection matrices")
+        if depth_values.shape[1] != num_depth:
+            raise ValueError(f"diner_amd: DeviceDepthNet: depth_values has {depth_values.shape[1]} planes, num_depth is {num_depth}")
+        given = view_weights is not None
+        if self.uses_kernels(features):
+            similarity, weights = cost_volume(features, proj_matrices, depth_values, None if given else self.pixelwise(), view_weights)
+            depth, conf, prob = select_depth(cost_regularization(similarity), depth_values, prob_volume_init)
+        else:
+            # the view weights from the module itself: differentiable down to its parameters, and in training mode on BatchNorm's batch
+            # statistics (which it then also updates), like the reference
+            similarity, weights = cost_volume_torch(features, proj_matrices, depth_values, None if given else self.pixel_wise_net, view_weights)
+            depth, conf, prob = select_depth_torch(cost_regularization(similarity).squeeze(1), depth_values, prob_volume_init)
+        out = {"depth": depth, "photometric_confidence": conf.detach(), "prob_volume": prob, "depth_values": depth_values}
+        return out if given else (out, weights.detach())
+
+    def hypotheses(self, cur_depth, ndepth, interval, image_hw, stage_scale):
+        """depth_hypotheses behind the same gate as forward()."""
+        if self.uses_kernels([cur_depth]):
+            return depth_hypotheses(cur_depth, ndepth, interval, image_hw, stage_scale)
+        return depth_hypotheses_torch(cur_depth, int(ndepth), float(interval), image_hw, stage_scale)
+
+
+def coarse_to_fine(features, proj_matrices, depth_values, depthnet, cost_regularization, ndepths=(48, 32, 8), ratios=(4, 2, 1),
+                   image_hw=None, depth_interval=None, scales=STAGE_SCALES):
+    """The stage loop of TransMVSNet.forward after feature extraction.
+    features: per view a dict {"stage1": (B,C1,H/4,W/4), "stage2": ..., "stage3": ...}; proj_matrices: {"stage1": (B,NV,2,4,4), ...};
+    depth_values (B,D0): stage 1's hypothesis range; depthnet: a DeviceDepthNet (or the reference's DepthNet); cost_regularization: one
+    callable or one per stage; image_hw: the full image size; depth_interval: the base interval, a host number -- the reference reads it
+    back from depth_values ((max - min) / D0); pass it to keep the loop free of host synchronisation.
+    -> the reference's `outputs` dict: "stage1" .. "stage3" and the last stage's entries at the top level."""
+    if image_hw is None:
+        raise ValueError("diner_amd: coarse_to_fine needs image_hw, the full image size")
+    H, W = (int(v) for v in image_hw)
+    if depth_interval is None:
+        depth_interval = float((depth_values[0, -1] - depth_values[0, 0]).item()) / depth_values.shape[1]
+    outputs, depth, view_weights = {}, None, None
+    B = depth_values.shape[0]
+    for i, (nd, ratio, s) in enumerate(zip(ndepths, ratios, scales)):
+        key = f"stage{i + 1}"
+        feats = [f[key] for f in features]
+        if depth is None:
+            lo, hi = depth_values[:, 0], depth_values[:, -1]
+            step = (hi - lo) / (nd - 1)
+            samples = lo.unsqueeze(1) + torch.arange(0, nd, device=depth_values.device, dtype=depth_values.dtype).reshape(1, -1) * step.unsqueeze(1)
+            hyp = samples.view(B, nd, 1, 1).expand(B, nd, H // s, W // s).contiguous()
+        else:
+            hypotheses = getattr(depthnet, "hypotheses", depth_hypotheses)           # the reference's DepthNet has none
+            hyp = hypotheses(depth.detach(), nd, ratio * depth_interval, (H, W), s)
+        reg = cost_regularization[i] if isinstance(cost_regularization, (list, tuple, nn.ModuleList)) else cost_regularization
+        if view_weights is None:
+            out, view_weights = depthnet(feats, proj_matrices[key], depth_values=hyp, num_depth=nd, cost_regularization=reg, view_weights=None)
+        else:
+            view_weights = F.interpolate(view_weights, scale_factor=2, mode="nearest")
+            out = depthnet(feats, proj_matrices[key], depth_values=hyp, num_depth=nd, cost_regularization=reg, view_weights=view_weights)
+        depth = out["depth"]
+        outputs[key] = out
+        outputs.update(out)
+    return outputs
+
+
+# ---- bridges to the renderer's batches ------------------------------------------------------------------------------------------------
+def proj_matrices_from_cameras(extrinsics, intrinsics, scales=STAGE_SCALES):
+    """A batch's cameras, reference view first -- extrinsics (B,NV,4,4) world -> camera, intrinsics (B,NV,3,3) of the full image -- ->
+    {"stage1": (B,NV,2,4,4), ...}: per view the pair (extrinsics, intrinsics in the top-left 3x3 of a zero 4x4) with the intrinsics' first
+    two rows divided by the stage's scale (datasets/dtu_yao.py:170-200 states the same from the quarter-size camera upwards)."""
+    if extrinsics.dim() != 4 or tuple(extrinsics.shape[2:]) != (4, 4) or tuple(intrinsics.shape) != tuple(extrinsics.shape[:2]) + (3, 3):
+        raise ValueError(f"diner_amd: proj_matrices_from_cameras expects extrinsics (B,NV,4,4) and intrinsics (B,NV,3,3), got "
+                         f"{tuple(extrinsics.shape)}, {tuple(intrinsics.shape)}")
+    B, NV = extrinsics.shape[:2]
+    out = {}
+    for i, s in enumerate(scales):
+        pair = torch.zeros(B, NV, 2, 4, 4, device=extrinsics.device, dtype=torch.float32)
+        pair[:, :, 0] = extrinsics
+        pair[:, :, 1, :3, :3] = intrinsics
+        pair[:, :, 1, :2, :] = pair[:, :, 1, :2, :] / float(s)
+        out[f"stage{i + 1}"] = pair
+    return out
+
+
+def to_source_maps(depth, confidence, law="dtu", dtu_rescale=False):
+    """The estimator's depth and photometric confidence (..,H,W), on any device -> (src_depths, src_depth_stds) as the data sets deliver
+    them after the PNG round trip, minus its 1e-4 quantisation: depth [/ (0.7 / 872) with dtu_rescale], std = formats.conf_to_std."""
+    if law not in formats.CONF_TO_STD:
+        raise ValueError(f"diner_amd: to_source_maps law must be one of {sorted(formats.CONF_TO_STD)}, got {law!r}")
+    depth = depth.to(torch.float32)
+    if dtu_rescale:
+        depth = depth / np.float32(formats.DTU_DEPTH_RESCALE)
+    return depth, formats.conf_to_std(confidence.to(torch.float32), law, depth=depth)

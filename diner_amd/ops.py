@@ -1338,6 +1338,108 @@ def pyramid_level(x, out, c0):
     return out
 
 
+def _check_mvs_limits(B, NS, Cf, D, H, W):
+    """The limits of diner_mvs_cost_volume_f32: refused, never truncated."""
+    if not 1 <= NS <= _lib.MAX_VIEWS - 1:
+        raise ValueError(f"diner_amd: mvs_cost_volume takes 1 .. {_lib.MAX_VIEWS - 1} source views, got {NS}")
+    if Cf % 4 or not 4 <= Cf <= _lib.MVS_MAX_CHANNELS:
+        raise ValueError(f"diner_amd: mvs_cost_volume takes a multiple of 4 channels in [4, {_lib.MVS_MAX_CHANNELS}], got {Cf}")
+    if not 1 <= D <= _lib.MVS_MAX_DEPTHS:
+        raise ValueError(f"diner_amd: mvs_cost_volume takes 1 .. {_lib.MVS_MAX_DEPTHS} depth hypotheses, got {D}")
+    if min(B, H, W) < 1 or B * D * H * W >= 2 ** 31:
+        raise ValueError(f"diner_amd: mvs_cost_volume needs B, H, W >= 1 and B D H W < 2^31, got {B} x {D} x {H} x {W}")
+
+
+def _check_mvs_cost_volume_args(ref_cl, src_cl, proj, depth, pixelwise, view_weights):
+    """The argument checks of mvs_cost_volume that need no device (the limits of diner_mvs_cost_volume_f32) -> (B, NS, C, D, H, W)."""
+    if ref_cl.dim() != 4 or src_cl.dim() != 5 or depth.dim() != 4:
+        raise ValueError(f"diner_amd: mvs_cost_volume expects ref (B,H,W,C), src (NS,B,H,W,C), depth (B,D,H,W), got {tuple(ref_cl.shape)}, "
+                         f"{tuple(src_cl.shape)}, {tuple(depth.shape)}")
+    B, H, W, Cf = (int(v) for v in ref_cl.shape)
+    NS, D = int(src_cl.shape[0]), int(depth.shape[1])
+    if tuple(src_cl.shape[1:]) != (B, H, W, Cf) or tuple(depth.shape) != (B, D, H, W) or tuple(proj.shape) != (B, NS + 1, 2, 4, 4):
+        raise ValueError(f"diner_amd: mvs_cost_volume shapes disagree: ref {tuple(ref_cl.shape)}, src {tuple(src_cl.shape)}, depth "
+                         f"{tuple(depth.shape)}, proj {tuple(proj.shape)}")
+    _check_mvs_limits(B, NS, Cf, D, H, W)
+    if (pixelwise is None) == (view_weights is None):
+        raise ValueError("diner_amd: mvs_cost_volume takes either the folded pixelwise net or the view weights")
+    if pixelwise is not None and pixelwise.numel() != _lib.MVS_PIXELWISE_FLOATS:
+        raise ValueError(f"diner_amd: the folded pixelwise net has {_lib.MVS_PIXELWISE_FLOATS} floats, got {pixelwise.numel()}")
+    if view_weights is not None and tuple(view_weights.shape) != (B, NS, H, W):
+        raise ValueError(f"diner_amd: mvs_cost_volume expects view weights ({B},{NS},{H},{W}), got {tuple(view_weights.shape)}")
+    return B, NS, Cf, D, H, W
+
+
+def mvs_cost_volume(ref_cl, src_cl, proj, depth, pixelwise=None, view_weights=None):
+    """diner_mvs_cost_volume_f32: channels-last features ref (B,H,W,C) and src (NS,B,H,W,C), camera pairs proj (B,NS+1,2,4,4), hypotheses
+    depth (B,D,H,W) and either the folded pixelwise net (177 floats) or view weights (B,NS,H,W) -> (similarity (B,D,H,W), view weights
+    (B,NS,H,W): the computed ones, or the given ones)."""
+    B, NS, Cf, D, H, W = _check_mvs_cost_volume_args(ref_cl, src_cl, proj, depth, pixelwise, view_weights)
+    _require_hip(ref_cl, src_cl, proj, depth, pixelwise, view_weights)
+    ref_cl, src_cl, proj, depth = ref_cl.contiguous(), src_cl.contiguous(), proj.contiguous(), depth.contiguous()
+    dev = ref_cl.device
+    sim = torch.empty(B, D, H, W, device=dev, dtype=torch.float32)
+    hom = torch.empty(B, NS, 12, device=dev, dtype=torch.float32)
+    if pixelwise is not None:
+        pixelwise, vw_in = pixelwise.contiguous(), None
+        vw_out = torch.empty(B, NS, H, W, device=dev, dtype=torch.float32)
+    else:
+        vw_in, vw_out = view_weights.contiguous(), None
+    with torch.cuda.device(dev):
+        _lib.check(lib.diner_mvs_cost_volume_f32(_ptr(ref_cl), _ptr(src_cl), _ptr(proj), _ptr(depth), _ptr(pixelwise), _ptr(vw_in), _ptr(sim),
+                                                 _ptr(vw_out), _ptr(hom), B, NS, Cf, D, H, W, _stream()))
+    return sim, (vw_out if vw_out is not None else view_weights)
+
+
+def mvs_select_depth(cost, hypotheses, prob_init=None, return_prob=True):
+    """diner_mvs_select_depth_f32: cost (B,D,H,W) [+ prob_init], hypotheses (B,D,H,W) -> (depth (B,H,W), confidence (B,H,W), prob volume
+    (B,D,H,W) or None)."""
+    if cost.dim() != 4 or tuple(hypotheses.shape) != tuple(cost.shape) or (prob_init is not None and tuple(prob_init.shape) != tuple(cost.shape)):
+        raise ValueError(f"diner_amd: mvs_select_depth expects cost, hypotheses [and prob_init] of one shape (B,D,H,W), got {tuple(cost.shape)}, "
+                         f"{tuple(hypotheses.shape)}" + ("" if prob_init is None else f", {tuple(prob_init.shape)}"))
+    B, D, H, W = (int(v) for v in cost.shape)
+    if min(B, D, H, W) < 1 or B * D * H * W >= 2 ** 31:
+        raise ValueError(f"diner_amd: mvs_select_depth needs B, D, H, W >= 1 and B D H W < 2^31, got {B} x {D} x {H} x {W}")
+    _require_hip(cost, hypotheses, prob_init)
+    cost, hypotheses = cost.contiguous(), hypotheses.contiguous()
+    prob_init = prob_init.contiguous() if prob_init is not None else None
+    depth = torch.empty(B, H, W, device=cost.device, dtype=torch.float32)
+    conf = torch.empty_like(depth)
+    prob = torch.empty_like(cost) if return_prob else None
+    with torch.cuda.device(cost.device):
+        _lib.check(lib.diner_mvs_select_depth_f32(_ptr(cost), _ptr(prob_init), _ptr(hypotheses), _ptr(depth), _ptr(conf), _ptr(prob), B, D, H, W,
+                                                  _stream()))
+    return depth, conf, prob
+
+
+def _check_mvs_hypotheses_args(cur_depth, ndepth, image_hw, stage_scale):
+    """The argument checks of mvs_hypotheses that need no device -> (B, h, w, H, W, scale, D)."""
+    if cur_depth.dim() != 3:
+        raise ValueError(f"diner_amd: mvs_hypotheses expects the previous stage's depth (B,h,w), got {tuple(cur_depth.shape)}")
+    B, h, w = (int(v) for v in cur_depth.shape)
+    H, W = (int(v) for v in image_hw)
+    s, D = int(stage_scale), int(ndepth)
+    if s != stage_scale or s not in (1, 2, 4):
+        raise ValueError(f"diner_amd: mvs_hypotheses stage scale must be 1, 2 or 4, got {stage_scale}")
+    if not 2 <= D <= _lib.MVS_MAX_DEPTHS:
+        raise ValueError(f"diner_amd: mvs_hypotheses takes 2 .. {_lib.MVS_MAX_DEPTHS} depth hypotheses, got {D}")
+    if min(B, h, w) < 1 or H < s or W < s or B * D * (H // s) * (W // s) >= 2 ** 31:
+        raise ValueError(f"diner_amd: mvs_hypotheses needs B, h, w >= 1, an image of at least {s} x {s} and B D (H / s) (W / s) < 2^31, got "
+                         f"depth {B} x {h} x {w}, image {H} x {W}, D {D}")
+    return B, h, w, H, W, s, D
+
+
+def mvs_hypotheses(cur_depth, ndepth, half_range, image_hw, stage_scale):
+    """diner_mvs_hypotheses_f32: the previous stage's depth (B,h,w) -> this stage's hypotheses (B, ndepth, H // s, W // s)."""
+    B, h, w, H, W, s, D = _check_mvs_hypotheses_args(cur_depth, ndepth, image_hw, stage_scale)
+    _require_hip(cur_depth)
+    cur_depth = cur_depth.contiguous()
+    out = torch.empty(B, D, H // s, W // s, device=cur_depth.device, dtype=torch.float32)
+    with torch.cuda.device(cur_depth.device):
+        _lib.check(lib.diner_mvs_hypotheses_f32(_ptr(cur_depth), _ptr(out), B, h, w, H, W, s, D, float(half_range), _stream()))
+    return out
+
+
 def _check_affine(who, shift, scale):
     out = []
     for name, v in (("shift", shift), ("scale", scale)):

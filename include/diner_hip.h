@@ -893,6 +893,52 @@ int diner_maxpool3s2_f32(const float* x, float* y, int N, int H, int W, int C, i
 int diner_encoder_input_f32(const float* x, const float* ring, float* y, int N, int H, int W, int pad, int Cring, int C, void* stream);
 int diner_pyramid_level_f32(const float* x, float* y, int N, int h, int w, int c, int Hf, int Wf, int Ctot, int c0, void* stream);
 
+/* ---- the depth estimator's matching stage: cost volume, depth read-out, next-stage hypotheses ------------------------------------------
+ * New symbols without an ABI bump (mvs.hip); inference only, no allocation, enqueue-only, no host read-back, everything fp32.  They are
+ * what TransMVSNet's DepthNet.forward and the stage loop of TransMVSNet.forward do between the learned networks (FeatureNet / FMT before,
+ * CostRegNet in the middle, which stay with the caller).  No atomics; the order of every sum is fixed by the shape alone and no workgroup
+ * crosses samples, so a sample's values are the same bits at any place in the batch.  Bad arguments and sizes beyond the limits return
+ * DINER_E_INVALID with a message before any device work; nothing is truncated.
+ *
+ * diner_mvs_cost_volume_f32: the view-weighted feature similarity of a reference view against NS source views over D per-pixel depth
+ *   hypotheses, without the warped (B,C,D,H,W) volume or a sampling grid.
+ *     ref_cl (B,H,W,C), src_cl (NS,B,H,W,C): channels-last feature maps, 16-byte aligned.  proj (B,NS+1,2,4,4): per view the pair
+ *     (extrinsics 4x4, intrinsics in the top-left 3x3 of the second 4x4), view 0 the reference.  depth (B,D,H,W).  Exactly one of
+ *     pixelwise (DINER_MVS_PIXELWISE_FLOATS floats, below) and view_weights_in (B,NS,H,W) is non-NULL.  similarity (B,D,H,W) out [the
+ *     reference's (B,1,D,H,W)]; view_weights_out (B,NS,H,W) out, required with pixelwise, else unused.  homography: B NS 12 floats of
+ *     workspace.
+ *   Per (b, source view v) a prep kernel computes proj = (K_s E_s[:3,:4] ; 0 0 0 1) inverse(K_r E_r[:3,:4] ; 0 0 0 1) in double (3x3
+ *   adjugate) and rounds rot = proj[:3,:3] | trans = proj[:3,3] once to 12 floats.  Per (pixel x,y; depth d):
+ *   p = (rot (x, y, 1)) depth[b,d,y,x] + trans; p.z < 1e-6: the sample is a zero feature; else the source map is sampled at
+ *   (p.x / p.z, p.y / p.z) in pixel units, bilinear, zero padding (a tap outside the map adds 0, the others keep their weights; NaN
+ *   coordinates sample 0).  similarity_v[d] = (sum_c warped[c] ref[c]) / C, each tap's dot product an fmaf chain over c in order, the
+ *   taps combined in the order (x0,y0), (x1,y0), (x0,y1), (x1,y1).  View weight: w_v = max_d sigmoid(net(similarity_v[d])) with net the
+ *   1 -> 16 -> 8 -> 1 pointwise net, BatchNorm folded: pixelwise = w0[16] b0[16] w1[8][16] b1[8] w2[8] b2, h0 = relu(w0 s + b0),
+ *   h1 = relu(w1 h0 + b1), y = w2 h1 + b2, sigmoid = 1 / (1 + exp(-y)) -- a view whose samples all fall outside gets
+ *   max_d sigmoid(net(0)) -- or w_v = view_weights_in[b,v,y,x].  similarity[d] = (sum_v similarity_v[d] w_v) / (1e-5 + sum_v w_v), views
+ *   in order.
+ *   Limits: 1 <= NS <= DINER_MAX_VIEWS - 1, C a multiple of 4 in [4, DINER_MVS_MAX_CHANNELS], 1 <= D <= DINER_MVS_MAX_DEPTHS, any
+ *   B, H, W >= 1 with B D H W < 2^31.
+ * diner_mvs_select_depth_f32: cost (B,D,H,W) [+ prob_init (B,D,H,W) or NULL, added first]; per pixel prob = exp(log_softmax(cost)) along D
+ *   (maximum subtracted, the sum in d order), arg = the first index of the maximum of prob, depth (B,H,W) = hypotheses[b,arg,y,x],
+ *   confidence (B,H,W) = prob[arg]; prob_volume (B,D,H,W) is written when non-NULL.  D >= 1, B D H W < 2^31.
+ * diner_mvs_hypotheses_f32: the next stage's hypotheses (B, D, H / scale, W / scale) from the previous stage's depth cur_depth (B,h,w), equal
+ *   to torch's chain F.interpolate(cur, (H,W), bilinear, align_corners=False) -> lo = up - half_range, hi = up + half_range,
+ *   step = (hi - lo) / (D - 1), sample_d = lo + d step -> F.interpolate(., (D, H / scale, W / scale), trilinear, align_corners=False),
+ *   which is the identity along d and two taps per axis in the plane (the 2 x 2 mean at scale 2; at scale 4 the mean of the window's
+ *   CENTRE 2 x 2, not of all 16 -- torch does not low-pass), in one pass.  half_range = ndepth / 2 * interval.  scale in {1, 2, 4},
+ *   2 <= D <= DINER_MVS_MAX_DEPTHS, integer division of H and W as the reference does. */
+#define DINER_MVS_PIXELWISE_FLOATS 177
+#define DINER_MVS_MAX_DEPTHS 256
+#define DINER_MVS_MAX_CHANNELS 64
+int diner_mvs_cost_volume_f32(const float* ref_cl, const float* src_cl, const float* proj, const float* depth, const float* pixelwise,
+                              const float* view_weights_in, float* similarity, float* view_weights_out, float* homography, int B, int NS, int C,
+                              int D, int H, int W, void* stream);
+int diner_mvs_select_depth_f32(const float* cost, const float* prob_init, const float* hypotheses, float* depth, float* confidence,
+                               float* prob_volume, int B, int D, int H, int W, void* stream);
+int diner_mvs_hypotheses_f32(const float* cur_depth, float* hypotheses, int B, int h, int w, int H, int W, int scale, int D, float half_range,
+                             void* stream);
+
 /* ---- measurement aid (bench.py): per-kernel durations of the two field kernels ------------------
  * With profiling enabled every field call brackets k_field_pre / k_field_post with HIP events on the
  * launch stream; diner_profile_collect waits for them, returns the summed durations (ms), the number

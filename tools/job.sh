@@ -21,6 +21,7 @@
 #   cloud-time [args]          tools/time_cloud.py: grid build, nearest neighbour in input and in own-grid order and the sums on 1 M x 1 M and 7.7 M x 5 M points, one child a size, and scipy's k-d tree on the host (stdout)
 #   optim-time [args]          tools/time_optim.py --loop: DeviceAdam.step against torch.optim.Adam (default and fused=True), alternating windows, and the whole fit step against the loop on torch's optimiser (stdout; keep it as profiles/optim_step_ab.txt)
 #   encoder-time [args]        tools/time_encoder.py: the trunk at 4 x 800x600 and 16 x 400x300 on the torch / MIOpen route and the device route, alternating; peak memory, the first call of each in a fresh process, the device route's launches one by one (stdout)
+#   mvs-time [args]            tools/time_mvs.py: the matching stage's entries and the whole coarse_to_fine at the DTU stage shapes and a 256 x 320 image, kernels against the torch restatement on the device, alternating; peak memory (stdout; keep it as profiles/mvs_time_ab.txt)
 #   smoke                      __graft_entry__.smoke()
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}" || exit 1
 mkdir -p gpurun_out
@@ -95,6 +96,9 @@ PY
   encoder-time)
     set -o pipefail
     timeout -k 10 500 python tools/time_encoder.py "$@" 2>&1 | grep -v amdgpu.ids ;;
+  mvs-time)
+    set -o pipefail
+    timeout -k 10 500 python tools/time_mvs.py "$@" 2>&1 | grep -v amdgpu.ids ;;
   smoke) python __graft_entry__.py smoke ;;
   *) echo "unknown job '$job' (see the header of tools/job.sh)"; exit 2 ;;
 esac
