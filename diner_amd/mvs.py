@@ -1,7 +1,8 @@
 """The matching stage of the multi-view depth estimator on the device: what TransMVSNet's DepthNet.forward (models/TransMVSNet.py:37-106)
 and the stage loop of TransMVSNet.forward do between the learned networks -- homography warping fused with the feature similarity, the
 pixelwise view weights, the weighted aggregation, the winner-take-all read-out of the regularised cost and the next stage's depth
-hypotheses -- on the kernels of csrc/mvs.hip.  FeatureNet, the FMT transformer and CostRegNet stay the caller's torch modules.
+hypotheses -- on the kernels of csrc/mvs.hip, and the cost regulariser between them, the 3-D U-Net CostRegNet (models/module.py:424-455),
+on the kernels of csrc/costreg.hip (DeviceCostRegNet).  FeatureNet and the FMT transformer stay the caller's torch modules.
 
 Every thin function takes the reference's tensor layouts (NCHW).  On HIP tensors it runs the kernels; on CPU tensors it runs a torch
 restatement of the same mathematics with the reference's own operations in the reference's order (`*_torch`, any floating dtype),
@@ -315,6 +316,151 @@ def coarse_to_fine(features, proj_matrices, depth_values, depthnet, cost_regular
         outputs[key] = out
         outputs.update(out)
     return outputs
+
+
+# ---- the drop-in for the reference's CostRegNet ---------------------------------------------------------------------------------------
+# name, kind, Cin and Cout in units of base_channels (conv0's Cin is in_channels), stride -- CostRegNet.__init__ (models/module.py:424-444)
+COSTREG_LAYERS = (("conv0", "conv", 0, 1, 1), ("conv1", "conv", 1, 2, 2), ("conv2", "conv", 2, 2, 1), ("conv3", "conv", 2, 4, 2),
+                  ("conv4", "conv", 4, 4, 1), ("conv5", "conv", 4, 8, 2), ("conv6", "conv", 8, 8, 1), ("conv7", "deconv", 8, 4, 2),
+                  ("conv9", "deconv", 4, 2, 2), ("conv11", "deconv", 2, 1, 2))
+
+
+class _Conv3dBnReLU(nn.Module):
+    """The reference's Conv3d / Deconv3d block (models/module.py:108-191) with BatchNorm and ReLU, under its state-dict keys."""
+
+    def __init__(self, cin, cout, stride=1, transposed=False):
+        super().__init__()
+        if transposed:
+            self.conv = nn.ConvTranspose3d(cin, cout, 3, stride=stride, padding=1, output_padding=1, bias=False)
+        else:
+            self.conv = nn.Conv3d(cin, cout, 3, stride=stride, padding=1, bias=False)
+        self.bn = nn.BatchNorm3d(cout, momentum=0.1)
+
+    def forward(self, x):
+        return F.relu(self.bn(self.conv(x)), inplace=True)
+
+
+def fold_conv_bn(weight, gamma, beta, mean, var, transposed=False):
+    """A bias-free convolution followed by BatchNorm on its running statistics as one convolution with a bias, folded in float64 on the
+    tensors' own device and rounded once: s = gamma / sqrt(var + eps), w' = w s (along Cout: dim 0, or dim 1 of a transposed
+    convolution's weight), b' = beta - mean s -> (w', b') float32."""
+    s = gamma.detach().double() / torch.sqrt(var.detach().double() + BN_EPS)
+    shape = (1, -1, 1, 1, 1) if transposed else (-1, 1, 1, 1, 1)
+    return ((weight.detach().double() * s.view(shape)).to(torch.float32),
+            (beta.detach().double() - mean.detach().double() * s).to(torch.float32))
+
+
+class DeviceCostRegNet(nn.Module):
+    """A replacement for the reference's CostRegNet (models/module.py:424-455): the same state-dict keys (conv0.conv.weight, conv0.bn.*,
+    ... conv11.*, prob.weight), the same forward(): similarity (B,in_channels,D,H,W) -> cost (B,1,D,H,W).  On float32 HIP tensors, in
+    eval mode, with gradients disabled and D, H, W all multiples of 8 (the only sizes at which the reference's skip additions match) it
+    runs the kernels of csrc/costreg.hip: eleven launches, BatchNorm folded into the weights, the skip additions in the epilogues.
+    Otherwise the same torch operations as the reference in its order: differentiable, on batch statistics in training mode, and failing
+    where the reference fails.  The kernel route keeps its intermediate volumes in a per-shape workspace (release_workspace()) and
+    serves one stream at a time.  `mvs.to_device(model)` switches a loaded TransMVSNet over."""
+
+    def __init__(self, in_channels=1, base_channels=8):
+        super().__init__()
+        self.in_channels, self.base_channels = int(in_channels), int(base_channels)
+        for name, kind, ci, co, stride in COSTREG_LAYERS:
+            cin = self.in_channels if ci == 0 else ci * self.base_channels
+            setattr(self, name, _Conv3dBnReLU(cin, co * self.base_channels, stride, kind == "deconv"))
+        self.prob = nn.Conv3d(self.base_channels, 1, 3, stride=1, padding=1, bias=False)
+        self._packed, self._packed_key, self._workspaces = None, None, {}
+
+    @classmethod
+    def from_module(cls, costregnet):
+        sd = costregnet.state_dict()
+        base, cin = sd["conv0.conv.weight"].shape[:2]
+        new = cls(int(cin), int(base))
+        new.to(device=sd["conv0.conv.weight"].device, dtype=sd["conv0.conv.weight"].dtype)     # the source's dtype: nothing is cast down
+        new.load_state_dict(sd)
+        new.train(costregnet.training)
+        return new
+
+    def invalidate(self):
+        """Forget the packed weights: call after writing a parameter or buffer through `.data`, which bumps no version counter."""
+        self._packed_key = None
+
+    def packed(self):
+        """Per layer (name, kind, stride, Cout, packed weight, bias or None, relu) of the current parameters; folded and packed again only
+        after a parameter or buffer changed (no host read-back either way)."""
+        sd = self.state_dict()
+        key = tuple((k, v.data_ptr(), v._version, str(v.device)) for k, v in sd.items())
+        if key != self._packed_key:
+            ops = _ops()
+            layers = []
+            for name, kind, _, co, stride in COSTREG_LAYERS:
+                w, b = fold_conv_bn(sd[name + ".conv.weight"], sd[name + ".bn.weight"], sd[name + ".bn.bias"], sd[name + ".bn.running_mean"],
+                                    sd[name + ".bn.running_var"], kind == "deconv")
+                pack = ops.pack_deconv3d(w) if kind == "deconv" else ops.pack_conv3d(w)
+                layers.append((name, kind, stride, co * self.base_channels, pack, b.contiguous(), True))
+            layers.append(("prob", "conv", 1, 1, ops.pack_conv3d(sd["prob.weight"].detach().to(torch.float32)), None, False))
+            self._packed, self._packed_key = layers, key
+        return self._packed
+
+    def uses_kernels(self, x):
+        """The gate.  Parameters of another dtype than float32 (after .double(), .half()) leave it closed, so that a float32 input then
+        fails in torch's own convolution as it does in the reference."""
+        return (x.is_cuda and x.dtype == torch.float32 and self.prob.weight.dtype == torch.float32 and not self.training
+                and not torch.is_grad_enabled() and x.dim() == 5 and x.shape[1] == self.in_channels
+                and all(int(n) >= 8 and int(n) % 8 == 0 for n in x.shape[2:]))
+
+    def release_workspace(self):
+        """Drop the cached intermediate volumes of every input shape seen so far (they are allocated again on the next forward)."""
+        self._workspaces.clear()
+
+    def _workspace(self, B, D, H, W, device):
+        """The seven intermediate volumes of one input shape, kept between calls -- one set per distinct (B, D, H, W); release_workspace()
+        drops them.  The up path overwrites the skip volumes in place, so a module serves ONE stream at a time: two streams running the
+        same module on the same shape would race on them (give each stream its own module, e.g. copy.deepcopy)."""
+        key = (B, D, H, W, self.base_channels, str(device))
+        ws = self._workspaces.get(key)
+        if ws is None:
+            c = self.base_channels
+            vol = lambda s, m: torch.empty(B, D // s, H // s, W // s, m * c, dtype=torch.float32, device=device)
+            ws = dict(conv0=vol(1, 1), conv1=vol(2, 2), conv2=vol(2, 2), conv3=vol(4, 4), conv4=vol(4, 4), conv5=vol(8, 8), conv6=vol(8, 8))
+            self._workspaces[key] = ws
+        return ws
+
+    def forward_torch(self, x):
+        conv0 = self.conv0(x)
+        conv2 = self.conv2(self.conv1(conv0))
+        conv4 = self.conv4(self.conv3(conv2))
+        x = self.conv6(self.conv5(conv4))
+        x = conv4 + self.conv7(x)
+        x = conv2 + self.conv9(x)
+        x = conv0 + self.conv11(x)
+        return self.prob(x)
+
+    def forward(self, x):
+        if not self.uses_kernels(x):
+            return self.forward_torch(x)
+        ops = _ops()
+        B, Cin, D, H, W = (int(n) for n in x.shape)
+        x = x.detach()
+        cur = x.contiguous().view(B, D, H, W, 1) if Cin == 1 else x.permute(0, 2, 3, 4, 1).contiguous()
+        ws = self._workspace(B, D, H, W, x.device)
+        # the up path writes over the skip tensor it adds: conv7 -> conv4's volume, conv9 -> conv2's, conv11 -> conv0's
+        skip = {"conv7": "conv4", "conv9": "conv2", "conv11": "conv0"}
+        for name, kind, stride, cout, pack, bias, relu in self.packed():
+            if kind == "deconv":
+                cur = ops.deconv3d_s2(cur, pack, bias, cout, relu=relu, addend=ws[skip[name]], out=ws[skip[name]])
+            else:
+                cur = ops.conv3d(cur, pack, bias, cout, stride=stride, relu=relu, out=ws.get(name))      # prob: a new tensor
+        return cur.view(B, 1, D, H, W)
+
+
+def to_device(model):
+    """A loaded TransMVSNet -> the same model with model.DepthNet a DeviceDepthNet and model.cost_regularization a DeviceCostRegNet (one
+    shared module, or a ModuleList of one per stage, as share_cr made it), each carrying the original's state, device and training flag."""
+    model.DepthNet = DeviceDepthNet.from_module(model.DepthNet)
+    cr = model.cost_regularization
+    if isinstance(cr, nn.ModuleList):
+        model.cost_regularization = nn.ModuleList([DeviceCostRegNet.from_module(m) for m in cr])
+    else:
+        model.cost_regularization = DeviceCostRegNet.from_module(cr)
+    return model
 
 
 # ---- bridges to the renderer's batches ------------------------------------------------------------------------------------------------

@@ -1440,6 +1440,110 @@ def mvs_hypotheses(cur_depth, ndepth, half_range, image_hw, stage_scale):
     return out
 
 
+CONV3D_CIN_CHUNK = 8             # DINER_CONV3D_CIN_CHUNK
+CONV3D_COUT_TILE = 16            # DINER_CONV3D_COUT_TILE
+
+
+def conv3d_cout_pad(Cout):
+    """The packed width of diner_conv3d_f32 / diner_deconv3d_s2_f32: one, two or four 16-wide column tiles a workgroup."""
+    Cout = int(Cout)
+    return 16 if Cout <= 16 else 32 if Cout <= 32 else _pad_to(Cout, 64)
+
+
+def _pack3d(who, weight, transposed):
+    if not torch.is_tensor(weight) or weight.dim() != 5 or tuple(weight.shape[2:]) != (3, 3, 3) or weight.shape[0] < 1 or weight.shape[1] < 1:
+        raise ValueError(f"diner_amd: {who} expects a ({'Cin,Cout' if transposed else 'Cout,Cin'},3,3,3) weight, got "
+                         f"{tuple(weight.shape) if torch.is_tensor(weight) else type(weight).__name__}")
+    if weight.dtype != torch.float32:
+        raise ValueError(f"diner_amd: {who} expects float32, got {weight.dtype}")
+    w = weight.detach()
+    if transposed:
+        w = w.transpose(0, 1)                    # the gather reads tap k = o + 1 - 2 i as stored: no flip
+    Cout, Cin = w.shape[:2]
+    cp, op = _pad_to(Cin, CONV3D_CIN_CHUNK), conv3d_cout_pad(Cout)
+    p = w.new_zeros(cp, 27, op)
+    p[:Cin, :, :Cout] = w.reshape(Cout, Cin, 27).permute(1, 2, 0)
+    return p.view(cp // CONV3D_CIN_CHUNK, CONV3D_CIN_CHUNK, 27, op).permute(0, 2, 1, 3).contiguous()
+
+
+def pack_conv3d(weight):
+    """A torch Conv3d weight (Cout,Cin,3,3,3) in the layout diner_conv3d_f32 reads: [ceil(Cin / 8)][tap (kd 3 + kh) 3 + kw][8][CoutPad],
+    zeros beyond Cin and Cout, CoutPad = conv3d_cout_pad(Cout).  Plain torch on the weight's own device, so it needs no HIP device."""
+    return _pack3d("pack_conv3d", weight, False)
+
+
+def pack_deconv3d(weight):
+    """A torch ConvTranspose3d weight (Cin,Cout,3,3,3) in the layout diner_deconv3d_s2_f32 reads: pack_conv3d's, element
+    w[cin][cout][kd][kh][kw] (taps not flipped)."""
+    return _pack3d("pack_deconv3d", weight, True)
+
+
+def _check_ndhwc(who, name, t, shape=None):
+    """A channels-last volume (N,D,H,W,C): float32, 5-D, contiguous -> its shape."""
+    if not torch.is_tensor(t) or t.dim() != 5:
+        raise ValueError(f"diner_amd: {who} expects {name} channels-last (N,D,H,W,C), got "
+                         f"{tuple(t.shape) if torch.is_tensor(t) else type(t).__name__}")
+    if t.dtype != torch.float32:
+        raise ValueError(f"diner_amd: {who} expects {name} float32, got {t.dtype}")
+    if not t.is_contiguous():
+        raise ValueError(f"diner_amd: {who} expects {name} contiguous in (N,D,H,W,C) order, got strides {t.stride()}")
+    if min(t.shape) < 1:
+        raise ValueError(f"diner_amd: {who} expects {name} with every size >= 1, got {tuple(t.shape)}")
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise ValueError(f"diner_amd: {who} expects {name} {tuple(shape)}, got {tuple(t.shape)}")
+    return tuple(int(s) for s in t.shape)
+
+
+def _check_conv3d_args(who, x, wpack, bias, Cout, stride, addend, out):
+    """The argument checks of conv3d (stride 1 | 2) and deconv3d_s2 (stride None) that need no device -> (N, D, H, W, Cin, output shape)."""
+    N, D, H, W, Cin = _check_ndhwc(who, "x", x)
+    Cout = int(Cout)
+    if stride not in (None, 1, 2):
+        raise ValueError(f"diner_amd: {who} stride must be 1 or 2, got {stride}")
+    want = (_pad_to(Cin, CONV3D_CIN_CHUNK) // CONV3D_CIN_CHUNK, 27, CONV3D_CIN_CHUNK, conv3d_cout_pad(max(Cout, 1)))
+    if Cout < 1 or not torch.is_tensor(wpack) or wpack.dtype != torch.float32 or tuple(wpack.shape) != want or not wpack.is_contiguous():
+        raise ValueError(f"diner_amd: {who} expects wpack float32 {want} (pack_{'deconv3d' if stride is None else 'conv3d'}) for Cin {Cin}, "
+                         f"Cout {Cout}, got {tuple(wpack.shape) if torch.is_tensor(wpack) else type(wpack).__name__}")
+    if bias is not None and (not torch.is_tensor(bias) or bias.dtype != torch.float32 or tuple(bias.shape) != (Cout,) or not bias.is_contiguous()):
+        raise ValueError(f"diner_amd: {who} expects bias float32 ({Cout},)")
+    if N > 65535:
+        raise ValueError(f"diner_amd: {who} takes at most 65535 samples a call, got {N}")
+    oshape = (N, 2 * D, 2 * H, 2 * W, Cout) if stride is None else (N,) + tuple((n - 1) // stride + 1 for n in (D, H, W)) + (Cout,)
+    for name, t in (("addend", addend), ("out", out)):
+        if t is not None:
+            _check_ndhwc(who, name, t, oshape)
+    return N, D, H, W, Cin, oshape
+
+
+def conv3d(x, wpack, bias, Cout, stride=1, relu=False, addend=None, out=None):
+    """3 x 3 x 3 convolution, stride 1 or 2, zero padding 1 (diner_conv3d_f32): x (N,D,H,W,Cin) channels-last -> (N,Do,Ho,Wo,Cout) with
+    (n - 1) // stride + 1 voxels per axis, = conv + bias, then ReLU, then + addend, each if given -- the skip tensor is added AFTER the
+    activation, unlike conv3x3.  wpack: pack_conv3d's layout; bias (Cout,) or None.  out: write there instead of a new tensor (it may be
+    the addend, not x)."""
+    N, D, H, W, Cin, oshape = _check_conv3d_args("conv3d", x, wpack, bias, Cout, stride, addend, out)
+    _require_hip(x, wpack, bias, addend, out)
+    dev = x.device
+    with torch.cuda.device(dev):
+        y = out if out is not None else torch.empty(oshape, dtype=torch.float32, device=dev)
+        _lib.check(lib.diner_conv3d_f32(_ptr(x), _ptr(wpack), _ptr(bias), _ptr(addend), _ptr(y), N, D, H, W, Cin, int(Cout), int(stride),
+                                        int(bool(relu)), _stream()))
+    return y
+
+
+def deconv3d_s2(x, wpack, bias, Cout, relu=False, addend=None, out=None):
+    """torch's ConvTranspose3d(3, stride 2, padding 1, output_padding 1) as a gather (diner_deconv3d_s2_f32): x (N,D,H,W,Cin)
+    channels-last -> (N, 2 D, 2 H, 2 W, Cout), = deconv + bias, then ReLU, then + addend, each if given.  wpack: pack_deconv3d's layout;
+    bias (Cout,) or None.  out: write there instead of a new tensor (it may be the addend, not x)."""
+    N, D, H, W, Cin, oshape = _check_conv3d_args("deconv3d_s2", x, wpack, bias, Cout, None, addend, out)
+    _require_hip(x, wpack, bias, addend, out)
+    dev = x.device
+    with torch.cuda.device(dev):
+        y = out if out is not None else torch.empty(oshape, dtype=torch.float32, device=dev)
+        _lib.check(lib.diner_deconv3d_s2_f32(_ptr(x), _ptr(wpack), _ptr(bias), _ptr(addend), _ptr(y), N, D, H, W, Cin, int(Cout),
+                                             int(bool(relu)), _stream()))
+    return y
+
+
 def _check_affine(who, shift, scale):
     out = []
     for name, v in (("shift", shift), ("scale", scale)):

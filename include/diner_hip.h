@@ -939,6 +939,39 @@ int diner_mvs_select_depth_f32(const float* cost, const float* prob_init, const 
 int diner_mvs_hypotheses_f32(const float* cur_depth, float* hypotheses, int B, int h, int w, int H, int W, int scale, int D, float half_range,
                              void* stream);
 
+/* ---- the depth estimator's cost regulariser: the layers of CostRegNet, a 3-D U-Net of 3 x 3 x 3 convolutions ---------------------------
+ * New symbols without an ABI bump (costreg.hip); inference only, no allocation, enqueue-only, one launch each, everything fp32;
+ * activations are channels-last (N,D,H,W,C) on the device -- a one-channel volume (N,1,D,H,W) is that layout already.  No atomics; every
+ * output is a sum of fp32 fmaf chains (v_mfma_f32_16x16x4_f32; plain fmaf in the same order where a stride-1 layer has Cin 1 and Cout <= 16,
+ * or Cout 1 and Cin 4 or 8) whose order the shape alone fixes, and no workgroup crosses samples, so two runs give the same bits and a
+ * sample's values do not depend on its place in the batch.  Bad arguments return DINER_E_INVALID with a message
+ * before any device work.  Non-finite inputs are the caller's error: the result is unspecified, nothing faults.
+ *
+ * diner_conv3d_f32: y = conv(x, w) + bias, 3 x 3 x 3, stride 1 or 2, zero padding 1, any Cin, Cout >= 1, N <= 65535; the output has
+ *   (n - 1) / stride + 1 voxels per axis (odd sizes are legal at stride 2).  Then, IN THIS ORDER, ReLU if relu != 0, then + addend
+ *   (N,Do,Ho,Wo,Cout) if given: the U-Net adds its skip tensors after the activation.  This is NOT diner_conv3x3_f32's order (addend, then
+ *   ReLU).  y may be the addend; it must not overlap x.
+ *   An output is bias + s_0 + s_1 + ..., added in that order, with s_c the sum over chunk c of DINER_CONV3D_CIN_CHUNK input channels: one
+ *   fmaf chain from zero over the 27 taps in (kd, kh, kw) row-major order, inside a tap over the chunk's channels (zeros beyond Cin and
+ *   outside the volume take part: they add +0).  One chain per chunk, not one per output, keeps the rounding error of Cin 64 (1728
+ *   products) near that of Cin 8.
+ *   wpack: diner_conv3d_pack_floats(Cin, Cout) floats, 16-byte aligned, [ceil(Cin / 8)][tap (kd 3 + kh) 3 + kw][8][CoutPad], element =
+ *   w[cout][cin][kd][kh][kw] of a torch Conv3d weight, zeros beyond Cin and Cout; CoutPad = 16 for Cout <= 16, 32 for Cout <= 32, else
+ *   Cout rounded up to 64 (the kernels run one, two or four DINER_CONV3D_COUT_TILE-wide column tiles a workgroup).  bias: Cout floats
+ *   (not padded) or NULL.  diner_conv3d_pack_floats returns 0 for Cin < 1 or Cout < 1.
+ * diner_deconv3d_s2_f32: torch's ConvTranspose3d(3, stride 2, padding 1, output_padding 1): y (N, 2 D, 2 H, 2 W, Cout) from
+ *   x (N,D,H,W,Cin), computed as a gather: per axis output index o receives input i through tap k = o + 1 - 2 i -- an even o from
+ *   (k 1, i o / 2), an odd o from (k 0, i (o + 1) / 2) and (k 2, i (o - 1) / 2), an i beyond the input adding zero.  Same epilogue, same
+ *   sums (per chunk a chain over the taps the output's parity class has in (kd, kh, kw) order, then channel) and the same pack layout, with
+ *   element = w[cin][cout][kd][kh][kw] of the torch ConvTranspose3d weight (no flip). */
+#define DINER_CONV3D_CIN_CHUNK 8
+#define DINER_CONV3D_COUT_TILE 16
+size_t diner_conv3d_pack_floats(int Cin, int Cout);
+int diner_conv3d_f32(const float* x, const float* wpack, const float* bias, const float* addend, float* y, int N, int D, int H, int W, int Cin,
+                     int Cout, int stride, int relu, void* stream);
+int diner_deconv3d_s2_f32(const float* x, const float* wpack, const float* bias, const float* addend, float* y, int N, int D, int H, int W,
+                          int Cin, int Cout, int relu, void* stream);
+
 /* ---- measurement aid (bench.py): per-kernel durations of the two field kernels ------------------
  * With profiling enabled every field call brackets k_field_pre / k_field_post with HIP events on the
  * launch stream; diner_profile_collect waits for them, returns the summed durations (ms), the number
