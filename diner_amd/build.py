@@ -13,7 +13,7 @@ ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(ROOT, "build", "obj")
 LIB = os.path.join(HERE, "libdiner_hip.so")
-SOURCES = ["api.cpp", "sampler.hip", "composite.hip", "stage_ops.hip", "prep.hip", "train.hip", "train_512.hip", "mlp.hip", "mlp_h3n.hip", "generic.hip", "metrics.hip", "objective.hip", "cull.hip", "geometry.hip", "surface.hip", "raycast.hip", "cloud.hip", "perceptual.hip", "optim.hip", "encoder.hip", "mvs.hip", "costreg.hip"]
+SOURCES = ["api.cpp", "sampler.hip", "composite.hip", "stage_ops.hip", "prep.hip", "train.hip", "train_512.hip", "mlp.hip", "mlp_h3n.hip", "generic.hip", "metrics.hip", "objective.hip", "cull.hip", "geometry.hip", "surface.hip", "raycast.hip", "cloud.hip", "conv2d.hip", "perceptual.hip", "optim.hip", "encoder.hip", "mvs.hip", "costreg.hip"]
 # -ffp-contract=off: every fp32 op of the geometry path rounds where the reference's torch ops round;
 # fused multiply-adds are written explicitly (fmaf / MFMA) where they are wanted.
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-Wno-unused-value",
@@ -23,10 +23,11 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fP
 # per-source additions: beside MFMAs packed fp32 VALU instructions (v_pk_add_f32 / v_pk_mul_f32, which -O3's SLP vectoriser forms from
 # adjacent scalar operations) are an anti-lever (MI355X_MICROARCH.md, "price of one filler beside MFMAs")
 EXTRA_FLAGS = {
-    # prints each kernel's registers, scratch, LDS and occupancy at build time: k_conv3x3 must stay free of scratch
+    # prints each kernel's registers, scratch, LDS and occupancy at build time
+    "conv2d.hip": ["-Rpass-analysis=kernel-resource-usage"],    # k_conv2d<3,1 | 1,2 | 3,2 | 7,2> must stay free of scratch
     "perceptual.hip": ["-Rpass-analysis=kernel-resource-usage"],
     "optim.hip": ["-Rpass-analysis=kernel-resource-usage"],     # k_adam and k_grad_stats must stay free of scratch
-    "encoder.hip": ["-Rpass-analysis=kernel-resource-usage"],   # k_conv_s2<1 | 3 | 7> must stay free of scratch
+    "encoder.hip": ["-Rpass-analysis=kernel-resource-usage"],
     "mvs.hip": ["-Rpass-analysis=kernel-resource-usage"],       # k_mvs_cost_volume<1 .. 16> must stay free of scratch
     "costreg.hip": ["-Rpass-analysis=kernel-resource-usage"],   # k_conv3d<1 | 2> and k_deconv3d_s2 must stay free of scratch
 }

@@ -247,19 +247,6 @@ struct CloudTaus {
   float t2[DINER_CLOUD_MAX_THRESHOLDS];
 };
 
-__device__ __forceinline__ double cloud_block_sum(double v, double* red) {   // metrics.hip's fixed-order tree: lanes, then waves 0..3
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  const int wave = threadIdx.x >> 6;
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[wave] = v;
-  __syncthreads();
-  double s = red[0];
-#pragma unroll
-  for (int w = 1; w < kCloudWaves; ++w) s += red[w];
-  return s;
-}
-
 // Thread t of workgroup b takes entries b 256 + t, + gridDim.x 256, ... in that order; slot b of the workspace = the workgroup's sums.
 __global__ void __launch_bounds__(kCloudThreads) k_cloud_reduce(const float* __restrict__ d2, const int* __restrict__ idx, long long n, float cap2,
                                                                 CloudTaus taus, int T, const float* __restrict__ na,
@@ -286,7 +273,7 @@ __global__ void __launch_bounds__(kCloudThreads) k_cloud_reduce(const float* __r
   }
 #pragma unroll
   for (int k = 0; k < kReduceSlot; ++k) {
-    const double s = cloud_block_sum(acc[k], red);
+    const double s = block_sum_d<kCloudWaves>(acc[k], red);
     if (threadIdx.x == 0) ws[(size_t)blockIdx.x * kReduceSlot + k] = s;
   }
 }

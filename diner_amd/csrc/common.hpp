@@ -35,6 +35,13 @@ void set_error(const char* fmt, ...);
     }                                                                                         \
   } while (0)
 
+// a channels-last activation (N,H,W,C) an entry was handed: every size >= 1, at most 2^40 elements
+inline int check_nhwc(const char* who, int N, int H, int W, int C) {
+  DINER_CHECK_ARG(N >= 1 && H >= 1 && W >= 1 && C >= 1, "%s: N, H, W, C = %d, %d, %d, %d (each must be >= 1)", who, N, H, W, C);
+  DINER_CHECK_ARG((long long)N * H * W <= (1LL << 40) / C, "%s: %d x %d x %d x %d elements are more than 2^40", who, N, H, W, C);
+  return 0;
+}
+
 int validate_scene(const DinerScene* s);
 // ResnetFC / positional-encoding configuration the kernels are built for (host-only check, before any device work);
 // poscode = false skips the encoding fields (gradient structs carry none)
@@ -165,6 +172,28 @@ __device__ __forceinline__ int wave_sum_i(int v) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
 }
+__device__ __forceinline__ double wave_sum_d(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+// The sum over a workgroup of WAVES waves in double, in a fixed order: waves_sum_d adds one value a wave (v of the wave's lane 0) in wave
+// order, block_sum_d one value a thread -- the lanes' xor tree, then the waves.  Every thread of the workgroup calls it and gets the sum.
+// red: WAVES doubles of LDS; the leading barrier lets calls follow each other on the same red.
+template <int WAVES>
+__device__ __forceinline__ double waves_sum_d(double v, double* red) {
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  double s = red[0];
+#pragma unroll
+  for (int w = 1; w < WAVES; ++w) s += red[w];
+  return s;
+}
+template <int WAVES>
+__device__ __forceinline__ double block_sum_d(double v, double* red) { return waves_sum_d<WAVES>(wave_sum_d(v), red); }
+
+typedef float v4f __attribute__((ext_vector_type(4)));
 
 // Philox4x32-10 counter-based generator (production noise when no explicit noise tensors are given)
 __device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0,

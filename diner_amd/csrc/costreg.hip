@@ -7,7 +7,7 @@
 //     i = (o - 1) / 2; i = n_in contributes zero).  The eight parity classes of (od, oh, ow) have 1, 2, 2, 2, 4, 4, 4, 8 taps; a workgroup
 //     computes ONE class, so its tap set is uniform and every MFMA is a needed one.  No scatter, no atomics.
 // Both share one body.  Epilogue: ReLU if asked, THEN + addend (the U-Net adds its skip tensors after the activation:
-// x = conv4 + relu(bn(deconv(x)))) -- the other order than k_conv3x3's (perceptual.hip).  The accumulator starts at the bias and takes one sum
+// x = conv4 + relu(bn(deconv(x)))) -- the other order than k_conv2d's (conv2d.hip).  The accumulator starts at the bias and takes one sum
 // per channel chunk, each chunk's sum an fmaf chain from zero (this keeps the rounding error of Cin 64 near that of Cin 8); K order of
 // every output: channel chunk of 8, then kd, kh, kw ascending (the taps a class has, for the transposed layer), then channel -- fixed by
 // the shape alone.  A workgroup never crosses samples (blockIdx.z is the sample), so a sample's bits do not depend on its batch position.
@@ -19,8 +19,6 @@
 
 namespace diner {
 namespace {
-
-typedef float v4f __attribute__((ext_vector_type(4)));
 
 constexpr int kCK = DINER_CONV3D_CIN_CHUNK;       // 8
 constexpr int kNT = DINER_CONV3D_COUT_TILE;       // 16
@@ -37,7 +35,7 @@ enum { kConvS1 = 0, kConvS2 = 1, kDeconv = 2 };
 template <int MODE> struct Tile;
 template <> struct Tile<kConvS1> { static constexpr int TD = 2, TH = 4, S = 1, PD = 4, PH = 6, PW = 18; };
 // stride 2: the patch's columns are stored split by parity (even columns first), so that the 16 voxels of one operand read -- columns
-// 2 lc + kw -- lie 12 words apart like stride 1's and cover the banks once (as k_conv_s2 does, encoder.hip)
+// 2 lc + kw -- lie 12 words apart like stride 1's and cover the banks once (as k_conv2d does at stride 2, conv2d.hip)
 template <> struct Tile<kConvS2> { static constexpr int TD = 2, TH = 2, S = 2, PD = 5, PH = 5, PW = 33; };
 // transposed: a class reads input voxels q and q + 1 per axis, at unit stride; its STORES are what is strided (every other voxel per axis)
 template <> struct Tile<kDeconv> { static constexpr int TD = 2, TH = 4, S = 1, PD = 3, PH = 5, PW = 17; };

@@ -1,191 +1,15 @@
 // The image encoder's trunk on the device (diner_amd/encoder.py): what SpatialEncoder.forward (image_encoder.py of the reference, :225-291)
-// needs beside the stride-1 3 x 3 convolution of perceptual.hip, all fp32, activations channels-last (N,H,W,C):
-//   * k_conv_s2<R>: R x R convolution (R = 1, 3, 7), stride 2, zero padding R / 2, as an implicit GEMM on the fp32-input MFMA
-//     (v_mfma_f32_16x16x4_f32, bit for bit an fmaf chain): pixels x Cout accumulators, K = R R Cin; epilogue + bias (the accumulator
-//     starts there) and an optional ReLU; the output has a channel stride and offset of its own, so the stem writes channels 0 .. 63 of
-//     the latent directly.
+// needs beside the convolutions of conv2d.hip, all fp32, activations channels-last (N,H,W,C):
 //   * k_maxpool3s2: MaxPool2d(3, 2, 1); the input has a channel stride (it reads the stem's output inside the latent).
 //   * k_encoder_input: (N,3,H,W) -> channels-last, replication-padded, with the positional-encoding ring channels and zero channels
 //     behind them (the stem reads 24 channels, not 21: float4 loads).
 //   * k_pyramid_level: bilinear align_corners=True resampling of one pyramid level into its channel slice of the latent.
-// Every output is computed in an order the shape alone fixes; a tile never crosses images (the image is blockIdx.z).
+// Every output is computed in an order the shape alone fixes.
 #include <cmath>
 #include "common.hpp"
 
 namespace diner {
 namespace {
-
-typedef float v4f __attribute__((ext_vector_type(4)));
-
-// ---- the strided convolution -----------------------------------------------------------------------------------------------------------
-// The tiling of k_conv3x3 (perceptual.hip): a workgroup (four waves) computes an 8 x 16 tile of OUTPUT pixels of one image for 64 output
-// channels; one tile row = the 16 rows of one MFMA tile, wave w owns tile rows 2 w, 2 w + 1 (two M tiles) x four N tiles = 32 accumulator
-// registers.  What differs is the staging.  A stage is (chunk of 8 input channels) x (kRS kernel rows): all three rows for R = 3, ONE row
-// for R = 7 and R = 1 -- one chunk of the stem's 7 x 7 x 8 x 64 weights is 100 KB, a kernel row of it 14 KB (17.5 KB with the row
-// padding), and the input rows a kernel row touches are 8 (every second one), not 21.  Per stage the workgroup holds in LDS
-//   * the input patch: kPR rows x kPC columns x 8 channels (12 words a pixel, as in k_conv3x3), zeros outside the image and beyond Cin.
-//     Columns are split by parity into two planes, so that the 16 pixels of an operand read -- input columns 2 j + kx, two apart -- are
-//     neighbours in their plane and the read covers the 64 banks once, as at stride 1;
-//   * the stage's kRS x R x 8 x 64 weights (80 words a row).
-// and runs kRS x R taps x 2 k-steps x 8 MFMAs per wave between two barriers (112 for the stem) while the next stage's loads are in
-// flight in registers.  K order of every output: chunk, kernel row, kernel column, channel.
-constexpr int kTH = 8, kTW = 16;
-constexpr int kBN = DINER_CONV3X3_COUT_TILE;      // 64
-constexpr int kCK = DINER_CONV3X3_CIN_CHUNK;      // 8
-constexpr int kPS = kCK + 4;
-constexpr int kWS = kBN + 16;
-constexpr int kConvThreads = 256;
-
-struct ConvS2Args {
-  const float* x;        // (N,H,W,Cin)
-  const float* w;        // packed [ceil(Cin / 8)][R R][8][CoutPad], zeros beyond Cin and Cout
-  const float* bias;     // Cout floats or null
-  float* y;              // (N,Ho,Wo,ldy), channels coff .. coff + Cout - 1
-  int H, W, Cin, Cout, CoutPad, Ho, Wo, tiles_w, relu, ldy, coff;
-};
-
-template <int R>
-struct ConvS2Shape {
-  static constexpr int kPad = R / 2;
-  static constexpr int kRS = R == 3 ? 3 : 1;                     // kernel rows per stage
-  static constexpr int kStagesPerChunk = R / kRS;
-  static constexpr int kPR = kRS == 1 ? kTH : 2 * (kTH - 1) + kRS;      // patch rows: every second input row, or all of them
-  static constexpr int kPC = R == 1 ? kTW : 2 * (kTW - 1) + R;          // patch columns likewise
-  static constexpr int kNQ = R == 1 ? 1 : 2;                     // column parity planes
-  static constexpr int kPCH = (kPC + kNQ - 1) / kNQ;             // columns per plane
-  static constexpr int kXWords = kPR * kNQ * kPCH * kPS;
-  static constexpr int kWRows = kRS * R * kCK;
-  static constexpr int kWWords = kWRows * kWS;
-  static constexpr int kPV = (kPR * kPC * 2 + kConvThreads - 1) / kConvThreads;        // float4 patch loads per thread
-  static constexpr int kPE = (kPR * kPC * kCK + kConvThreads - 1) / kConvThreads;      // scalar patch loads per thread
-  static constexpr int kWV = (kWRows * (kBN / 4) + kConvThreads - 1) / kConvThreads;   // float4 weight loads per thread
-};
-
-template <int R>
-__global__ __launch_bounds__(kConvThreads) void k_conv_s2(ConvS2Args a) {
-  using S = ConvS2Shape<R>;
-  __shared__ __attribute__((aligned(16))) float Xs[S::kXWords];
-  __shared__ __attribute__((aligned(16))) float Ws[S::kWWords];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int h0 = ((int)blockIdx.x / a.tiles_w) * kTH, w0 = ((int)blockIdx.x % a.tiles_w) * kTW, n0 = (int)blockIdx.y * kBN;
-  const float* x = a.x + (size_t)blockIdx.z * a.H * a.W * a.Cin;       // this image: a tile never leaves it
-  const int lc = lane & 15, lk = lane >> 4;
-  v4f acc[2][4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const int n = n0 + 16 * j + lc;
-    const float b = (a.bias && n < a.Cout) ? a.bias[n] : 0.0f;          // D layout: column lane & 15 in all four registers
-#pragma unroll
-    for (int i = 0; i < 2; ++i) acc[i][j] = (v4f){b, b, b, b};
-  }
-  const bool vec = (a.Cin & 3) == 0 && (reinterpret_cast<uintptr_t>(a.x) & 15) == 0;
-  const int chunks = (a.Cin + kCK - 1) / kCK;
-  const int stages = chunks * S::kStagesPerChunk;
-  v4f xv[S::kPV], wv[S::kWV];
-  float xe[S::kPE];
-  // patch element (row r, column q) of the stage with first kernel row ky0 -> input pixel, or outside
-  auto in_h = [&](int r, int ky0) { return S::kRS == 1 ? 2 * (h0 + r) + ky0 - S::kPad : 2 * h0 + r - S::kPad; };
-  auto in_w = [&](int q) { return R == 1 ? 2 * (w0 + q) : 2 * w0 + q - S::kPad; };
-  auto fetch = [&](int s) {
-    const int c = s / S::kStagesPerChunk, ky0 = (s % S::kStagesPerChunk) * S::kRS, c0 = c * kCK;
-    if (vec) {
-#pragma unroll
-      for (int u = 0; u < S::kPV; ++u) {
-        const int e = tid + kConvThreads * u, p = e >> 1, q4 = e & 1;
-        const int h = in_h(p / S::kPC, ky0), w = in_w(p % S::kPC);
-        xv[u] = (v4f){0.f, 0.f, 0.f, 0.f};
-        if (e < S::kPR * S::kPC * 2 && h >= 0 && h < a.H && w >= 0 && w < a.W && c0 + 4 * q4 < a.Cin)
-          xv[u] = *reinterpret_cast<const v4f*>(x + ((size_t)h * a.W + w) * a.Cin + c0 + 4 * q4);
-      }
-    } else {
-#pragma unroll
-      for (int u = 0; u < S::kPE; ++u) {
-        const int e = tid + kConvThreads * u, p = e >> 3, k = e & 7;
-        const int h = in_h(p / S::kPC, ky0), w = in_w(p % S::kPC);
-        xe[u] = 0.0f;
-        if (e < S::kPR * S::kPC * kCK && h >= 0 && h < a.H && w >= 0 && w < a.W && c0 + k < a.Cin) xe[u] = x[((size_t)h * a.W + w) * a.Cin + c0 + k];
-      }
-    }
-    const float* wsrc = a.w + ((size_t)c * R * R + (size_t)ky0 * R) * kCK * a.CoutPad + n0;
-#pragma unroll
-    for (int u = 0; u < S::kWV; ++u) {
-      const int e = tid + kConvThreads * u, r = e >> 4, q = e & 15;
-      if (e < S::kWRows * (kBN / 4)) wv[u] = *reinterpret_cast<const v4f*>(wsrc + (size_t)r * a.CoutPad + 4 * q);
-    }
-  };
-  // LDS word of patch pixel p = row * kPC + column: the column's parity picks the plane
-  auto xs_at = [&](int p) {
-    const int r = p / S::kPC, q = p % S::kPC;
-    return ((r * S::kNQ + (S::kNQ == 2 ? (q & 1) : 0)) * S::kPCH + (S::kNQ == 2 ? (q >> 1) : q)) * kPS;
-  };
-  auto stash = [&]() {
-    if (vec) {
-#pragma unroll
-      for (int u = 0; u < S::kPV; ++u) {
-        const int e = tid + kConvThreads * u;
-        if (e < S::kPR * S::kPC * 2) *reinterpret_cast<v4f*>(&Xs[xs_at(e >> 1) + 4 * (e & 1)]) = xv[u];
-      }
-    } else {
-#pragma unroll
-      for (int u = 0; u < S::kPE; ++u) {
-        const int e = tid + kConvThreads * u;
-        if (e < S::kPR * S::kPC * kCK) Xs[xs_at(e >> 3) + (e & 7)] = xe[u];
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < S::kWV; ++u) {
-      const int e = tid + kConvThreads * u;
-      if (e < S::kWRows * (kBN / 4)) *reinterpret_cast<v4f*>(&Ws[(e >> 4) * kWS + 4 * (e & 15)]) = wv[u];
-    }
-  };
-  fetch(0);
-  for (int s = 0; s < stages; ++s) {
-    stash();
-    __syncthreads();
-    if (s + 1 < stages) fetch(s + 1);
-#pragma unroll
-    for (int t = 0; t < S::kRS * R; ++t) {
-      const int kyl = t / R, kx = t % R;                 // kernel row within the stage, kernel column
-      const int plane = S::kNQ == 2 ? (kx & 1) : 0, col = S::kNQ == 2 ? (kx >> 1) : 0;
-#pragma unroll
-      for (int kk = 0; kk < kCK; kk += 4) {
-        float av[2], bv[4];
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-          const int row = S::kRS == 1 ? 2 * wave + i : 2 * (2 * wave + i) + kyl;
-          av[i] = Xs[((row * S::kNQ + plane) * S::kPCH + lc + col) * kPS + kk + lk];
-        }
-#pragma unroll
-        for (int j = 0; j < 4; ++j) bv[j] = Ws[(t * kCK + kk + lk) * kWS + 16 * j + lc];
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-          for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[i], bv[j], acc[i][j], 0, 0, 0);
-      }
-    }
-    __syncthreads();
-  }
-  // D layout: lane holds rows (pixels of the tile row) 4 (lane >> 4) .. + 3 of column (output channel) lane & 15
-  float* y = a.y + (size_t)blockIdx.z * a.Ho * a.Wo * a.ldy + a.coff;
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const int h = h0 + 2 * wave + i;
-    if (h >= a.Ho) continue;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int n = n0 + 16 * j + lc;
-      if (n >= a.Cout) continue;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int w = w0 + 4 * lk + r;
-        if (w >= a.Wo) continue;
-        float v = acc[i][j][r];
-        if (a.relu) v = fmaxf(v, 0.0f);
-        y[((size_t)h * a.Wo + w) * a.ldy + n] = v;
-      }
-    }
-  }
-}
 
 // ---- element-wise kernels: one thread per output element -------------------------------------------------------------------------------
 constexpr int kThreads = 256;
@@ -292,59 +116,10 @@ __global__ __launch_bounds__(kThreads) void k_pyramid_level(const float* x, floa
 inline unsigned blocks_for(long long total) { return (unsigned)((total + kThreads - 1) / kThreads); }
 constexpr long long kMaxElems = (1LL << 31) * (long long)kThreads - 1;      // one thread per element, grid.x < 2^31
 
-int check_nhwc(const char* who, int N, int H, int W, int C) {
-  DINER_CHECK_ARG(N >= 1 && H >= 1 && W >= 1 && C >= 1, "%s: N, H, W, C = %d, %d, %d, %d (each must be >= 1)", who, N, H, W, C);
-  DINER_CHECK_ARG((long long)N * H * W <= (1LL << 40) / C, "%s: %d x %d x %d x %d elements are more than 2^40", who, N, H, W, C);
-  return 0;
-}
-
-template <int R>
-void launch_conv_s2(const ConvS2Args& a, dim3 grid, hipStream_t stream) {
-  hipLaunchKernelGGL(k_conv_s2<R>, grid, dim3(kConvThreads), 0, stream, a);
-}
-
 }  // namespace
 }  // namespace diner
 
 using namespace diner;
-
-extern "C" size_t diner_conv2d_s2_pack_floats(int Cin, int Cout, int R) {
-  if (Cin < 1 || Cout < 1 || (R != 1 && R != 3 && R != 7)) return 0;
-  return (size_t)((Cin + kCK - 1) / kCK) * R * R * kCK * (size_t)((Cout + kBN - 1) / kBN * kBN);
-}
-
-extern "C" int diner_conv2d_s2_f32(const float* x, const float* wpack, const float* bias, float* y, int N, int H, int W, int Cin, int Cout, int R,
-                                   int relu, int ldy, int coff, void* stream) {
-  int rc = check_nhwc("conv2d_s2", N, H, W, Cin);
-  if (rc) return rc;
-  if (R != 1 && R != 3 && R != 7) {
-    set_error("conv2d_s2: R = %d (the kernel sizes built are 1, 3 and 7)", R);
-    return DINER_E_UNSUPPORTED;
-  }
-  DINER_CHECK_ARG(Cout >= 1, "conv2d_s2: N, H, W, C = %d, %d, %d, %d (each must be >= 1)", N, H, W, Cout);
-  DINER_CHECK_ARG(N <= 65535, "conv2d_s2: N = %d images (at most 65535 a call)", N);
-  DINER_CHECK_ARG(coff >= 0 && ldy >= 1 && Cout <= ldy - coff, "conv2d_s2: channels %d .. %d do not fit an output of %d channels", coff,
-                  coff + Cout - 1, ldy);
-  const int pad = R / 2;
-  const int Ho = (H + 2 * pad - R) / 2 + 1, Wo = (W + 2 * pad - R) / 2 + 1;
-  rc = check_nhwc("conv2d_s2", N, Ho, Wo, ldy);
-  if (rc) return rc;
-  DINER_CHECK_ARG(x && wpack && y, "conv2d_s2: null pointer argument");
-  DINER_CHECK_ARG((reinterpret_cast<uintptr_t>(wpack) & 15) == 0, "conv2d_s2: the packed weights are not 16-byte aligned");
-  ConvS2Args a;
-  a.x = x; a.w = wpack; a.bias = bias; a.y = y;
-  a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.CoutPad = (Cout + kBN - 1) / kBN * kBN;
-  a.Ho = Ho; a.Wo = Wo; a.tiles_w = (Wo + kTW - 1) / kTW;
-  a.relu = relu != 0; a.ldy = ldy; a.coff = coff;
-  const long long tiles = (long long)a.tiles_w * ((Ho + kTH - 1) / kTH);
-  DINER_CHECK_ARG(tiles < (1LL << 31) && a.CoutPad / kBN <= 65535, "conv2d_s2: %d x %d pixels x %d channels are too many tiles", Ho, Wo, Cout);
-  const dim3 grid((unsigned)tiles, (unsigned)(a.CoutPad / kBN), (unsigned)N);
-  if (R == 1) launch_conv_s2<1>(a, grid, (hipStream_t)stream);
-  else if (R == 3) launch_conv_s2<3>(a, grid, (hipStream_t)stream);
-  else launch_conv_s2<7>(a, grid, (hipStream_t)stream);
-  DINER_LAUNCH_OK();
-  return 0;
-}
 
 extern "C" int diner_maxpool3s2_f32(const float* x, float* y, int N, int H, int W, int C, int ldx, void* stream) {
   const int rc = check_nhwc("maxpool3s2", N, H, W, C);

@@ -30,19 +30,6 @@ constexpr U8Table make_u8_table() {              // constant-folded, correctly r
 }
 __constant__ U8Table kU8Table = make_u8_table();
 
-__device__ __forceinline__ double block_sum(double v, double* red) {   // fixed-order tree: lanes, then waves 0..3
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  const int wave = threadIdx.x >> 6;
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[wave] = v;
-  __syncthreads();
-  double s = red[0];
-#pragma unroll
-  for (int w = 1; w < kMetThreads / 64; ++w) s += red[w];
-  return s;
-}
-
 // Input routes: byte at (image n, channel ch, row r, column c) of the pair.
 struct SrcU8 {
   const unsigned char* pred;
@@ -147,9 +134,9 @@ __global__ void __launch_bounds__(kMetThreads) k_metrics_partial(Src src, int H,
     __syncthreads();
   }
 
-  l1 = block_sum(l1, red);
-  l2 = block_sum(l2, red);
-  ss = block_sum(ss, red);
+  l1 = block_sum_d<kMetThreads / 64>(l1, red);
+  l2 = block_sum_d<kMetThreads / 64>(l2, red);
+  ss = block_sum_d<kMetThreads / 64>(ss, red);
   if (t == 0) {
     const int n_slots = gridDim.x;
     double* o = ws + (((size_t)n * 3 + ch) * n_slots + blockIdx.x) * kMetSlot;

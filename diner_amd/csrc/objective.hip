@@ -19,17 +19,6 @@ constexpr int kObjChunk = 3 * kObjThreads;       // values per workgroup without
 constexpr int kPatchThreads = 1024;
 constexpr uint32_t kPatchStream = 3u;            // Philox stream of the patch centre (0..2: the sampler's noise fields)
 
-__device__ __forceinline__ double block_sum(double v, double* red, int n_waves) {   // fixed-order tree: lanes, then the waves in order
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double s = red[0];
-  for (int w = 1; w < n_waves; ++w) s += red[w];
-  return s;
-}
-
 // ---- the patch of the step -----------------------------------------------------------------------------------------------------
 // One workgroup per object.  Thread t owns the contiguous pixels [t chunk, (t + 1) chunk) of the row-major image; the weight of a pixel
 // in the first / last `pad` rows and columns counts as 0, as does a weight that is not > 0.  Pass 1: the thread's sum (double, in pixel
@@ -168,8 +157,8 @@ __global__ void __launch_bounds__(kObjThreads) k_objective(ObjArgs a, double* __
     }
     d_pred[(size_t)o * a.B * 3 + gv] = (float)g;
   }
-  mse = block_sum(mse, red, kObjThreads / 64);
-  ab = block_sum(ab, red, kObjThreads / 64);
+  mse = block_sum_d<kObjThreads / 64>(mse, red);
+  ab = block_sum_d<kObjThreads / 64>(ab, red);
   if (t == 0) {
     double* slot = ws + ((size_t)o * a.n_bands + band) * 2;
     slot[0] = mse;

@@ -38,17 +38,6 @@ struct AdamArgs {
 
 __device__ __forceinline__ bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 
-__device__ __forceinline__ double block_sum(double v, double* red) {       // fixed order: the lanes' xor tree, then the waves in order
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double s = red[0];
-  for (int w = 1; w < kOptWaves; ++w) s += red[w];
-  return s;
-}
-
 __device__ __forceinline__ void stat_elem(float g, double& s, long long& bad) {
   s += (double)g * (double)g;                     // a non-finite g makes the norm non-finite, as torch's clip_grad_norm_ reports it
   bad += (__builtin_isfinite(g) ? 0 : 1);
@@ -76,8 +65,8 @@ __global__ void __launch_bounds__(kOptThreads) k_grad_stats(const DinerOptimChun
   } else {
     for (int i = t; i < ch.numel; i += kOptThreads) stat_elem(g[i], s, bad);
   }
-  s = block_sum(s, red);
-  const double b = block_sum((double)bad, red);   // <= DINER_OPTIM_CHUNK: exact
+  s = block_sum_d<kOptWaves>(s, red);
+  const double b = block_sum_d<kOptWaves>((double)bad, red);   // <= DINER_OPTIM_CHUNK: exact
   if (t == 0) {
     part[blockIdx.x].sumsq = s;
     part[blockIdx.x].nonfinite = (long long)b;
@@ -91,8 +80,8 @@ __global__ void __launch_bounds__(kOptThreads) k_grad_stats_final(const Partial*
     s += part[k].sumsq;
     b += (double)part[k].nonfinite;
   }
-  s = block_sum(s, red);
-  b = block_sum(b, red);
+  s = block_sum_d<kOptWaves>(s, red);
+  b = block_sum_d<kOptWaves>(b, red);
   if (threadIdx.x == 0) {
     st->grad_norm_sq = s;
     st->nonfinite = (long long)b;

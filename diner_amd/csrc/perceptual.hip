@@ -1,10 +1,7 @@
 // The perceptual network on the device (diner_amd/perceptual.py): the VGG convolution stack behind the reference's two perceptual
 // quantities -- the LPIPS score of evaluate_folder (eval_suite.py:52,75-77) and the VGG loss of every shipped training config
-// (vggloss.py:59-69) -- as five building blocks, all fp32, activations channels-last (N,H,W,C):
-//   * k_conv3x3: 3 x 3 convolution, stride 1, zero padding 1, as an implicit GEMM on the fp32-input MFMA (v_mfma_f32_16x16x4_f32, bit
-//     for bit an fmaf chain): pixels x Cout accumulators, K = 9 Cin.  With the second packed weight set (taps flipped, Cin and Cout
-//     swapped) the same kernel is the data gradient; its epilogue then adds the loss gradient that enters at a tap layer and applies the
-//     ReLU mask of the saved activation.  The weights are frozen: there is no weight gradient.
+// (vggloss.py:59-69) -- as the 3 x 3 convolution of conv2d.hip and four more building blocks, all fp32, activations channels-last
+// (N,H,W,C):
 //   * k_maxpool2 / k_maxpool2_bwd: MaxPool2d(2, 2), odd sizes floored; the gradient goes to the first maximum of a window in row-major
 //     order (torch's CPU max_pool2d), recomputed from the saved input.
 //   * k_image_in / k_image_in_bwd: (N,3,H,W) -> channels-last with a per-channel affine, and its adjoint.
@@ -16,150 +13,6 @@
 
 namespace diner {
 namespace {
-
-typedef float v4f __attribute__((ext_vector_type(4)));
-
-// ---- the convolution -------------------------------------------------------------------------------------------------------------------
-// A workgroup (four waves) computes an 8 x 16 pixel tile of one image for 64 output channels.  One tile row = 16 pixels = the 16 rows of
-// one MFMA tile, so wave w owns rows 2 w, 2 w + 1 (two M tiles) x four N tiles: 32 accumulator registers.  Per chunk of 8 input channels
-// the workgroup stages the 10 x 18 pixel patch (tile + one-pixel halo, zeros outside the image and beyond Cin) and the chunk's
-// 9 x 8 x 64 weights in LDS, then runs 9 taps x 2 k-steps x 8 MFMAs per wave between two barriers, the next chunk's loads in flight
-// meanwhile.  K order of every output: chunk, tap, channel -- the same whatever the tile or the image's place in the batch.
-constexpr int kTH = 8, kTW = 16;
-constexpr int kBN = DINER_CONV3X3_COUT_TILE;      // 64
-constexpr int kCK = DINER_CONV3X3_CIN_CHUNK;      // 8
-constexpr int kPS = kCK + 4;        // LDS words per patch pixel: 12 p + k (16 pixels x 4 k of one operand read) covers the 64 banks once
-constexpr int kPH = kTH + 2, kPW = kTW + 2;
-constexpr int kWS = kBN + 16;       // LDS words per weight row: the four k rows of one operand read start 16 banks apart
-constexpr int kConvThreads = 256;
-
-struct ConvArgs {
-  const float* x;        // (N,H,W,Cin)
-  const float* w;        // packed [ceil(Cin / 8)][9][8][CoutPad], zeros beyond Cin and Cout
-  const float* bias;     // CoutPad or null
-  const float* addend;   // (N,H,W,Cout) or null: added before the mask
-  const float* mask;     // (N,H,W,Cout) or null: the output is zero where !(mask > 0)
-  float* y;              // (N,H,W,Cout)
-  int H, W, Cin, Cout, CoutPad, tiles_w, relu;
-};
-
-__global__ __launch_bounds__(kConvThreads) void k_conv3x3(ConvArgs a) {
-  __shared__ __attribute__((aligned(16))) float Xs[kPH * kPW * kPS];
-  __shared__ __attribute__((aligned(16))) float Ws[9 * kCK * kWS];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int h0 = ((int)blockIdx.x / a.tiles_w) * kTH, w0 = ((int)blockIdx.x % a.tiles_w) * kTW, n0 = (int)blockIdx.y * kBN;
-  const size_t img = (size_t)blockIdx.z * a.H * a.W;       // first pixel of this image: a tile never leaves it
-  const float* x = a.x + img * a.Cin;
-  const int lc = lane & 15, lk = lane >> 4;
-  v4f acc[2][4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const float b = a.bias ? a.bias[n0 + 16 * j + lc] : 0.0f;          // D layout: column lane & 15 in all four registers
-#pragma unroll
-    for (int i = 0; i < 2; ++i) acc[i][j] = (v4f){b, b, b, b};
-  }
-  const bool vec = (a.Cin & 3) == 0 && (reinterpret_cast<uintptr_t>(a.x) & 15) == 0;
-  const int chunks = (a.Cin + kCK - 1) / kCK;
-  // Chunk c + 1 travels from global memory into registers while chunk c's MFMAs run, and moves into LDS behind the barrier that ends them:
-  // a small image gives each CU one workgroup, and nothing else would hide the loads.
-  constexpr int kPV = (kPH * kPW * 2 + kConvThreads - 1) / kConvThreads;        // float4 patch loads per thread (vector path): 2
-  constexpr int kPE = (kPH * kPW * kCK + kConvThreads - 1) / kConvThreads;      // scalar patch loads per thread: 6
-  constexpr int kWV = (9 * kCK * (kBN / 4) + kConvThreads - 1) / kConvThreads;  // float4 weight loads per thread: 5
-  v4f xv[kPV], wv[kWV];
-  float xe[kPE];
-  auto fetch = [&](int c) {
-    const int c0 = c * kCK;
-    if (vec) {
-#pragma unroll
-      for (int u = 0; u < kPV; ++u) {
-        const int e = tid + kConvThreads * u, p = e >> 1, q = e & 1;
-        const int h = h0 + p / kPW - 1, w = w0 + p % kPW - 1;
-        xv[u] = (v4f){0.f, 0.f, 0.f, 0.f};
-        if (e < kPH * kPW * 2 && h >= 0 && h < a.H && w >= 0 && w < a.W && c0 + 4 * q < a.Cin)
-          xv[u] = *reinterpret_cast<const v4f*>(x + ((size_t)h * a.W + w) * a.Cin + c0 + 4 * q);
-      }
-    } else {
-#pragma unroll
-      for (int u = 0; u < kPE; ++u) {
-        const int e = tid + kConvThreads * u, p = e >> 3, k = e & 7;
-        const int h = h0 + p / kPW - 1, w = w0 + p % kPW - 1;
-        xe[u] = 0.0f;
-        if (e < kPH * kPW * kCK && h >= 0 && h < a.H && w >= 0 && w < a.W && c0 + k < a.Cin) xe[u] = x[((size_t)h * a.W + w) * a.Cin + c0 + k];
-      }
-    }
-    const float* wsrc = a.w + (size_t)c * 9 * kCK * a.CoutPad + n0;
-#pragma unroll
-    for (int u = 0; u < kWV; ++u) {
-      const int e = tid + kConvThreads * u, r = e >> 4, q = e & 15;
-      if (e < 9 * kCK * (kBN / 4)) wv[u] = *reinterpret_cast<const v4f*>(wsrc + (size_t)r * a.CoutPad + 4 * q);
-    }
-  };
-  auto stash = [&]() {
-    if (vec) {
-#pragma unroll
-      for (int u = 0; u < kPV; ++u) {
-        const int e = tid + kConvThreads * u;
-        if (e < kPH * kPW * 2) *reinterpret_cast<v4f*>(&Xs[(e >> 1) * kPS + 4 * (e & 1)]) = xv[u];
-      }
-    } else {
-#pragma unroll
-      for (int u = 0; u < kPE; ++u) {
-        const int e = tid + kConvThreads * u;
-        if (e < kPH * kPW * kCK) Xs[(e >> 3) * kPS + (e & 7)] = xe[u];
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < kWV; ++u) {
-      const int e = tid + kConvThreads * u;
-      if (e < 9 * kCK * (kBN / 4)) *reinterpret_cast<v4f*>(&Ws[(e >> 4) * kWS + 4 * (e & 15)]) = wv[u];
-    }
-  };
-  fetch(0);
-  for (int c = 0; c < chunks; ++c) {
-    stash();
-    __syncthreads();
-    if (c + 1 < chunks) fetch(c + 1);
-#pragma unroll
-    for (int t = 0; t < 9; ++t) {
-      const int ky = t / 3, kx = t % 3;
-#pragma unroll
-      for (int kk = 0; kk < kCK; kk += 4) {
-        float av[2], bv[4];
-#pragma unroll
-        for (int i = 0; i < 2; ++i) av[i] = Xs[((2 * wave + i + ky) * kPW + lc + kx) * kPS + kk + lk];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) bv[j] = Ws[(t * kCK + kk + lk) * kWS + 16 * j + lc];
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-          for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[i], bv[j], acc[i][j], 0, 0, 0);
-      }
-    }
-    __syncthreads();
-  }
-  // D layout: lane holds rows (pixels of the tile row) 4 (lane >> 4) .. + 3 of column (output channel) lane & 15
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const int h = h0 + 2 * wave + i;
-    if (h >= a.H) continue;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int n = n0 + 16 * j + lc;
-      if (n >= a.Cout) continue;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int w = w0 + 4 * lk + r;
-        if (w >= a.W) continue;
-        const size_t at = (img + (size_t)h * a.W + w) * a.Cout + n;
-        float v = acc[i][j][r];
-        if (a.addend) v += a.addend[at];
-        if (a.relu) v = fmaxf(v, 0.0f);
-        if (a.mask && !(a.mask[at] > 0.0f)) v = 0.0f;
-        a.y[at] = v;
-      }
-    }
-  }
-}
 
 // ---- 2 x 2 max-pool --------------------------------------------------------------------------------------------------------------------
 constexpr int kThreads = 256;
@@ -239,20 +92,6 @@ __global__ __launch_bounds__(kThreads) void k_image_in_bwd(const float* g, float
 // ---- reductions in double, fixed order -------------------------------------------------------------------------------------------------
 constexpr int kMaxBlocks = 1024;
 
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-// the workgroup's sum: per wave, then the four waves in order; valid in thread 0
-__device__ __forceinline__ double block_sum_d(double v, double* sh) {
-  v = wave_sum_d(v);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return ((sh[0] + sh[1]) + sh[2]) + sh[3];
-}
-
 int l1_blocks(long long n) {
   const long long b = (n + kThreads - 1) / kThreads;
   return (int)(b < kMaxBlocks ? b : kMaxBlocks);
@@ -272,7 +111,7 @@ __global__ __launch_bounds__(kThreads) void k_feature_l1(const float* fx, const 
       grad[i] = g;
     }
   }
-  s = block_sum_d(s, sh);
+  s = block_sum_d<kThreads / 64>(s, sh);
   if (threadIdx.x == 0) partial[blockIdx.x] = s;
 }
 
@@ -318,50 +157,17 @@ __global__ __launch_bounds__(kThreads) void k_lpips_layer(const float* fx, const
     }
     total += wave_sum_d(s);
   }
-  if (lane == 0) sh[wave] = total;
-  __syncthreads();
-  if (threadIdx.x == 0) partial[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = ((sh[0] + sh[1]) + sh[2]) + sh[3];
+  total = waves_sum_d<kThreads / 64>(total, sh);
+  if (threadIdx.x == 0) partial[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = total;
 }
 
 inline unsigned blocks_for(long long total) { return (unsigned)((total + kThreads - 1) / kThreads); }
 constexpr long long kMaxElems = (1LL << 31) * (long long)kThreads - 1;      // one thread per element, grid.x < 2^31
 
-int check_nhwc(const char* who, int N, int H, int W, int C) {
-  DINER_CHECK_ARG(N >= 1 && H >= 1 && W >= 1 && C >= 1, "%s: N, H, W, C = %d, %d, %d, %d (each must be >= 1)", who, N, H, W, C);
-  DINER_CHECK_ARG((long long)N * H * W <= (1LL << 40) / C, "%s: %d x %d x %d x %d elements are more than 2^40", who, N, H, W, C);
-  return 0;
-}
-
 }  // namespace
 }  // namespace diner
 
 using namespace diner;
-
-extern "C" size_t diner_conv3x3_pack_floats(int Cin, int Cout) {
-  if (Cin < 1 || Cout < 1) return 0;
-  return (size_t)((Cin + kCK - 1) / kCK) * 9 * kCK * (size_t)((Cout + kBN - 1) / kBN * kBN);
-}
-
-extern "C" int diner_conv3x3_f32(const float* x, const float* wpack, const float* bias, const float* addend, const float* mask, float* y, int N,
-                                 int H, int W, int Cin, int Cout, int relu, void* stream) {
-  int rc = check_nhwc("conv3x3", N, H, W, Cin);
-  if (rc) return rc;
-  rc = check_nhwc("conv3x3", N, H, W, Cout);
-  if (rc) return rc;
-  DINER_CHECK_ARG(N <= 65535, "conv3x3: N = %d images (at most 65535 a call)", N);
-  DINER_CHECK_ARG(x && wpack && y, "conv3x3: null pointer argument");
-  DINER_CHECK_ARG((reinterpret_cast<uintptr_t>(wpack) & 15) == 0, "conv3x3: the packed weights are not 16-byte aligned");
-  ConvArgs a;
-  a.x = x; a.w = wpack; a.bias = bias; a.addend = addend; a.mask = mask; a.y = y;
-  a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.CoutPad = (Cout + kBN - 1) / kBN * kBN;
-  a.tiles_w = (W + kTW - 1) / kTW;
-  a.relu = relu != 0;
-  const long long tiles = (long long)a.tiles_w * ((H + kTH - 1) / kTH);
-  DINER_CHECK_ARG(tiles < (1LL << 31) && a.CoutPad / kBN <= 65535, "conv3x3: %d x %d pixels x %d channels are too many tiles", H, W, Cout);
-  hipLaunchKernelGGL(k_conv3x3, dim3((unsigned)tiles, (unsigned)(a.CoutPad / kBN), (unsigned)N), dim3(kConvThreads), 0, (hipStream_t)stream, a);
-  DINER_LAUNCH_OK();
-  return 0;
-}
 
 extern "C" int diner_maxpool2_f32(const float* x, float* y, int N, int H, int W, int C, void* stream) {
   const int rc = check_nhwc("maxpool2", N, H, W, C);

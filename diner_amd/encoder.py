@@ -1,5 +1,5 @@
 """The image encoder's trunk on the device: SpatialEncoder.forward's ResNet feature pyramid (image_encoder.py:225-291 of the reference)
-in this library's own kernels (csrc/encoder.hip + the stride-1 convolution of csrc/perceptual.hip), for inference.
+in this library's own kernels (csrc/encoder.hip + the convolutions of csrc/conv2d.hip), for inference.
 
     trunk = DeviceTrunk(nerf.encoder)                      # or a state dict with torchvision's key names (`model.*`)
     latent = trunk(images)                                 # (SB,NV,3,H,W) normalised, on the HIP device -> (SB,NV,L,Hf,Wf)

@@ -1085,31 +1085,43 @@ def cloud_reduce(d2, idx, max_dist=float("inf"), thresholds=(), normals_a=None, 
     return out
 
 
+# ---- the 2-D convolution (conv2d.hip): conv3x3 (stride 1) and conv_s2 (stride 2) ----------------------------------------------------------
 CONV3X3_CIN_CHUNK = 8            # DINER_CONV3X3_CIN_CHUNK
 CONV3X3_COUT_TILE = 64           # DINER_CONV3X3_COUT_TILE
+CONV_S2_KERNELS = (1, 3, 7)      # the kernel sizes diner_conv2d_s2_f32 is built for
 
 
 def _pad_to(n, m):
     return -(-int(n) // m) * m
 
 
+def _pack_conv2d(who, weight, kernels, Cin=None, transpose=False):
+    """A torch Conv2d weight (Cout,Cw,R,R), R in `kernels`, as [ceil(Cin / 8)][ky R + kx][8][Cout rounded up to 64], zeros beyond Cw and
+    Cout; transpose: taps flipped, Cin and Cout swapped first."""
+    if not torch.is_tensor(weight) or weight.dim() != 4 or weight.shape[2] != weight.shape[3] or weight.shape[2] not in kernels \
+            or weight.shape[0] < 1 or weight.shape[1] < 1:
+        want = "(Cout,Cin,3,3) weight" if kernels == (3,) else f"(Cout,Cin,R,R) weight with R in {kernels}"
+        raise ValueError(f"diner_amd: {who} expects a {want}, got {tuple(weight.shape) if torch.is_tensor(weight) else type(weight).__name__}")
+    if weight.dtype != torch.float32:
+        raise ValueError(f"diner_amd: {who} expects float32, got {weight.dtype}")
+    w = weight.detach()
+    if transpose:
+        w = w.flip(2, 3).transpose(0, 1)
+    Cout, Cw, R = int(w.shape[0]), int(w.shape[1]), int(w.shape[2])
+    Cin = Cw if Cin is None else int(Cin)
+    if Cin < Cw:
+        raise ValueError(f"diner_amd: {who}: Cin = {Cin} is less than the weight's {Cw} input channels")
+    cp, op = _pad_to(Cin, CONV3X3_CIN_CHUNK), _pad_to(Cout, CONV3X3_COUT_TILE)
+    p = w.new_zeros(cp, R * R, op)
+    p[:Cw, :, :Cout] = w.reshape(Cout, Cw, R * R).permute(1, 2, 0)
+    return p.view(cp // CONV3X3_CIN_CHUNK, CONV3X3_CIN_CHUNK, R * R, op).permute(0, 2, 1, 3).contiguous()
+
+
 def pack_conv3x3(weight, transpose=False):
     """A torch Conv2d weight (Cout,Cin,3,3) in the layout diner_conv3x3_f32 reads: [ceil(Cin / 8)][tap][8][Cout rounded up to 64], zeros
     beyond Cin and Cout.  transpose: the weight set of the data gradient instead (taps flipped, Cin and Cout swapped).  Plain torch on
     the weight's own device (done once at load), so it needs no HIP device."""
-    if not torch.is_tensor(weight) or weight.dim() != 4 or tuple(weight.shape[2:]) != (3, 3) or weight.shape[0] < 1 or weight.shape[1] < 1:
-        raise ValueError(f"diner_amd: pack_conv3x3 expects a (Cout,Cin,3,3) weight, got "
-                         f"{tuple(weight.shape) if torch.is_tensor(weight) else type(weight).__name__}")
-    if weight.dtype != torch.float32:
-        raise ValueError(f"diner_amd: pack_conv3x3 expects float32, got {weight.dtype}")
-    w = weight.detach()
-    if transpose:
-        w = w.flip(2, 3).transpose(0, 1)
-    Cout, Cin = w.shape[:2]
-    cp, op = _pad_to(Cin, CONV3X3_CIN_CHUNK), _pad_to(Cout, CONV3X3_COUT_TILE)
-    p = w.new_zeros(cp, 9, op)
-    p[:Cin, :, :Cout] = w.reshape(Cout, Cin, 9).permute(1, 2, 0)
-    return p.view(cp // CONV3X3_CIN_CHUNK, CONV3X3_CIN_CHUNK, 9, op).permute(0, 2, 1, 3).contiguous()
+    return _pack_conv2d("pack_conv3x3", weight, (3,), transpose=transpose)
 
 
 def _check_nhwc(who, name, t, shape=None, min_hw=1):
@@ -1128,19 +1140,32 @@ def _check_nhwc(who, name, t, shape=None, min_hw=1):
     return tuple(int(s) for s in t.shape)
 
 
+def _check_conv2d_args(who, x, wpack, bias, Cout, R, kernels, padded_bias):
+    """What conv3x3 and conv_s2 check alike: x, the kernel size, the packed weights for (Cin, Cout, R), the bias (of the packed width, or
+    of at least Cout elements) and the image count -> (N, H, W, Cin)."""
+    N, H, W, Cin = _check_nhwc(who, "x", x)
+    if R not in kernels:
+        raise NotImplementedError(f"diner_amd: {who} is built for kernel sizes {kernels}, got {R}")
+    want = (_pad_to(Cin, CONV3X3_CIN_CHUNK) // CONV3X3_CIN_CHUNK, R * R, CONV3X3_CIN_CHUNK, _pad_to(max(Cout, 1), CONV3X3_COUT_TILE))
+    if Cout < 1 or not torch.is_tensor(wpack) or wpack.dtype != torch.float32 or tuple(wpack.shape) != want or not wpack.is_contiguous():
+        raise ValueError(f"diner_amd: {who} expects wpack float32 {want} (pack_{who}) for Cin {Cin}, Cout {Cout}"
+                         f"{'' if who == 'conv3x3' else f', R {R}'}, got {tuple(wpack.shape) if torch.is_tensor(wpack) else type(wpack).__name__}")
+    if bias is not None:
+        ok = torch.is_tensor(bias) and bias.dtype == torch.float32 and bias.dim() == 1 and bias.is_contiguous()
+        if padded_bias:
+            if not (ok and bias.shape[0] == want[3]):
+                raise ValueError(f"diner_amd: {who} expects bias float32 ({want[3]},) (zero-padded to the packed width)")
+        elif not (ok and bias.shape[0] >= Cout):
+            raise ValueError(f"diner_amd: {who} expects bias float32 with at least Cout = {Cout} elements")
+    if N > 65535:
+        raise ValueError(f"diner_amd: {who} takes at most 65535 images a call, got {N}")
+    return N, H, W, Cin
+
+
 def _check_conv3x3_args(x, wpack, bias, Cout, addend, mask):
     """The argument checks of conv3x3 that need no device -> (N, H, W, Cin)."""
-    N, H, W, Cin = _check_nhwc("conv3x3", "x", x)
     Cout = int(Cout)
-    want = (_pad_to(Cin, CONV3X3_CIN_CHUNK) // CONV3X3_CIN_CHUNK, 9, CONV3X3_CIN_CHUNK, _pad_to(max(Cout, 1), CONV3X3_COUT_TILE))
-    if Cout < 1 or not torch.is_tensor(wpack) or wpack.dtype != torch.float32 or tuple(wpack.shape) != want or not wpack.is_contiguous():
-        raise ValueError(f"diner_amd: conv3x3 expects wpack float32 {want} (pack_conv3x3) for Cin {Cin}, Cout {Cout}, got "
-                         f"{tuple(wpack.shape) if torch.is_tensor(wpack) else type(wpack).__name__}")
-    if bias is not None and (not torch.is_tensor(bias) or bias.dtype != torch.float32 or tuple(bias.shape) != (want[3],)
-                             or not bias.is_contiguous()):
-        raise ValueError(f"diner_amd: conv3x3 expects bias float32 ({want[3]},) (zero-padded to the packed width)")
-    if N > 65535:
-        raise ValueError(f"diner_amd: conv3x3 takes at most 65535 images a call, got {N}")
+    N, H, W, Cin = _check_conv2d_args("conv3x3", x, wpack, bias, Cout, 3, (3,), True)
     for name, t in (("addend", addend), ("mask", mask)):
         if t is not None:
             _check_nhwc("conv3x3", name, t, (N, H, W, Cout))
@@ -1189,28 +1214,11 @@ def maxpool2_bwd(x, gy, addend=None, relu_mask=False):
 
 
 # ---- the image encoder's trunk (encoder.hip) ---------------------------------------------------------------------------------------------
-CONV_S2_KERNELS = (1, 3, 7)      # the kernel sizes diner_conv2d_s2_f32 is built for
-
-
 def pack_conv_s2(weight, Cin=None):
     """A torch Conv2d weight (Cout,Cin,R,R), R in {1, 3, 7}, in the layout diner_conv2d_s2_f32 reads: [ceil(Cin / 8)][ky R + kx][8][Cout
     rounded up to 64], zeros beyond Cin and Cout.  Cin: pack for that many input channels (>= the weight's; the added ones are zero), for
     an input that encoder_input widened.  Plain torch on the weight's own device (done once at load), so it needs no HIP device."""
-    if not torch.is_tensor(weight) or weight.dim() != 4 or weight.shape[2] != weight.shape[3] or weight.shape[2] not in CONV_S2_KERNELS \
-            or weight.shape[0] < 1 or weight.shape[1] < 1:
-        raise ValueError(f"diner_amd: pack_conv_s2 expects a (Cout,Cin,R,R) weight with R in {CONV_S2_KERNELS}, got "
-                         f"{tuple(weight.shape) if torch.is_tensor(weight) else type(weight).__name__}")
-    if weight.dtype != torch.float32:
-        raise ValueError(f"diner_amd: pack_conv_s2 expects float32, got {weight.dtype}")
-    w = weight.detach()
-    Cout, Cw, R = int(w.shape[0]), int(w.shape[1]), int(w.shape[2])
-    Cin = Cw if Cin is None else int(Cin)
-    if Cin < Cw:
-        raise ValueError(f"diner_amd: pack_conv_s2: Cin = {Cin} is less than the weight's {Cw} input channels")
-    cp, op = _pad_to(Cin, CONV3X3_CIN_CHUNK), _pad_to(Cout, CONV3X3_COUT_TILE)
-    p = w.new_zeros(cp, R * R, op)
-    p[:Cw, :, :Cout] = w.reshape(Cout, Cw, R * R).permute(1, 2, 0)
-    return p.view(cp // CONV3X3_CIN_CHUNK, CONV3X3_CIN_CHUNK, R * R, op).permute(0, 2, 1, 3).contiguous()
+    return _pack_conv2d("pack_conv_s2", weight, CONV_S2_KERNELS, Cin=Cin)
 
 
 def conv_s2_out_size(n, R):
@@ -1220,19 +1228,8 @@ def conv_s2_out_size(n, R):
 
 def _check_conv_s2_args(x, wpack, bias, Cout, R, out, coff):
     """The argument checks of conv_s2 that need no device -> (N, H, W, Cin, Ho, Wo, ldy)."""
-    N, H, W, Cin = _check_nhwc("conv_s2", "x", x)
     Cout, R, coff = int(Cout), int(R), int(coff)
-    if R not in CONV_S2_KERNELS:
-        raise NotImplementedError(f"diner_amd: conv_s2 is built for kernel sizes {CONV_S2_KERNELS}, got {R}")
-    want = (_pad_to(Cin, CONV3X3_CIN_CHUNK) // CONV3X3_CIN_CHUNK, R * R, CONV3X3_CIN_CHUNK, _pad_to(max(Cout, 1), CONV3X3_COUT_TILE))
-    if Cout < 1 or not torch.is_tensor(wpack) or wpack.dtype != torch.float32 or tuple(wpack.shape) != want or not wpack.is_contiguous():
-        raise ValueError(f"diner_amd: conv_s2 expects wpack float32 {want} (pack_conv_s2) for Cin {Cin}, Cout {Cout}, R {R}, got "
-                         f"{tuple(wpack.shape) if torch.is_tensor(wpack) else type(wpack).__name__}")
-    if bias is not None and (not torch.is_tensor(bias) or bias.dtype != torch.float32 or bias.dim() != 1 or bias.shape[0] < Cout
-                             or not bias.is_contiguous()):
-        raise ValueError(f"diner_amd: conv_s2 expects bias float32 with at least Cout = {Cout} elements")
-    if N > 65535:
-        raise ValueError(f"diner_amd: conv_s2 takes at most 65535 images a call, got {N}")
+    N, H, W, Cin = _check_conv2d_args("conv_s2", x, wpack, bias, Cout, R, CONV_S2_KERNELS, False)
     Ho, Wo = conv_s2_out_size(H, R), conv_s2_out_size(W, R)
     ldy = Cout
     if out is not None:

@@ -1,4 +1,4 @@
-"""The perceptual network on the device: the VGG convolution stack (csrc/perceptual.hip) behind the reference's LPIPS score
+"""The perceptual network on the device: the VGG convolution stack (csrc/conv2d.hip, csrc/perceptual.hip) behind the reference's LPIPS score
 (eval_suite.py:52,75-77, lpips.LPIPS(net="vgg")) and its VGG loss (vggloss.py:59-69).
 
     lp = Lpips(lpips.LPIPS(net="vgg").state_dict())            # evaluate_folder(lpips_fn=lp), or --lpips_weights FILE

@@ -1,4 +1,4 @@
-"""GPU: the image encoder's trunk on the device (csrc/encoder.hip, diner_amd.encoder) against torch on the CPU in float64, computed at run
+"""GPU: the image encoder's trunk on the device (csrc/conv2d.hip, csrc/encoder.hip, diner_amd.encoder) against torch on the CPU in float64, computed at run
 time.
 
 The strided convolution's bound is a priori, the one tests/test_perceptual_gpu.py uses: every output is one sequential fp32 fmaf chain over
@@ -91,6 +91,29 @@ def test_conv_s2_writes_its_channel_slice_only():
     assert bool((err <= c["bound"]).all())
     dense = ops.conv_s2(nhwc(c["x"]).cuda(), ops.pack_conv_s2(c["w"]).cuda(), c["b"].cuda(), Cout, R, relu=True)
     assert torch.equal(dense.cpu(), o[..., 64:128])
+
+
+@pytest.mark.parametrize("relu", (False, True))
+@pytest.mark.parametrize("Cin", (12, 3))              # float4 patch loads with a ragged last chunk; element-wise loads
+@pytest.mark.parametrize("size", ((11, 19), (17, 35)))
+def test_conv_s2_3x3_is_conv3x3_subsampled_bit_for_bit(size, Cin, relu):
+    """Both start at the bias and add the same products in the same K order (chunk, kernel row, kernel column, channel), and the zero
+    padding adds exact zeros: the stride-2 output is every second pixel of the stride-1 output.  One kernel template behind both; this
+    pins the parity-plane patch addressing of stride 2 against the plain one.  Odd sizes, tails in both tilings (8 x 16), two images,
+    two Cout tiles with the last one ragged."""
+    from diner_amd import ops
+    (H, W), N, Cout = size, 2, 70
+    g = torch.Generator().manual_seed(3000 + Cin + H)
+    w = torch.randn(Cout, Cin, 3, 3, generator=g) * (2.0 / (9 * Cin)) ** 0.5
+    b = torch.zeros(128)
+    b[:Cout] = torch.randn(Cout, generator=g) * 0.1
+    x = torch.randn(N, H, W, Cin, generator=g).cuda()
+    wp, b = ops.pack_conv3x3(w).cuda(), b.cuda()
+    full = ops.conv3x3(x, wp, b, Cout, relu=relu)
+    half = ops.conv_s2(x, wp, b, Cout, 3, relu=relu)
+    assert tuple(half.shape) == (N, (H + 1) // 2, (W + 1) // 2, Cout)
+    assert torch.equal(half, full[:, ::2, ::2])
+    assert float(half.abs().max()) > 0.1 and (not relu or float((half == 0).float().mean()) > 0.2)
 
 
 @pytest.mark.parametrize("size", ((1, 1), (2, 3), (7, 8), (23, 29)))
