@@ -2,7 +2,8 @@
 and the stage loop of TransMVSNet.forward do between the learned networks -- homography warping fused with the feature similarity, the
 pixelwise view weights, the weighted aggregation, the winner-take-all read-out of the regularised cost and the next stage's depth
 hypotheses -- on the kernels of csrc/mvs.hip, and the cost regulariser between them, the 3-D U-Net CostRegNet (models/module.py:424-455),
-on the kernels of csrc/costreg.hip (DeviceCostRegNet).  FeatureNet and the FMT transformer stay the caller's torch modules.
+on the kernels of csrc/costreg.hip (DeviceCostRegNet), and the feature transformer in front of the loop, FMT_with_pathway (models/FMT.py),
+on the kernels of csrc/fmt.hip (DeviceFMT, DeviceFMTWithPathway).  FeatureNet stays the caller's torch module.
 
 Every thin function takes the reference's tensor layouts (NCHW).  On HIP tensors it runs the kernels; on CPU tensors it runs a torch
 restatement of the same mathematics with the reference's own operations in the reference's order (`*_torch`, any floating dtype),
@@ -451,15 +452,287 @@ class DeviceCostRegNet(nn.Module):
         return cur.view(B, 1, D, H, W)
 
 
+# ---- the drop-ins for the reference's FMT and FMT_with_pathway ------------------------------------------------------------------------
+FMT_LAYER_NAMES = ("self", "cross") * 4
+FMT_PE_SHAPE = (600, 600)
+
+
+def sine_position_encoding(d_model=32, max_shape=FMT_PE_SHAPE):
+    """The 2-D sinusoidal encoding PositionEncodingSine (models/position_encoding.py, temp_bug_fix=True) registers as its buffer, built
+    with the same float32 torch operations so that it has the same bits -> (d_model, *max_shape).  Channel 4 i + (0, 1, 2, 3) is
+    (sin x f_i, cos x f_i, sin y f_i, cos y f_i) with x, y counted from 1 and f_i = exp(-2 i ln(10000) / (d_model / 2))."""
+    pe = torch.zeros((d_model, *max_shape))
+    ys = torch.ones(max_shape).cumsum(0).float().unsqueeze(0)
+    xs = torch.ones(max_shape).cumsum(1).float().unsqueeze(0)
+    freq = torch.exp(torch.arange(0, d_model // 2, 2).float() * (-np.log(10000.0) / (d_model // 2)))[:, None, None]
+    pe[0::4], pe[1::4] = torch.sin(xs * freq), torch.cos(xs * freq)
+    pe[2::4], pe[3::4] = torch.sin(ys * freq), torch.cos(ys * freq)
+    return pe
+
+
+class _AttentionLayer(nn.Module):
+    """The reference's AttentionLayer around LinearAttention (models/FMT.py:16-75) under its state-dict keys."""
+
+    def __init__(self, d_model, n_heads):
+        super().__init__()
+        self.query_projection, self.key_projection = nn.Linear(d_model, d_model), nn.Linear(d_model, d_model)
+        self.value_projection, self.out_projection = nn.Linear(d_model, d_model), nn.Linear(d_model, d_model)
+        self.n_heads = n_heads
+
+    def forward(self, queries, keys, values):
+        N, L, _ = queries.shape
+        S, H = keys.shape[1], self.n_heads
+        Q = F.elu(self.query_projection(queries).view(N, L, H, -1)) + 1
+        K = F.elu(self.key_projection(keys).view(N, S, H, -1)) + 1
+        values = self.value_projection(values).view(N, S, H, -1)
+        KV = torch.einsum("nshd,nshm->nhmd", K, values)
+        Z = 1 / (torch.einsum("nlhd,nhd->nlh", Q, K.sum(dim=1)) + 1e-6)
+        V = torch.einsum("nlhd,nhmd,nlh->nlhm", Q, KV, Z)
+        return self.out_projection(V.contiguous().view(N, L, -1))
+
+
+class _EncoderLayer(nn.Module):
+    """The reference's EncoderLayer (models/FMT.py:78-111; its dropout has probability 0)."""
+
+    def __init__(self, d_model, n_heads):
+        super().__init__()
+        self.attention = _AttentionLayer(d_model, n_heads)
+        self.linear1, self.linear2 = nn.Linear(d_model, 2 * d_model), nn.Linear(2 * d_model, d_model)
+        self.norm1, self.norm2 = nn.LayerNorm(d_model), nn.LayerNorm(d_model)
+
+    def forward(self, x, source):
+        x = self.norm1(x + self.attention(x, source, source))
+        return self.norm2(x + self.linear2(F.relu(self.linear1(x))))
+
+
+def _tokens(x):
+    return x.permute(0, 2, 3, 1).reshape(x.shape[0], -1, x.shape[1])
+
+
+def _maps(tokens, H):
+    N, L, C = tokens.shape
+    return tokens.reshape(N, H, L // H, C).permute(0, 3, 1, 2)
+
+
+class DeviceFMT(nn.Module):
+    """A replacement for the reference's FMT (models/FMT.py:114-174): the same state-dict keys (layers.{i}.attention.*_projection.*,
+    linear1/2, norm1/2; the positional encoding `pe` is a non-persistent buffer), the same forward(ref_feature, src_feature, feat).
+    encode(ref, sources) is the device route: the reference view's tokens through the four self layers and all source views as ONE batch
+    through the eight layers on the kernels of csrc/fmt.hip, a cross layer's attention state computed once per batch element from the
+    reference view.  forward() itself always runs the reference's torch operations in the reference's order."""
+
+    def __init__(self, config=None):
+        super().__init__()
+        config = config or {"d_model": 32, "nhead": 8, "layer_names": list(FMT_LAYER_NAMES)}
+        self.d_model, self.nhead, self.layer_names = int(config["d_model"]), int(config["nhead"]), list(config["layer_names"])
+        self.layers = nn.ModuleList([_EncoderLayer(self.d_model, self.nhead) for _ in self.layer_names])
+        for p in self.parameters():
+            if p.dim() > 1:
+                nn.init.xavier_uniform_(p)
+        self.register_buffer("pe", sine_position_encoding(self.d_model).unsqueeze(0), persistent=False)
+        self._packed, self._packed_key = None, None
+
+    @classmethod
+    def from_module(cls, fmt):
+        new = cls({"d_model": fmt.d_model, "nhead": fmt.nhead, "layer_names": list(fmt.layer_names)})
+        p = next(fmt.parameters())
+        new.to(device=p.device, dtype=p.dtype)
+        new.load_state_dict(fmt.state_dict())
+        new.train(fmt.training)
+        return new
+
+    def invalidate(self):
+        """Forget the packed weights: call after writing a parameter through `.data`, which bumps no version counter."""
+        self._packed_key = None
+
+    def packed(self):
+        """One ops.pack_fmt_layer per layer of the current parameters; packed again only after a parameter changed."""
+        sd = self.state_dict()
+        key = tuple((k, v.data_ptr(), v._version, str(v.device)) for k, v in sd.items())
+        if key != self._packed_key:
+            ops = _ops()
+            self._packed, self._packed_key = [ops.pack_fmt_layer(sd, f"layers.{i}.") for i in range(len(self.layers))], key
+        return self._packed
+
+    def uses_kernels(self, x):
+        """The gate: a float32 HIP map (B,32,H,W) with H, W <= 600, float32 parameters, eval mode, gradients disabled, and the
+        reference's layer schedule at d_model 32 with 8 heads."""
+        return (x.is_cuda and x.dtype == torch.float32 and self.layers[0].linear1.weight.dtype == torch.float32 and not self.training
+                and not torch.is_grad_enabled() and tuple(self.layer_names) == FMT_LAYER_NAMES and self.d_model == 32 and self.nhead == 8
+                and x.dim() == 4 and x.shape[1] == 32 and 1 <= x.shape[2] <= FMT_PE_SHAPE[0] and 1 <= x.shape[3] <= FMT_PE_SHAPE[1])
+
+    def pos_encoding(self, x):
+        return x + self.pe[:, :, :x.size(2), :x.size(3)]
+
+    def forward(self, ref_feature=None, src_feature=None, feat="ref"):
+        assert ref_feature is not None
+        if feat == "ref":
+            assert self.d_model == ref_feature.size(1)
+            H = ref_feature.shape[2]
+            x = _tokens(self.pos_encoding(ref_feature))
+            out = []
+            for layer, name in zip(self.layers, self.layer_names):
+                if name == "self":
+                    x = layer(x, x)
+                    out.append(_maps(x, H))
+            return out
+        if feat == "src":
+            assert self.d_model == ref_feature[0].size(1)
+            H = ref_feature[0].shape[2]
+            refs = [_tokens(r) for r in ref_feature]
+            x = _tokens(self.pos_encoding(src_feature))
+            for i, (layer, name) in enumerate(zip(self.layers, self.layer_names)):
+                if name == "self":
+                    x = layer(x, x)
+                elif name == "cross":
+                    x = layer(x, refs[i // 2])
+                else:
+                    raise KeyError
+            return _maps(x, H)
+        raise ValueError("Wrong feature name")
+
+    def encode_tokens(self, maps):
+        """maps (NV,B,32,H,W) contiguous float32 on the device, view 0 the reference -> tokens (NV,B,H W,32): the reference view after its
+        four self layers, every source view after all eight.  Everything on the current stream, no host synchronisation."""
+        ops = _ops()
+        NV, B, _, H, W = (int(n) for n in maps.shape)
+        L = H * W
+        packs = self.packed()
+        tok = ops.fmt_tokenise(maps.view(NV * B, 32, H, W), self.pe[0]).view(NV, B, L, 32)
+        ref, src = tok[0], tok[1:].reshape((NV - 1) * B, L, 32) if NV > 1 else None
+        partials = torch.empty(max(NV - 1, 1) * B * ops.fmt_kv_blocks(L) * ops.FMT_STATE_FLOATS, dtype=torch.float64, device=maps.device)
+        cross = []
+        for j in range(4):
+            ops.fmt_layer(ref, packs[2 * j], ops.fmt_kv(ref, packs[2 * j], partials), out=ref)
+            if src is not None:
+                cross.append(ops.fmt_kv(ref, packs[2 * j + 1], partials))         # reference output j feeds cross layer 2 j + 1
+        if src is not None:
+            for j in range(4):
+                ops.fmt_layer(src, packs[2 * j], ops.fmt_kv(src, packs[2 * j], partials), out=src)
+                ops.fmt_layer(src, packs[2 * j + 1], cross[j], out=src)          # image n = view B + b reads row n mod B
+        return tok
+
+    def encode(self, ref, sources):
+        """The device route of one sample batch: ref (B,32,H,W), sources a list of (B,32,H,W) -> (ref', [source', ...]), each (B,32,H,W)
+        as a permuted view of channels-last memory.  Outside the gate: forward() per view, as the reference's FMT_with_pathway calls it."""
+        views = [ref] + list(sources)
+        if self.uses_kernels(ref) and all(v.shape == ref.shape and v.is_cuda and v.dtype == torch.float32 for v in views):
+            B, _, H, W = ref.shape
+            tok = self.encode_tokens(torch.stack([v.detach() for v in views], 0))
+            out = [tok[v].view(B, H, W, 32).permute(0, 3, 1, 2) for v in range(len(views))]
+            return out[0], out[1:]
+        refs = self.forward(ref.clone(), feat="ref")
+        return refs[-1], [self.forward([r.clone() for r in refs], s.clone(), feat="src") for s in sources]
+
+
+class DeviceFMTWithPathway(nn.Module):
+    """A replacement for the reference's FMT_with_pathway (models/FMT.py:178-225): the same 132 state-dict keys (FMT.layers.*,
+    dim_reduction_{1,2}.weight, smooth_{1,2}.weight), the same forward(features): it rewrites "stage1" / "stage2" / "stage3" of each
+    view's dict in place and returns the list.  The kernel route (csrc/fmt.hip, and diner_conv3x3_f32 for the smooth convolutions) needs
+    float32 HIP tensors and parameters, eval mode, gradients disabled, layer_names ['self','cross'] * 4, every view of one shape,
+    stage 2 and stage 3 exactly 2 x and 4 x stage 1 with 16 and 8 channels, and H, W <= 600; all views then run as one batch.  Its results
+    have the reference's shapes (B,C,H,W) but are PERMUTED VIEWS OF CHANNELS-LAST MEMORY (call .contiguous() where NCHW strides matter).
+    Outside the gate it runs the reference's torch operations in the reference's order: differentiable, and failing where the reference
+    fails.  `mvs.to_device(model)` switches a loaded TransMVSNet over."""
+
+    def __init__(self, base_channels=8, FMT_config=None):
+        super().__init__()
+        c = int(base_channels)
+        self.base_channels = c
+        self.FMT = DeviceFMT(FMT_config)
+        self.dim_reduction_1 = nn.Conv2d(c * 4, c * 2, 1, bias=False)
+        self.dim_reduction_2 = nn.Conv2d(c * 2, c * 1, 1, bias=False)
+        self.smooth_1 = nn.Conv2d(c * 2, c * 2, 3, padding=1, bias=False)
+        self.smooth_2 = nn.Conv2d(c * 1, c * 1, 3, padding=1, bias=False)
+        self._packed, self._packed_key = None, None
+
+    @classmethod
+    def from_module(cls, module):
+        fmt = module.FMT
+        new = cls(int(module.dim_reduction_2.weight.shape[0]), {"d_model": fmt.d_model, "nhead": fmt.nhead, "layer_names": list(fmt.layer_names)})
+        p = module.dim_reduction_1.weight
+        new.to(device=p.device, dtype=p.dtype)
+        new.load_state_dict(module.state_dict())
+        new.train(module.training)
+        return new
+
+    def invalidate(self):
+        """Forget the packed weights of the pathway and of the FMT: call after writing a parameter through `.data`."""
+        self._packed_key = None
+        self.FMT.invalidate()
+
+    def packed(self):
+        """(smooth_1 packed, smooth_2 packed) in ops.pack_conv3x3's layout of the current parameters."""
+        ws = (self.smooth_1.weight, self.smooth_2.weight)
+        key = tuple((w.data_ptr(), w._version, str(w.device)) for w in ws)
+        if key != self._packed_key:
+            ops = _ops()
+            self._packed, self._packed_key = tuple(ops.pack_conv3x3(w.detach()) for w in ws), key
+        return self._packed
+
+    def uses_kernels(self, features):
+        if not features or not self.FMT.uses_kernels(features[0]["stage1"]) or self.training or self.base_channels != 8:
+            return False
+        s1, s2, s3 = (features[0][k] for k in ("stage1", "stage2", "stage3"))
+        B, _, H, W = s1.shape
+        if tuple(s2.shape) != (B, 16, 2 * H, 2 * W) or tuple(s3.shape) != (B, 8, 4 * H, 4 * W) or self.smooth_1.weight.dtype != torch.float32:
+            return False
+        return all(f[k].shape == features[0][k].shape and f[k].is_cuda and f[k].dtype == torch.float32
+                   for f in features for k in ("stage1", "stage2", "stage3"))
+
+    def _upsample_add(self, x, y):
+        return F.interpolate(x, size=(y.shape[2], y.shape[3]), mode="bilinear") + y
+
+    def forward_torch(self, features):
+        refs = None
+        for i, f in enumerate(features):
+            if i == 0:
+                refs = self.FMT(f["stage1"].clone(), feat="ref")
+                f["stage1"] = refs[-1]
+            else:
+                f["stage1"] = self.FMT([r.clone() for r in refs], f["stage1"].clone(), feat="src")
+            f["stage2"] = self.smooth_1(self._upsample_add(self.dim_reduction_1(f["stage1"]), f["stage2"]))
+            f["stage3"] = self.smooth_2(self._upsample_add(self.dim_reduction_2(f["stage2"]), f["stage3"]))
+        return features
+
+    def pathway(self, tok, lateral2, lateral3):
+        """tok (N,H,W,32), lateral2 (N,2H,2W,16), lateral3 (N,4H,4W,8), channels-last -> (stage 2, stage 3) channels-last.  The merges
+        write over the laterals."""
+        ops = _ops()
+        p1, p2 = self.packed()
+        m2 = ops.fpn_merge(tok, self.dim_reduction_1.weight.detach(), lateral2, out=lateral2)
+        s2 = ops.conv3x3(m2, p1, None, 16)
+        m3 = ops.fpn_merge(s2, self.dim_reduction_2.weight.detach(), lateral3, out=lateral3)
+        return s2, ops.conv3x3(m3, p2, None, 8)
+
+    def forward(self, features):
+        if not self.uses_kernels(features):
+            return self.forward_torch(features)
+        NV = len(features)
+        B, _, H, W = (int(n) for n in features[0]["stage1"].shape)
+        tok = self.FMT.encode_tokens(torch.stack([f["stage1"].detach() for f in features], 0))
+        cl = lambda key: torch.stack([f[key].detach() for f in features], 0).permute(0, 1, 3, 4, 2).contiguous().view(NV * B, *(
+            features[0][key].shape[i] for i in (2, 3, 1)))                    # the one repack of each lateral: a copy the merge may write over
+        s2, s3 = self.pathway(tok.view(NV * B, H, W, 32), cl("stage2"), cl("stage3"))
+        for v, f in enumerate(features):
+            f["stage1"] = tok[v].view(B, H, W, 32).permute(0, 3, 1, 2)
+            f["stage2"] = s2[v * B:(v + 1) * B].permute(0, 3, 1, 2)
+            f["stage3"] = s3[v * B:(v + 1) * B].permute(0, 3, 1, 2)
+        return features
+
+
 def to_device(model):
-    """A loaded TransMVSNet -> the same model with model.DepthNet a DeviceDepthNet and model.cost_regularization a DeviceCostRegNet (one
-    shared module, or a ModuleList of one per stage, as share_cr made it), each carrying the original's state, device and training flag."""
+    """A loaded TransMVSNet -> the same model with model.DepthNet a DeviceDepthNet, model.cost_regularization a DeviceCostRegNet (one
+    shared module, or a ModuleList of one per stage, as share_cr made it) and model.FMT_with_pathway a DeviceFMTWithPathway, each carrying
+    the original's state, device and training flag.  A model without FMT_with_pathway keeps what it has."""
     model.DepthNet = DeviceDepthNet.from_module(model.DepthNet)
     cr = model.cost_regularization
     if isinstance(cr, nn.ModuleList):
         model.cost_regularization = nn.ModuleList([DeviceCostRegNet.from_module(m) for m in cr])
     else:
         model.cost_regularization = DeviceCostRegNet.from_module(cr)
+    if getattr(model, "FMT_with_pathway", None) is not None:
+        model.FMT_with_pathway = DeviceFMTWithPathway.from_module(model.FMT_with_pathway)
     return model
 
 

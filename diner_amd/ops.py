@@ -1541,6 +1541,178 @@ def deconv3d_s2(x, wpack, bias, Cout, relu=False, addend=None, out=None):
     return y
 
 
+# ---- the depth estimator's feature transformer (fmt.hip) ------------------------------------------------------------------------------
+FMT_D_MODEL, FMT_NHEAD, FMT_D_FF, FMT_MAX_HW = 32, 8, 64, 600      # DINER_FMT_*
+FMT_STATE_FLOATS, FMT_KV_TOKENS, FMT_PACK_FLOATS = 160, 512, 8544
+FPN_MAX_CHANNELS = 64                                              # DINER_FPN_MAX_CHANNELS
+# the sixteen tensors of one encoder layer in the pack's order, under the reference's state-dict keys: six matrices, then ten vectors
+FMT_LAYER_KEYS = ("attention.query_projection.weight", "attention.key_projection.weight", "attention.value_projection.weight",
+                  "attention.out_projection.weight", "linear1.weight", "linear2.weight",
+                  "attention.query_projection.bias", "attention.key_projection.bias", "attention.value_projection.bias",
+                  "attention.out_projection.bias", "norm1.weight", "norm1.bias", "linear1.bias", "linear2.bias", "norm2.weight", "norm2.bias")
+_FMT_LAYER_SHAPES = ((32, 32), (32, 32), (32, 32), (32, 32), (64, 32), (32, 64), (32,), (32,), (32,), (32,), (32,), (32,), (64,), (32,),
+                     (32,), (32,))
+
+
+def fmt_kv_blocks(L):
+    """Workgroups (partial sums) an image of L tokens takes in diner_fmt_kv_f32."""
+    return -(-int(L) // FMT_KV_TOKENS)
+
+
+def pack_fmt_layer(state_dict, prefix=""):
+    """One encoder layer's sixteen tensors (FMT_LAYER_KEYS under `prefix`) in the layout the kernels read: the six matrices transposed to
+    [in][out] -- query, key, value, out projection, linear1, linear2 -- then the ten vectors; FMT_PACK_FLOATS float32.  Plain torch on the
+    tensors' own device, so it needs no HIP device."""
+    parts = []
+    for key, shape in zip(FMT_LAYER_KEYS, _FMT_LAYER_SHAPES):
+        if prefix + key not in state_dict:
+            raise KeyError(f"diner_amd: pack_fmt_layer misses {prefix + key}")
+        t = state_dict[prefix + key]
+        if not torch.is_tensor(t) or tuple(t.shape) != shape:
+            raise ValueError(f"diner_amd: pack_fmt_layer expects {prefix + key} of shape {shape} (d_model 32, 8 heads, d_ff 64), got "
+                             f"{tuple(t.shape) if torch.is_tensor(t) else type(t).__name__}")
+        if t.dtype != torch.float32:
+            raise ValueError(f"diner_amd: pack_fmt_layer expects float32, got {t.dtype} for {prefix + key}")
+        t = t.detach()
+        parts.append((t.t() if t.dim() == 2 else t).reshape(-1))
+    return torch.cat(parts).contiguous()
+
+
+def _check_tokens(who, name, t, shape=None):
+    """Channels-last tokens (N,L,32): float32, contiguous -> (N, L)."""
+    if not torch.is_tensor(t) or t.dim() != 3 or t.shape[2] != FMT_D_MODEL:
+        raise ValueError(f"diner_amd: {who} expects {name} tokens (N,L,{FMT_D_MODEL}), got {tuple(t.shape) if torch.is_tensor(t) else type(t).__name__}")
+    if t.dtype != torch.float32:
+        raise ValueError(f"diner_amd: {who} expects {name} float32, got {t.dtype}")
+    if not t.is_contiguous():
+        raise ValueError(f"diner_amd: {who} expects {name} contiguous, got strides {t.stride()}")
+    N, L = int(t.shape[0]), int(t.shape[1])
+    if not (1 <= N <= 65535 and 1 <= L <= FMT_MAX_HW * FMT_MAX_HW):
+        raise ValueError(f"diner_amd: {who} expects 1 <= N <= 65535 images of 1 <= L <= {FMT_MAX_HW * FMT_MAX_HW} tokens, got {tuple(t.shape)}")
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise ValueError(f"diner_amd: {who} expects {name} {tuple(shape)}, got {tuple(t.shape)}")
+    return N, L
+
+
+def _check_fmt_pack(who, pack):
+    if not torch.is_tensor(pack) or pack.dtype != torch.float32 or tuple(pack.shape) != (FMT_PACK_FLOATS,) or not pack.is_contiguous():
+        raise ValueError(f"diner_amd: {who} expects pack float32 ({FMT_PACK_FLOATS},) (pack_fmt_layer), got "
+                         f"{tuple(pack.shape) if torch.is_tensor(pack) else type(pack).__name__}")
+
+
+def _check_fmt_tokenise_args(x, pe, out=None):
+    """-> (N, H, W)."""
+    if not torch.is_tensor(x) or x.dim() != 4 or x.shape[1] != FMT_D_MODEL:
+        raise ValueError(f"diner_amd: fmt_tokenise expects x (N,{FMT_D_MODEL},H,W), got {tuple(x.shape) if torch.is_tensor(x) else type(x).__name__}")
+    if not torch.is_tensor(pe) or pe.dim() != 3 or pe.shape[0] != FMT_D_MODEL or max(pe.shape[1:]) > FMT_MAX_HW:
+        raise ValueError(f"diner_amd: fmt_tokenise expects pe ({FMT_D_MODEL},h,w) with h, w <= {FMT_MAX_HW}, got "
+                         f"{tuple(pe.shape) if torch.is_tensor(pe) else type(pe).__name__}")
+    for name, t in (("x", x), ("pe", pe)):
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError(f"diner_amd: fmt_tokenise expects {name} float32 and contiguous, got {t.dtype}, strides {t.stride()}")
+    N, _, H, W = (int(s) for s in x.shape)
+    if not (1 <= N <= 65535 and 1 <= H <= pe.shape[1] and 1 <= W <= pe.shape[2]):
+        raise ValueError(f"diner_amd: fmt_tokenise expects 1 <= N <= 65535 and a map within the positional encoding's {tuple(pe.shape[1:])} "
+                         f"(at most {FMT_MAX_HW} a side), got {tuple(x.shape)}")
+    if out is not None:
+        _check_tokens("fmt_tokenise", "out", out, (N, H * W, FMT_D_MODEL))
+    return N, H, W
+
+
+def fmt_tokenise(x, pe, out=None):
+    """(N,32,H,W) NCHW + the top-left H x W of the positional encoding pe (32,h,w) -> tokens (N, H W, 32) (diner_fmt_tokenise_f32)."""
+    N, H, W = _check_fmt_tokenise_args(x, pe, out)
+    _require_hip(x, pe, out)
+    with torch.cuda.device(x.device):
+        y = out if out is not None else torch.empty(N, H * W, FMT_D_MODEL, dtype=torch.float32, device=x.device)
+        _lib.check(lib.diner_fmt_tokenise_f32(_ptr(x), _ptr(pe), _ptr(y), N, FMT_D_MODEL, H, W, int(pe.shape[1]), int(pe.shape[2]), _stream()))
+    return y
+
+
+def _check_fmt_kv_args(src, pack, partials=None, out=None):
+    """-> (N, L, partial blocks)."""
+    N, L = _check_tokens("fmt_kv", "src", src)
+    _check_fmt_pack("fmt_kv", pack)
+    nblk = fmt_kv_blocks(L)
+    if partials is not None and (not torch.is_tensor(partials) or partials.dtype != torch.float64 or not partials.is_contiguous()
+                                 or partials.numel() < N * nblk * FMT_STATE_FLOATS):
+        raise ValueError(f"diner_amd: fmt_kv expects partials float64, contiguous, of at least {N * nblk * FMT_STATE_FLOATS} elements")
+    if out is not None and (not torch.is_tensor(out) or out.dtype != torch.float32 or tuple(out.shape) != (N, FMT_STATE_FLOATS)
+                            or not out.is_contiguous()):
+        raise ValueError(f"diner_amd: fmt_kv expects out float32 ({N},{FMT_STATE_FLOATS}), contiguous")
+    return N, L, nblk
+
+
+def fmt_kv(src, pack, partials=None, out=None):
+    """The attention state of the source tokens src (N,L,32) under a layer pack's key and value projections -> (N,160): per head
+    KV[m][d] (128 floats as [h][m][d]), then Ksum[h][d] (diner_fmt_kv_f32).  partials: float64 workspace of N x fmt_kv_blocks(L) x 160."""
+    N, L, nblk = _check_fmt_kv_args(src, pack, partials, out)
+    _require_hip(src, pack, out)
+    if partials is not None and not partials.is_cuda:
+        raise RuntimeError("diner_amd: tensors must live on a HIP device (MI355X); there is no CPU fallback")
+    with torch.cuda.device(src.device):
+        if partials is None:
+            partials = torch.empty(N * nblk * FMT_STATE_FLOATS, dtype=torch.float64, device=src.device)
+        state = out if out is not None else torch.empty(N, FMT_STATE_FLOATS, dtype=torch.float32, device=src.device)
+        _lib.check(lib.diner_fmt_kv_f32(_ptr(src), _ptr(pack), _ptr(partials), _ptr(state), N, L, _stream()))
+    return state
+
+
+def _check_fmt_layer_args(x, pack, state, out=None):
+    """-> (N, L, rows of state)."""
+    N, L = _check_tokens("fmt_layer", "x", x)
+    _check_fmt_pack("fmt_layer", pack)
+    if not torch.is_tensor(state) or state.dtype != torch.float32 or state.dim() != 2 or state.shape[1] != FMT_STATE_FLOATS \
+            or not state.is_contiguous() or state.shape[0] < 1 or N % state.shape[0] != 0:
+        raise ValueError(f"diner_amd: fmt_layer expects state float32 (R,{FMT_STATE_FLOATS}), contiguous, R a divisor of N = {N}, got "
+                         f"{tuple(state.shape) if torch.is_tensor(state) else type(state).__name__}")
+    if out is not None:
+        _check_tokens("fmt_layer", "out", out, (N, L, FMT_D_MODEL))
+    return N, L, int(state.shape[0])
+
+
+def fmt_layer(x, pack, state, out=None):
+    """One encoder layer on the tokens x (N,L,32) with the attention state (R,160) of fmt_kv: image n reads row n mod R -- R = N for a
+    self layer, R = the batch size for a cross layer on view-major images (diner_fmt_layer_f32).  out may be x."""
+    N, L, R = _check_fmt_layer_args(x, pack, state, out)
+    _require_hip(x, pack, state, out)
+    with torch.cuda.device(x.device):
+        y = out if out is not None else torch.empty_like(x)
+        _lib.check(lib.diner_fmt_layer_f32(_ptr(x), _ptr(pack), _ptr(state), _ptr(y), N, L, R, _stream()))
+    return y
+
+
+def _check_fpn_merge_args(top, weight, lateral, out=None):
+    """-> (N, H, W, Ctop, Clat)."""
+    N, H, W, Ctop = _check_nhwc("fpn_merge", "top", top)
+    if not torch.is_tensor(weight) or weight.dtype != torch.float32 or not weight.is_contiguous() or weight.dim() not in (2, 4) \
+            or weight.shape[1] != Ctop or weight.numel() != weight.shape[0] * Ctop:
+        raise ValueError(f"diner_amd: fpn_merge expects the 1 x 1 weight float32 (Clat,{Ctop}) or (Clat,{Ctop},1,1), contiguous, got "
+                         f"{tuple(weight.shape) if torch.is_tensor(weight) else type(weight).__name__}")
+    Clat = int(weight.shape[0])
+    if Ctop > FPN_MAX_CHANNELS or Clat > FPN_MAX_CHANNELS or Clat < 4 or Clat % 4:
+        raise ValueError(f"diner_amd: fpn_merge expects Ctop <= {FPN_MAX_CHANNELS} and Clat a multiple of 4 up to it, got {Ctop} -> {Clat}")
+    if max(H, W) > 1 << 14:
+        raise ValueError(f"diner_amd: fpn_merge expects H, W <= 2^14, got {H}, {W}")
+    _check_nhwc("fpn_merge", "lateral", lateral, (N, 2 * H, 2 * W, Clat))
+    if out is not None:
+        _check_nhwc("fpn_merge", "out", out, (N, 2 * H, 2 * W, Clat))
+    return N, H, W, Ctop, Clat
+
+
+def fpn_merge(top, weight, lateral, out=None):
+    """The pathway's merge on channels-last maps (diner_fpn_merge_f32): top (N,H,W,Ctop), weight the bias-free 1 x 1 convolution
+    (Clat,Ctop[,1,1]), lateral (N,2H,2W,Clat) -> bilinear2x(conv1x1(top)) + lateral, the upsampling as
+    F.interpolate(mode="bilinear", align_corners=False).  out may be lateral."""
+    N, H, W, Ctop, Clat = _check_fpn_merge_args(top, weight, lateral, out)
+    _require_hip(top, weight, lateral, out)
+    with torch.cuda.device(top.device):
+        reduced = torch.empty(N, H, W, Clat, dtype=torch.float32, device=top.device)
+        y = out if out is not None else torch.empty_like(lateral)
+        _lib.check(lib.diner_fpn_merge_f32(_ptr(top), _ptr(weight), _ptr(lateral), _ptr(reduced), _ptr(y), N, H, W, Ctop, Clat, _stream()))
+    return y
+
+
 def _check_affine(who, shift, scale):
     out = []
     for name, v in (("shift", shift), ("scale", scale)):

@@ -972,6 +972,50 @@ int diner_conv3d_f32(const float* x, const float* wpack, const float* bias, cons
 int diner_deconv3d_s2_f32(const float* x, const float* wpack, const float* bias, const float* addend, float* y, int N, int D, int H, int W,
                           int Cin, int Cout, int relu, void* stream);
 
+/* ---- the depth estimator's feature transformer: TransMVSNet's FMT and its FPN pathway --------------------------------------------------
+ * New symbols without an ABI bump (fmt.hip); inference only, no allocation, enqueue-only, everything fp32 (the partial sums of the
+ * attention state are doubles); activations are channels-last tokens (N, L = H W, 32).  Built for d_model DINER_FMT_D_MODEL, DINER_FMT_NHEAD
+ * heads, d_ff DINER_FMT_D_FF and maps of at most DINER_FMT_MAX_HW a side.  No atomics; every sum has an order the shape alone fixes and no
+ * workgroup crosses images, so two runs give the same bits and an image's values depend neither on its place in the batch nor on how
+ * many images share the call.  Bad arguments return DINER_E_INVALID with a message before any device work.
+ *
+ * The layer pack, diner_fmt_pack_floats() = DINER_FMT_PACK_FLOATS floats, 16-byte aligned: the matrices of one encoder layer TRANSPOSED
+ * ([in][out], element [k][j] = weight[j][k] of the torch Linear) in the order query, key, value, out projection (32 x 32 each), linear1
+ * (32 x 64), linear2 (64 x 32), then the vectors query, key, value, out bias, norm1 weight, norm1 bias, linear1 bias (64), linear2 bias,
+ * norm2 weight, norm2 bias.
+ *
+ * diner_fmt_tokenise_f32: tokens[n][y W + x][c] = x[n][c][y][x] + pe[c][y][x], x (N,C,H,W) NCHW with C = 32, pe (C,pe_h,pe_w) the sine
+ *   positional encoding of which the top-left H x W is read; one fp32 add.
+ * diner_fmt_kv_f32: the attention state of the source tokens src (N,L,32) under the pack's key and value projections:
+ *   K = elu(src Wk^T + bk) + 1, V = src Wv^T + bv (each the bias plus one fmaf chain, k ascending); per head h of 4 channels
+ *   KV[h][m][d] = sum_s K[s][4 h + d] V[s][4 h + m], Ksum[h][d] = sum_s K[s][4 h + d]; state (N, DINER_FMT_STATE_FLOATS): KV as
+ *   [h][m][d] (128 floats), then Ksum [h][d] (32).  Workgroup b of an image sums tokens [b T, (b + 1) T), T = DINER_FMT_KV_TOKENS, in double
+ *   (the 64 lanes' xor tree, then the four waves in order) into partials (N, diner_fmt_kv_blocks(L), 160) doubles, workspace; a second
+ *   launch adds an image's partials in block order and rounds once to float.
+ * diner_fmt_layer_f32: one encoder layer per token, out (N,L,32) (may be x): Q = elu(x Wq^T + bq) + 1; per head Z = 1 / (Q . Ksum + 1e-6),
+ *   A[m] = Z sum_d Q[d] KV[m][d]; x1 = LN1(x + A Wo^T + bo); y = relu(x1 W1^T + b1) W2^T + b2; out = LN2(x1 + y); LayerNorm over the 32
+ *   channels with the biased variance, eps 1e-5, affine.  Image n reads row n mod state_rows of state (state_rows, 160): state_rows = N
+ *   for a self layer, = the batch size for a cross layer whose images are ordered view-major (n = view B + b).  state_rows divides N.
+ * diner_fpn_merge_f32: y (N,2H,2W,Clat) = bilinear2x(conv1x1(top)) + lateral: top (N,H,W,Ctop), w (Clat,Ctop) the bias-free 1 x 1
+ *   convolution, computed at the coarse size into reduced (N,H,W,Clat), workspace; the upsampling is
+ *   F.interpolate(mode="bilinear", align_corners=False) at exactly twice the size (phases 0.25 / 0.75, the edge clamped), evaluated as
+ *   ly0 (lx0 p00 + lx1 p01) + ly1 (lx0 p10 + lx1 p11).  Ctop <= DINER_FPN_MAX_CHANNELS, Clat a multiple of 4 up to it; two launches. */
+#define DINER_FMT_D_MODEL 32
+#define DINER_FMT_NHEAD 8
+#define DINER_FMT_D_FF 64
+#define DINER_FMT_MAX_HW 600
+#define DINER_FMT_STATE_FLOATS 160
+#define DINER_FMT_KV_TOKENS 512
+#define DINER_FMT_PACK_FLOATS 8544
+#define DINER_FPN_MAX_CHANNELS 64
+size_t diner_fmt_pack_floats(void);
+size_t diner_fmt_kv_blocks(int L);
+int diner_fmt_tokenise_f32(const float* x, const float* pe, float* tokens, int N, int C, int H, int W, int pe_h, int pe_w, void* stream);
+int diner_fmt_kv_f32(const float* src, const float* pack, double* partials, float* state, int N, int L, void* stream);
+int diner_fmt_layer_f32(const float* x, const float* pack, const float* state, float* out, int N, int L, int state_rows, void* stream);
+int diner_fpn_merge_f32(const float* top, const float* w, const float* lateral, float* reduced, float* y, int N, int H, int W, int Ctop,
+                        int Clat, void* stream);
+
 /* ---- measurement aid (bench.py): per-kernel durations of the two field kernels ------------------
  * With profiling enabled every field call brackets k_field_pre / k_field_post with HIP events on the
  * launch stream; diner_profile_collect waits for them, returns the summed durations (ms), the number

@@ -23,6 +23,7 @@
 #   encoder-time [args]        tools/time_encoder.py: the trunk at 4 x 800x600 and 16 x 400x300 on the torch / MIOpen route and the device route, alternating; peak memory, the first call of each in a fresh process, the device route's launches one by one (stdout)
 #   mvs-time [args]            tools/time_mvs.py: the matching stage's entries and the whole coarse_to_fine at the DTU stage shapes and a 256 x 320 image, kernels against the torch restatement on the device, alternating; peak memory (stdout; keep it as profiles/mvs_time_ab.txt)
 #   costreg-time [args]        tools/time_costreg.py: CostRegNet on the three DTU stage volumes at base 8, kernels against the torch / MIOpen route, alternating; peak memory, the eleven launches one by one against their bounds, and the whole coarse_to_fine with the real regulariser (stdout; keep it as profiles/costreg_time_ab.txt)
+#   fmt-time [args]            tools/time_fmt.py: FMT_with_pathway, the FMT alone and the pathway alone at the DTU shape (stage 1 of 128 x 160, five views), kernels against the torch route, alternating; peak memory, each launch against its bound, and coarse_to_fine with the module in front (stdout; keep it as profiles/fmt_time_ab.txt)
 #   smoke                      __graft_entry__.smoke()
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}" || exit 1
 mkdir -p gpurun_out
@@ -103,6 +104,9 @@ PY
   costreg-time)
     set -o pipefail
     timeout -k 10 500 python tools/time_costreg.py "$@" 2>&1 | grep -v amdgpu.ids ;;
+  fmt-time)
+    set -o pipefail
+    timeout -k 10 500 python tools/time_fmt.py "$@" 2>&1 | grep -v amdgpu.ids ;;
   smoke) python __graft_entry__.py smoke ;;
   *) echo "unknown job '$job' (see the header of tools/job.sh)"; exit 2 ;;
 esac
