@@ -13,7 +13,7 @@ ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(ROOT, "build", "obj")
 LIB = os.path.join(HERE, "libdiner_hip.so")
-SOURCES = ["api.cpp", "sampler.hip", "composite.hip", "stage_ops.hip", "prep.hip", "train.hip", "train_512.hip", "mlp.hip", "mlp_h3n.hip", "generic.hip", "metrics.hip", "objective.hip", "cull.hip", "geometry.hip", "surface.hip", "raycast.hip", "cloud.hip", "conv2d.hip", "perceptual.hip", "optim.hip", "encoder.hip", "mvs.hip", "costreg.hip", "fmt.hip"]
+SOURCES = ["api.cpp", "sampler.hip", "composite.hip", "stage_ops.hip", "prep.hip", "train.hip", "train_512.hip", "mlp.hip", "mlp_h3n.hip", "generic.hip", "metrics.hip", "objective.hip", "cull.hip", "geometry.hip", "surface.hip", "raycast.hip", "cloud.hip", "conv2d.hip", "perceptual.hip", "optim.hip", "encoder.hip", "mvs.hip", "costreg.hip", "fmt.hip", "deform.hip"]
 # -ffp-contract=off: every fp32 op of the geometry path rounds where the reference's torch ops round;
 # fused multiply-adds are written explicitly (fmaf / MFMA) where they are wanted.
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-Wno-unused-value",
@@ -31,6 +31,7 @@ EXTRA_FLAGS = {
     "mvs.hip": ["-Rpass-analysis=kernel-resource-usage"],       # k_mvs_cost_volume<1 .. 16> must stay free of scratch
     "costreg.hip": ["-Rpass-analysis=kernel-resource-usage"],   # k_conv3d<1 | 2> and k_deconv3d_s2 must stay free of scratch
     "fmt.hip": ["-Rpass-analysis=kernel-resource-usage"],       # k_fmt_kv and k_fmt_layer must stay free of scratch
+    "deform.hip": ["-Rpass-analysis=kernel-resource-usage"],    # k_deform_conv3x3<1 | 2, 1 | 2 | 4> and k_fpn_lateral likewise
 }
 
 
@@ -72,6 +73,7 @@ def build_variant(name, defines, verbose=False):
 def build(force=False, verbose=False):
     os.makedirs(OBJ, exist_ok=True)
     deps = [os.path.join(CSRC, "common.hpp"), os.path.join(CSRC, "field_common.hpp"), os.path.join(CSRC, "train_lin512.hpp"),
+            os.path.join(CSRC, "deform_geom.hpp"),
             os.path.join(CSRC, "train_lin512.hip"), os.path.join(CSRC, "train_wgrad512.hip"),      # included by train_512.hip
             os.path.join(ROOT, "include", "diner_hip.h")]
     hipcc = _hipcc()

@@ -2,7 +2,8 @@
 // activations channels-last (N,H,W,C):
 //   * k_conv2d<R, S>: R x R convolution, stride S, zero padding R / 2, as an implicit GEMM on the fp32-input MFMA
 //     (v_mfma_f32_16x16x4_f32, bit for bit an fmaf chain): pixels x Cout accumulators, K = R R Cin.  Built for <3,1> (the VGG stack and
-//     the trunk's residual blocks) and <1,2>, <3,2>, <7,2> (the trunk's downsample, first block convolution and stem).
+//     the trunk's residual blocks), <1,2>, <3,2>, <7,2> (the trunk's downsample, first block convolution and stem) and, behind entries of
+//     their own, <5,2> and <1,1> (the depth estimator's FeatureNet: its two downsampling convolutions and the 1 x 1 in front of stage 1).
 //   * The accumulator starts at the bias; the epilogue adds an optional addend, applies an optional ReLU and an optional mask, and
 //     writes with a channel stride and offset of the output's own (the stem writes channels 0 .. 63 of the latent directly).  With the
 //     second packed weight set (taps flipped, Cin and Cout swapped) <3,1> is the data gradient: the addend is then the loss gradient
@@ -206,9 +207,10 @@ size_t conv2d_pack_floats(int Cin, int Cout, int R) {
   return (size_t)((Cin + kCK - 1) / kCK) * R * R * kCK * (size_t)((Cout + kBN - 1) / kBN * kBN);
 }
 
-// the checks, the arguments and the grid of both entries; `who` begins every error text
+// the checks, the arguments and the grid of every entry; `who` begins every error text.  featurenet: the caller is one of the entries that
+// reach <5,2> and <1,1>; diner_conv2d_s2_f32 keeps refusing R = 5
 int conv2d(const char* who, int R, int S, const float* x, const float* wpack, const float* bias, const float* addend, const float* mask, float* y,
-           int N, int H, int W, int Cin, int Cout, int relu, int ldy, int coff, hipStream_t stream) {
+           int N, int H, int W, int Cin, int Cout, int relu, int ldy, int coff, hipStream_t stream, bool featurenet = false) {
   int rc = check_nhwc(who, N, H, W, Cin);
   if (rc) return rc;
   void (*launch)(const ConvArgs&, dim3, hipStream_t) = nullptr;
@@ -216,6 +218,8 @@ int conv2d(const char* who, int R, int S, const float* x, const float* wpack, co
   else if (S == 2 && R == 1) launch = launch_conv2d<1, 2>;
   else if (S == 2 && R == 3) launch = launch_conv2d<3, 2>;
   else if (S == 2 && R == 7) launch = launch_conv2d<7, 2>;
+  else if (featurenet && S == 2 && R == 5) launch = launch_conv2d<5, 2>;
+  else if (featurenet && S == 1 && R == 1) launch = launch_conv2d<1, 1>;
   if (!launch) {
     set_error("%s: R = %d (the kernel sizes built are 1, 3 and 7)", who, R);
     return DINER_E_UNSUPPORTED;
@@ -266,4 +270,24 @@ extern "C" size_t diner_conv2d_s2_pack_floats(int Cin, int Cout, int R) {
 extern "C" int diner_conv2d_s2_f32(const float* x, const float* wpack, const float* bias, float* y, int N, int H, int W, int Cin, int Cout, int R,
                                    int relu, int ldy, int coff, void* stream) {
   return conv2d("conv2d_s2", R, 2, x, wpack, bias, nullptr, nullptr, y, N, H, W, Cin, Cout, relu, ldy, coff, (hipStream_t)stream);
+}
+
+extern "C" size_t diner_conv5x5_s2_pack_floats(int Cin, int Cout) {
+  if (Cin < 1 || Cout < 1) return 0;
+  return conv2d_pack_floats(Cin, Cout, 5);
+}
+
+extern "C" int diner_conv5x5_s2_f32(const float* x, const float* wpack, const float* bias, float* y, int N, int H, int W, int Cin, int Cout, int relu,
+                                    void* stream) {
+  return conv2d("conv5x5_s2", 5, 2, x, wpack, bias, nullptr, nullptr, y, N, H, W, Cin, Cout, relu, Cout, 0, (hipStream_t)stream, true);
+}
+
+extern "C" size_t diner_conv1x1_pack_floats(int Cin, int Cout) {
+  if (Cin < 1 || Cout < 1) return 0;
+  return conv2d_pack_floats(Cin, Cout, 1);
+}
+
+extern "C" int diner_conv1x1_f32(const float* x, const float* wpack, const float* bias, float* y, int N, int H, int W, int Cin, int Cout, int relu,
+                                 void* stream) {
+  return conv2d("conv1x1", 1, 1, x, wpack, bias, nullptr, nullptr, y, N, H, W, Cin, Cout, relu, Cout, 0, (hipStream_t)stream, true);
 }

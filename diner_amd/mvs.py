@@ -3,7 +3,9 @@ and the stage loop of TransMVSNet.forward do between the learned networks -- hom
 pixelwise view weights, the weighted aggregation, the winner-take-all read-out of the regularised cost and the next stage's depth
 hypotheses -- on the kernels of csrc/mvs.hip, and the cost regulariser between them, the 3-D U-Net CostRegNet (models/module.py:424-455),
 on the kernels of csrc/costreg.hip (DeviceCostRegNet), and the feature transformer in front of the loop, FMT_with_pathway (models/FMT.py),
-on the kernels of csrc/fmt.hip (DeviceFMT, DeviceFMTWithPathway).  FeatureNet stays the caller's torch module.
+on the kernels of csrc/fmt.hip (DeviceFMT, DeviceFMTWithPathway), and the feature pyramid in front of that, FeatureNet
+(models/module.py:343-421) with its nine modulated deformable convolutions, on the kernels of csrc/deform.hip and csrc/conv2d.hip
+(DeviceFeatureNet); depth_from_images chains them from the images to the stage outputs.
 
 Every thin function takes the reference's tensor layouts (NCHW).  On HIP tensors it runs the kernels; on CPU tensors it runs a torch
 restatement of the same mathematics with the reference's own operations in the reference's order (`*_torch`, any floating dtype),
@@ -598,6 +600,7 @@ class DeviceFMT(nn.Module):
         NV, B, _, H, W = (int(n) for n in maps.shape)
         L = H * W
         packs = self.packed()
+        maps = maps.contiguous()                 # stacked channels-last views (DeviceFeatureNet's kernel route) keep their strides
         tok = ops.fmt_tokenise(maps.view(NV * B, 32, H, W), self.pe[0]).view(NV, B, L, 32)
         ref, src = tok[0], tok[1:].reshape((NV - 1) * B, L, 32) if NV > 1 else None
         partials = torch.empty(max(NV - 1, 1) * B * ops.fmt_kv_blocks(L) * ops.FMT_STATE_FLOATS, dtype=torch.float64, device=maps.device)
@@ -721,10 +724,264 @@ class DeviceFMTWithPathway(nn.Module):
         return features
 
 
+# ---- the drop-in for the reference's FeatureNet -------------------------------------------------------------------------------------------
+def _pair(v):
+    return (int(v), int(v)) if isinstance(v, int) else tuple(int(a) for a in v)
+
+
+def deform_conv2d_torch(input, offset, weight, bias=None, stride=(1, 1), padding=(0, 0), dilation=(1, 1), mask=None):
+    """torchvision.ops.deform_conv2d in torch operations (index gathers; differentiable in every argument; any floating dtype), with one
+    offset group and one weight group: input (B,Cin,H,W), offset (B, 2 kh kw, Ho, Wo) with channel 2 k the row and 2 k + 1 the column
+    offset of tap k = ky kw + kx, weight (Cout,Cin,kh,kw), mask (B, kh kw, Ho, Wo) or None -> (B,Cout,Ho,Wo).  Tap k of output pixel
+    (h, w) samples the input at py = (h stride - padding + ky dilation) + dy, px likewise, with torchvision's bilinear_interpolate: 0 when
+    py <= -1, py >= H, px <= -1 or px >= W; otherwise y0 = floor(py), ly = py - y0, hy = 1 - ly (columns likewise), corners outside the
+    image contribute 0, value = hy hx v00 + hy lx v01 + ly hx v10 + ly lx v11; times the mask; then the convolution's sum and the bias."""
+    if input.dim() != 4 or weight.dim() != 4 or offset.dim() != 4:
+        raise ValueError("diner_amd: deform_conv2d_torch expects input (B,Cin,H,W), offset (B,2 kh kw,Ho,Wo) and weight (Cout,Cin,kh,kw)")
+    B, Cin, H, W = (int(n) for n in input.shape)
+    Cout, Cw, kh, kw = (int(n) for n in weight.shape)
+    (sh, sw), (ph, pw), (dh, dw) = _pair(stride), _pair(padding), _pair(dilation)
+    Ho, Wo = (H + 2 * ph - dh * (kh - 1) - 1) // sh + 1, (W + 2 * pw - dw * (kw - 1) - 1) // sw + 1
+    K = kh * kw
+    if Cw != Cin:
+        raise ValueError(f"diner_amd: deform_conv2d_torch is stated for one weight group: weight has {Cw} input channels, input {Cin}")
+    if tuple(offset.shape) != (B, 2 * K, Ho, Wo):
+        raise ValueError(f"diner_amd: deform_conv2d_torch is stated for one offset group: offset must be {(B, 2 * K, Ho, Wo)}, got "
+                         f"{tuple(offset.shape)}")
+    if mask is not None and tuple(mask.shape) != (B, K, Ho, Wo):
+        raise ValueError(f"diner_amd: deform_conv2d_torch expects mask {(B, K, Ho, Wo)}, got {tuple(mask.shape)}")
+    dt, dev = input.dtype, input.device
+    ky, kx = torch.arange(kh, device=dev).repeat_interleave(kw), torch.arange(kw, device=dev).repeat(kh)
+    base_y = (torch.arange(Ho, device=dev) * sh - ph).view(1, Ho, 1) + (ky * dh).view(K, 1, 1)          # integers first, as torchvision sums them
+    base_x = (torch.arange(Wo, device=dev) * sw - pw).view(1, 1, Wo) + (kx * dw).view(K, 1, 1)
+    py = base_y.to(dt).unsqueeze(0) + offset[:, 0::2]
+    px = base_x.to(dt).unsqueeze(0) + offset[:, 1::2]
+    inside = (py > -1) & (py < H) & (px > -1) & (px < W)                   # a NaN fails every comparison: outside
+    py, px = torch.where(inside, py, torch.zeros_like(py)), torch.where(inside, px, torch.zeros_like(px))
+    y0, x0 = torch.floor(py), torch.floor(px)
+    ly, lx = py - y0, px - x0
+    hy, hx = 1 - ly, 1 - lx
+    y0i, x0i = y0.detach().long(), x0.detach().long()
+    flat = input.reshape(B, Cin, H * W)
+
+    def corner(yi, xi):
+        valid = inside & (yi >= 0) & (yi <= H - 1) & (xi >= 0) & (xi <= W - 1)
+        idx = (yi.clamp(0, H - 1) * W + xi.clamp(0, W - 1)).reshape(B, 1, K * Ho * Wo).expand(B, Cin, K * Ho * Wo)
+        v = flat.gather(2, idx).reshape(B, Cin, K, Ho, Wo)
+        return torch.where(valid.unsqueeze(1), v, torch.zeros_like(v))
+
+    val = ((hy * hx).unsqueeze(1) * corner(y0i, x0i) + (hy * lx).unsqueeze(1) * corner(y0i, x0i + 1)
+           + (ly * hx).unsqueeze(1) * corner(y0i + 1, x0i) + (ly * lx).unsqueeze(1) * corner(y0i + 1, x0i + 1))
+    if mask is not None:
+        val = val * mask.unsqueeze(1)
+    out = torch.matmul(weight.reshape(Cout, Cin * K), val.reshape(B, Cin * K, Ho * Wo)).reshape(B, Cout, Ho, Wo)
+    return out if bias is None else out + bias.view(1, -1, 1, 1)
+
+
+class _Conv2dBnReLU(nn.Module):
+    """The reference's Conv2d block (models/module.py:24-62) with BatchNorm and ReLU, under its state-dict keys (conv.weight, bn.*)."""
+
+    def __init__(self, cin, cout, kernel, stride=1, padding=0):
+        super().__init__()
+        self.conv = nn.Conv2d(cin, cout, kernel, stride=stride, padding=padding, bias=False)
+        self.bn = nn.BatchNorm2d(cout, momentum=0.1)
+
+    def forward(self, x):
+        return F.relu(self.bn(self.conv(x)), inplace=True)
+
+
+class _DCN(nn.Module):
+    """The reference's DCN (models/dcn.py) under its state-dict keys (weight, bias, conv_offset_mask.*), on deform_conv2d_torch."""
+
+    def __init__(self, cin, cout):
+        super().__init__()
+        self.weight = nn.Parameter(torch.empty(cout, cin, 3, 3))
+        self.bias = nn.Parameter(torch.zeros(cout))
+        self.conv_offset_mask = nn.Conv2d(cin, 27, 3, stride=1, padding=1, bias=True)
+        stdv = 1.0 / np.sqrt(cin * 9)
+        nn.init.uniform_(self.weight, -stdv, stdv)
+        nn.init.zeros_(self.conv_offset_mask.weight)
+        nn.init.zeros_(self.conv_offset_mask.bias)
+
+    def forward(self, x):
+        out = self.conv_offset_mask(x)
+        o1, o2, mask = torch.chunk(out, 3, dim=1)
+        return deform_conv2d_torch(x, torch.cat((o1, o2), dim=1), self.weight, self.bias, (1, 1), (1, 1), (1, 1), mask=torch.sigmoid(mask))
+
+
+def _fold_bn2d(weight, bias, sd, bn):
+    """A 2-D convolution (bias or None) followed by the BatchNorm under prefix `bn` of sd as one convolution with a bias, fold_conv_bn's
+    idiom: float64 on the tensors' own device, rounded once: s = gamma / sqrt(var + eps), w' = w s, b' = (b - mean) s + beta."""
+    s = sd[bn + "weight"].detach().double() / torch.sqrt(sd[bn + "running_var"].detach().double() + BN_EPS)
+    b = 0.0 if bias is None else bias.detach().double()
+    return ((weight.detach().double() * s.view(-1, 1, 1, 1)).to(torch.float32),
+            ((b - sd[bn + "running_mean"].detach().double()) * s + sd[bn + "bias"].detach().double()).to(torch.float32))
+
+
+def _pad_bias(b, n=64):
+    out = b.new_zeros(-(-b.shape[0] // n) * n)
+    out[:b.shape[0]] = b
+    return out
+
+
+FEATURENET_HEADS = (("out1", "stage1", 32), ("out2", "stage2", 16), ("out3", "stage3", 8))
+
+
+class DeviceFeatureNet(nn.Module):
+    """A replacement for the reference's FeatureNet (models/module.py:343-421): the same state-dict keys (conv0.0.conv.weight,
+    conv0.0.bn.*, ... out1.1.weight, out1.1.bias, out1.1.conv_offset_mask.*, out1.2.*, ... inner1.*, inner2.*), the same forward():
+    images (B,3,H,W) -> {"stage1": (B,32,H/4,W/4), "stage2": (B,16,H/2,W/2), "stage3": (B,8,H,W)}.  On float32 HIP tensors and
+    parameters, in eval mode, with gradients disabled, base_channels 8 and H, W multiples of 4 (the only sizes at which the reference's
+    own upsample-and-add matches) it runs the kernels: diner_encoder_input_f32 (C 4), diner_conv3x3_f32, diner_conv5x5_s2_f32,
+    diner_conv1x1_f32, diner_fpn_lateral_f32 and, for each of the nine deformable convolutions, diner_conv3x3_f32 (the 27 offset and
+    modulation channels) followed by diner_deform_conv3x3_f32; BatchNorm is folded into the weights.  Its results then have the
+    reference's shapes but are PERMUTED VIEWS OF CHANNELS-LAST MEMORY, which DeviceFMTWithPathway takes unchanged.  Otherwise it runs
+    the reference's operations in the reference's order, the deformable convolution as deform_conv2d_torch: differentiable, on batch
+    statistics in training mode.  No torchvision anywhere.  `mvs.to_device(model)` switches a loaded TransMVSNet over."""
+
+    def __init__(self, base_channels=8):
+        super().__init__()
+        c = self.base_channels = int(base_channels)
+        self.conv0 = nn.Sequential(_Conv2dBnReLU(3, c, 3, 1, 1), _Conv2dBnReLU(c, c, 3, 1, 1))
+        self.conv1 = nn.Sequential(_Conv2dBnReLU(c, 2 * c, 5, 2, 2), _Conv2dBnReLU(2 * c, 2 * c, 3, 1, 1), _Conv2dBnReLU(2 * c, 2 * c, 3, 1, 1))
+        self.conv2 = nn.Sequential(_Conv2dBnReLU(2 * c, 4 * c, 5, 2, 2), _Conv2dBnReLU(4 * c, 4 * c, 3, 1, 1), _Conv2dBnReLU(4 * c, 4 * c, 3, 1, 1))
+        f = 4 * c
+
+        def head(first, cout):
+            return nn.Sequential(first, _DCN(f, f), nn.BatchNorm2d(f), nn.ReLU(inplace=True), _DCN(f, f), nn.BatchNorm2d(f),
+                                 nn.ReLU(inplace=True), _DCN(f, cout))
+        self.out1 = head(_Conv2dBnReLU(f, f, 1), f)
+        self.inner1 = nn.Conv2d(2 * c, f, 1, bias=True)
+        self.inner2 = nn.Conv2d(c, f, 1, bias=True)
+        self.out2 = head(_Conv2dBnReLU(f, f, 3, 1, 1), 2 * c)
+        self.out3 = head(_Conv2dBnReLU(f, f, 3, 1, 1), c)
+        self.out_channels = [4 * c, 2 * c, c]
+        self._packed, self._packed_key = None, None
+
+    @classmethod
+    def from_module(cls, feature):
+        sd = feature.state_dict()
+        w = sd["conv0.0.conv.weight"]
+        new = cls(int(w.shape[0]))
+        new.to(device=w.device, dtype=w.dtype)
+        new.load_state_dict(sd)
+        new.train(feature.training)
+        return new
+
+    def invalidate(self):
+        """Forget the packed weights: call after writing a parameter or buffer through `.data`, which bumps no version counter."""
+        self._packed_key = None
+
+    def packed(self):
+        """name -> (packed weight, bias) of every layer of the kernel route, BatchNorm folded, of the current parameters; a deformable
+        layer "outX.i" has a second entry "outX.i.offset" for its conv_offset_mask.  Packed again only after a parameter or buffer
+        changed (no host read-back either way)."""
+        sd = self.state_dict()
+        key = tuple((k, v.data_ptr(), v._version, str(v.device)) for k, v in sd.items())
+        if key != self._packed_key:
+            ops = _ops()
+            P = {}
+            for name, kind in (("conv0.0", 3), ("conv0.1", 3), ("conv1.0", 5), ("conv1.1", 3), ("conv1.2", 3), ("conv2.0", 5), ("conv2.1", 3),
+                               ("conv2.2", 3), ("out1.0", 1), ("out2.0", 3), ("out3.0", 3)):
+                w, b = _fold_bn2d(sd[name + ".conv.weight"], None, sd, name + ".bn.")
+                if kind == 3:
+                    cin = 4 if name == "conv0.0" else None                   # the input relayout writes four channels, the fourth zero
+                    P[name] = (ops.pack_conv3x3(w, Cin=cin), _pad_bias(b))
+                else:
+                    P[name] = ((ops.pack_conv5x5 if kind == 5 else ops.pack_conv1x1)(w), b.contiguous())
+            for head, _, _ in FEATURENET_HEADS:
+                for i in (1, 4, 7):
+                    d = f"{head}.{i}."
+                    P[d + "offset"] = (ops.pack_conv3x3(sd[d + "conv_offset_mask.weight"].detach().float()),
+                                       _pad_bias(sd[d + "conv_offset_mask.bias"].detach().float()))
+                    if i < 7:
+                        w, b = _fold_bn2d(sd[d + "weight"], sd[d + "bias"], sd, f"{head}.{i + 1}.")
+                    else:
+                        w, b = sd[d + "weight"].detach().float(), sd[d + "bias"].detach().float()
+                    P[d[:-1]] = (ops.pack_deform_conv3x3(w.contiguous()), b.contiguous())
+            for name in ("inner1", "inner2"):
+                P[name] = (sd[name + ".weight"].detach().float().contiguous(), sd[name + ".bias"].detach().float().contiguous())
+            self._packed, self._packed_key = P, key
+        return self._packed
+
+    def uses_kernels(self, x):
+        """The gate.  Parameters of another dtype than float32 leave it closed, so that a float32 input then fails in torch's own
+        convolution as it does in the reference."""
+        return (x.is_cuda and x.dtype == torch.float32 and self.inner1.weight.dtype == torch.float32 and not self.training
+                and not torch.is_grad_enabled() and self.base_channels == 8 and x.dim() == 4 and x.shape[1] == 3 and x.shape[0] >= 1
+                and x.shape[2] >= 4 and x.shape[3] >= 4 and x.shape[2] % 4 == 0 and x.shape[3] % 4 == 0)
+
+    def forward_torch(self, x):
+        conv0 = self.conv0(x)
+        conv1 = self.conv1(conv0)
+        conv2 = self.conv2(conv1)
+        intra_feat = conv2
+        outputs = {"stage1": self.out1(intra_feat)}
+        intra_feat = F.interpolate(intra_feat, scale_factor=2, mode="nearest") + self.inner1(conv1)
+        outputs["stage2"] = self.out2(intra_feat)
+        intra_feat = F.interpolate(intra_feat, scale_factor=2, mode="nearest") + self.inner2(conv0)
+        outputs["stage3"] = self.out3(intra_feat)
+        return outputs
+
+    def forward_cl(self, x):
+        """The kernel route on images (N,3,H,W) -> channels-last (stage 1 (N,H/4,W/4,32), stage 2 (N,H/2,W/2,16), stage 3 (N,H,W,8))."""
+        ops, P = _ops(), self.packed()
+        conv = lambda t, name, cout: ops.conv3x3(t, *P[name], cout, relu=True)
+
+        def head(t, name, cout):
+            for i, (co, relu) in ((1, (32, True)), (4, (32, True)), (7, (cout, False))):
+                offmask = ops.conv3x3(t, *P[f"{name}.{i}.offset"], 27)
+                t = ops.deform_conv3x3(t, offmask, *P[f"{name}.{i}"], co, relu=relu)
+            return t
+        x = ops.encoder_input(x.detach().contiguous(), pad=0, C=4)
+        conv0 = conv(conv(x, "conv0.0", 8), "conv0.1", 8)
+        conv1 = conv(conv(ops.conv5x5_s2(conv0, *P["conv1.0"], 16, relu=True), "conv1.1", 16), "conv1.2", 16)
+        conv2 = conv(conv(ops.conv5x5_s2(conv1, *P["conv2.0"], 32, relu=True), "conv2.1", 32), "conv2.2", 32)
+        s1 = head(ops.conv1x1(conv2, *P["out1.0"], 32, relu=True), "out1", 32)
+        intra = ops.fpn_lateral(conv2, conv1, *P["inner1"])
+        s2 = head(conv(intra, "out2.0", 32), "out2", 16)
+        intra = ops.fpn_lateral(intra, conv0, *P["inner2"])
+        s3 = head(conv(intra, "out3.0", 32), "out3", 8)
+        return s1, s2, s3
+
+    def forward(self, x):
+        if not self.uses_kernels(x):
+            return self.forward_torch(x)
+        return {k: t.permute(0, 3, 1, 2) for k, t in zip(("stage1", "stage2", "stage3"), self.forward_cl(x))}
+
+    def forward_views(self, imgs):
+        """imgs (B,NV,3,H,W) -> the per-view list of dicts FMT_with_pathway takes.  On the kernel route all NV B images run as one batch
+        (view-major); otherwise view by view, as TransMVSNet.forward calls the module."""
+        if imgs.dim() != 5 or imgs.shape[2] != 3:
+            raise ValueError(f"diner_amd: DeviceFeatureNet.forward_views expects imgs (B,NV,3,H,W), got {tuple(imgs.shape)}")
+        B, NV = int(imgs.shape[0]), int(imgs.shape[1])
+        if not self.uses_kernels(imgs[:, 0]):
+            return [self.forward(img) for img in torch.unbind(imgs, 1)]
+        out = self.forward(imgs.detach().transpose(0, 1).reshape(NV * B, *imgs.shape[2:]))
+        return [{k: t[v * B:(v + 1) * B] for k, t in out.items()} for v in range(NV)]
+
+
+def depth_from_images(imgs, proj_matrices, depth_values, feature, fmt_with_pathway, depthnet, cost_regularization, **kwargs):
+    """TransMVSNet.forward up to the stage outputs: imgs (B,NV,3,H,W), reference view first -> feature (a DeviceFeatureNet, or the
+    reference's FeatureNet called view by view) -> fmt_with_pathway -> coarse_to_fine with its keywords (image_hw defaults to the images'
+    size).  With the device modules and float32 HIP tensors under torch.no_grad() everything from the images to the depth maps runs on
+    this library's kernels."""
+    if imgs.dim() != 5:
+        raise ValueError(f"diner_amd: depth_from_images expects imgs (B,NV,3,H,W), got {tuple(imgs.shape)}")
+    if hasattr(feature, "forward_views"):
+        features = feature.forward_views(imgs)
+    else:
+        features = [feature(img) for img in torch.unbind(imgs, 1)]
+    features = fmt_with_pathway(features)
+    kwargs.setdefault("image_hw", tuple(int(n) for n in imgs.shape[-2:]))
+    return coarse_to_fine(features, proj_matrices, depth_values, depthnet, cost_regularization, **kwargs)
+
+
 def to_device(model):
     """A loaded TransMVSNet -> the same model with model.DepthNet a DeviceDepthNet, model.cost_regularization a DeviceCostRegNet (one
-    shared module, or a ModuleList of one per stage, as share_cr made it) and model.FMT_with_pathway a DeviceFMTWithPathway, each carrying
-    the original's state, device and training flag.  A model without FMT_with_pathway keeps what it has."""
+    shared module, or a ModuleList of one per stage, as share_cr made it), model.FMT_with_pathway a DeviceFMTWithPathway and model.feature
+    a DeviceFeatureNet, each carrying the original's state, device and training flag.  A model without FMT_with_pathway or without
+    feature keeps what it has."""
     model.DepthNet = DeviceDepthNet.from_module(model.DepthNet)
     cr = model.cost_regularization
     if isinstance(cr, nn.ModuleList):
@@ -733,6 +990,8 @@ def to_device(model):
         model.cost_regularization = DeviceCostRegNet.from_module(cr)
     if getattr(model, "FMT_with_pathway", None) is not None:
         model.FMT_with_pathway = DeviceFMTWithPathway.from_module(model.FMT_with_pathway)
+    if getattr(model, "feature", None) is not None:
+        model.feature = DeviceFeatureNet.from_module(model.feature)
     return model
 
 

@@ -1117,11 +1117,12 @@ def _pack_conv2d(who, weight, kernels, Cin=None, transpose=False):
     return p.view(cp // CONV3X3_CIN_CHUNK, CONV3X3_CIN_CHUNK, R * R, op).permute(0, 2, 1, 3).contiguous()
 
 
-def pack_conv3x3(weight, transpose=False):
+def pack_conv3x3(weight, transpose=False, Cin=None):
     """A torch Conv2d weight (Cout,Cin,3,3) in the layout diner_conv3x3_f32 reads: [ceil(Cin / 8)][tap][8][Cout rounded up to 64], zeros
-    beyond Cin and Cout.  transpose: the weight set of the data gradient instead (taps flipped, Cin and Cout swapped).  Plain torch on
-    the weight's own device (done once at load), so it needs no HIP device."""
-    return _pack_conv2d("pack_conv3x3", weight, (3,), transpose=transpose)
+    beyond Cin and Cout.  transpose: the weight set of the data gradient instead (taps flipped, Cin and Cout swapped).  Cin: pack for that
+    many input channels (>= the weight's; the added ones are zero), for an input that encoder_input widened.  Plain torch on the weight's
+    own device (done once at load), so it needs no HIP device."""
+    return _pack_conv2d("pack_conv3x3", weight, (3,), Cin=Cin, transpose=transpose)
 
 
 def _check_nhwc(who, name, t, shape=None, min_hw=1):
@@ -1710,6 +1711,154 @@ def fpn_merge(top, weight, lateral, out=None):
         reduced = torch.empty(N, H, W, Clat, dtype=torch.float32, device=top.device)
         y = out if out is not None else torch.empty_like(lateral)
         _lib.check(lib.diner_fpn_merge_f32(_ptr(top), _ptr(weight), _ptr(lateral), _ptr(reduced), _ptr(y), N, H, W, Ctop, Clat, _stream()))
+    return y
+
+
+# ---- the depth estimator's FeatureNet (deform.hip, conv2d.hip) ----------------------------------------------------------------------------
+DEFORM_MAX_CIN = 64              # DINER_DEFORM_MAX_CIN
+DEFORM_TAPS = 9
+
+
+def deform_col_tile(Cout):
+    """The column tile diner_deform_conv3x3_f32 pads Cout to: 16 up to 16 output channels, else 32."""
+    return 16 if int(Cout) <= 16 else 32
+
+
+def pack_deform_conv3x3(weight):
+    """A DCN weight (Cout,Cin,3,3) in the layout diner_deform_conv3x3_f32 reads: [ceil(Cout / BN)][tap ky 3 + kx][Cin][BN] with BN =
+    deform_col_tile(Cout), zeros beyond Cout.  Plain torch on the weight's own device, so it needs no HIP device."""
+    if not torch.is_tensor(weight) or weight.dim() != 4 or tuple(weight.shape[2:]) != (3, 3) or weight.shape[0] < 1:
+        raise ValueError(f"diner_amd: pack_deform_conv3x3 expects a (Cout,Cin,3,3) weight, got "
+                         f"{tuple(weight.shape) if torch.is_tensor(weight) else type(weight).__name__}")
+    if weight.dtype != torch.float32:
+        raise ValueError(f"diner_amd: pack_deform_conv3x3 expects float32, got {weight.dtype}")
+    Cout, Cin = int(weight.shape[0]), int(weight.shape[1])
+    if Cin < 8 or Cin > DEFORM_MAX_CIN or Cin % 8:
+        raise ValueError(f"diner_amd: pack_deform_conv3x3 expects Cin a multiple of 8 in [8, {DEFORM_MAX_CIN}], got {Cin}")
+    bn = deform_col_tile(Cout)
+    tiles = -(-Cout // bn)
+    p = weight.new_zeros(tiles * bn, Cin, DEFORM_TAPS)
+    p[:Cout] = weight.detach().reshape(Cout, Cin, DEFORM_TAPS)
+    return p.view(tiles, bn, Cin, DEFORM_TAPS).permute(0, 3, 2, 1).contiguous()
+
+
+def _check_bias(who, bias, Cout):
+    if bias is not None and not (torch.is_tensor(bias) and bias.dtype == torch.float32 and bias.dim() == 1 and bias.is_contiguous()
+                                 and bias.shape[0] >= Cout):
+        raise ValueError(f"diner_amd: {who} expects bias float32 with at least Cout = {Cout} elements")
+
+
+def _check_deform_conv3x3_args(x, offmask, wpack, bias, Cout, out=None):
+    """The argument checks of deform_conv3x3 that need no device -> (N, H, W, Cin)."""
+    Cout = int(Cout)
+    N, H, W, Cin = _check_nhwc("deform_conv3x3", "x", x)
+    if Cin < 8 or Cin > DEFORM_MAX_CIN or Cin % 8:
+        raise ValueError(f"diner_amd: deform_conv3x3 expects Cin a multiple of 8 in [8, {DEFORM_MAX_CIN}], got {Cin}")
+    if Cout < 1:
+        raise ValueError(f"diner_amd: deform_conv3x3 expects Cout >= 1, got {Cout}")
+    if max(H, W) > 1 << 14 or N > 65535:
+        raise ValueError(f"diner_amd: deform_conv3x3 expects H, W <= 2^14 and at most 65535 images, got {N} x {H} x {W}")
+    _check_nhwc("deform_conv3x3", "offmask", offmask, (N, H, W, 3 * DEFORM_TAPS))
+    bn = deform_col_tile(Cout)
+    want = (-(-Cout // bn), DEFORM_TAPS, Cin, bn)
+    if not torch.is_tensor(wpack) or wpack.dtype != torch.float32 or tuple(wpack.shape) != want or not wpack.is_contiguous():
+        raise ValueError(f"diner_amd: deform_conv3x3 expects wpack float32 {want} (pack_deform_conv3x3) for Cin {Cin}, Cout {Cout}, got "
+                         f"{tuple(wpack.shape) if torch.is_tensor(wpack) else type(wpack).__name__}")
+    _check_bias("deform_conv3x3", bias, Cout)
+    if out is not None:
+        _check_nhwc("deform_conv3x3", "out", out, (N, H, W, Cout))
+        if out.data_ptr() in (x.data_ptr(), offmask.data_ptr()):
+            raise ValueError("diner_amd: deform_conv3x3: out must not be x or offmask")
+    return N, H, W, Cin
+
+
+def deform_conv3x3(x, offmask, wpack, bias, Cout, relu=False, out=None):
+    """torchvision's modulated deform_conv2d, 3 x 3, stride 1, padding 1, one offset group (diner_deform_conv3x3_f32): x (N,H,W,Cin) and
+    offmask (N,H,W,27) channels-last -- the raw output of the layer's conv_offset_mask: channels 2 k, 2 k + 1 the row and column offset
+    of tap k, channel 18 + k the logit of its modulation -> (N,H,W,Cout) = bias + sum over taps and channels, then ReLU if asked.
+    wpack: pack_deform_conv3x3's layout; bias (>= Cout,) or None."""
+    N, H, W, Cin = _check_deform_conv3x3_args(x, offmask, wpack, bias, Cout, out)
+    _require_hip(x, offmask, wpack, bias, out)
+    with torch.cuda.device(x.device):
+        y = out if out is not None else torch.empty(N, H, W, int(Cout), dtype=torch.float32, device=x.device)
+        _lib.check(lib.diner_deform_conv3x3_f32(_ptr(x), _ptr(offmask), _ptr(wpack), _ptr(bias), _ptr(y), N, H, W, Cin, int(Cout),
+                                                int(bool(relu)), _stream()))
+    return y
+
+
+def pack_conv5x5(weight):
+    """A torch Conv2d weight (Cout,Cin,5,5) in the layout diner_conv5x5_s2_f32 reads: [ceil(Cin / 8)][ky 5 + kx][8][Cout rounded up to 64]."""
+    return _pack_conv2d("pack_conv5x5", weight, (5,))
+
+
+def pack_conv1x1(weight):
+    """A torch Conv2d weight (Cout,Cin,1,1) in the layout diner_conv1x1_f32 reads: [ceil(Cin / 8)][1][8][Cout rounded up to 64]."""
+    return _pack_conv2d("pack_conv1x1", weight, (1,))
+
+
+def _check_conv_fixed_args(who, x, wpack, bias, Cout, R, stride, out=None):
+    """conv5x5_s2 and conv1x1 -> (N, H, W, Cin, Ho, Wo)."""
+    Cout = int(Cout)
+    N, H, W, Cin = _check_conv2d_args(who, x, wpack, bias, Cout, R, (R,), False)
+    Ho, Wo = ((H - 1) // 2 + 1, (W - 1) // 2 + 1) if stride == 2 else (H, W)
+    if out is not None:
+        _check_nhwc(who, "out", out, (N, Ho, Wo, Cout))
+    return N, H, W, Cin, Ho, Wo
+
+
+def conv5x5_s2(x, wpack, bias, Cout, relu=False, out=None):
+    """5 x 5 convolution, stride 2, zero padding 2 (diner_conv5x5_s2_f32): x (N,H,W,Cin) channels-last -> (N, (H - 1) // 2 + 1,
+    (W - 1) // 2 + 1, Cout) = conv + bias, then ReLU if asked.  wpack: pack_conv5x5's layout; bias (>= Cout,) or None."""
+    N, H, W, Cin, Ho, Wo = _check_conv_fixed_args("conv5x5", x, wpack, bias, Cout, 5, 2, out)
+    _require_hip(x, wpack, bias, out)
+    with torch.cuda.device(x.device):
+        y = out if out is not None else torch.empty(N, Ho, Wo, int(Cout), dtype=torch.float32, device=x.device)
+        _lib.check(lib.diner_conv5x5_s2_f32(_ptr(x), _ptr(wpack), _ptr(bias), _ptr(y), N, H, W, Cin, int(Cout), int(bool(relu)), _stream()))
+    return y
+
+
+def conv1x1(x, wpack, bias, Cout, relu=False, out=None):
+    """1 x 1 convolution (diner_conv1x1_f32): x (N,H,W,Cin) channels-last -> (N,H,W,Cout) = conv + bias, then ReLU if asked.  wpack:
+    pack_conv1x1's layout; bias (>= Cout,) or None.  out must not be x."""
+    N, H, W, Cin, Ho, Wo = _check_conv_fixed_args("conv1x1", x, wpack, bias, Cout, 1, 1, out)
+    if out is not None and out.data_ptr() == x.data_ptr():
+        raise ValueError("diner_amd: conv1x1: out must not be x")
+    _require_hip(x, wpack, bias, out)
+    with torch.cuda.device(x.device):
+        y = out if out is not None else torch.empty(N, H, W, int(Cout), dtype=torch.float32, device=x.device)
+        _lib.check(lib.diner_conv1x1_f32(_ptr(x), _ptr(wpack), _ptr(bias), _ptr(y), N, H, W, Cin, int(Cout), int(bool(relu)), _stream()))
+    return y
+
+
+def _check_fpn_lateral_args(top, lateral, weight, bias, out=None):
+    """-> (N, H, W, Ctop, Clat) with H, W the fine size."""
+    N, H, W, Clat = _check_nhwc("fpn_lateral", "lateral", lateral)
+    if H % 2 or W % 2 or max(H, W) > 1 << 15:
+        raise ValueError(f"diner_amd: fpn_lateral expects a lateral of even H, W <= 2^15, got {H}, {W}")
+    if not torch.is_tensor(weight) or weight.dtype != torch.float32 or not weight.is_contiguous() or weight.dim() not in (2, 4) \
+            or weight.shape[1] != Clat or weight.numel() != weight.shape[0] * Clat:
+        raise ValueError(f"diner_amd: fpn_lateral expects the 1 x 1 weight float32 (Ctop,{Clat}) or (Ctop,{Clat},1,1), contiguous, got "
+                         f"{tuple(weight.shape) if torch.is_tensor(weight) else type(weight).__name__}")
+    Ctop = int(weight.shape[0])
+    if Ctop > FPN_MAX_CHANNELS or Clat > FPN_MAX_CHANNELS or Ctop < 4 or Ctop % 4:
+        raise ValueError(f"diner_amd: fpn_lateral expects Clat <= {FPN_MAX_CHANNELS} and Ctop a multiple of 4 up to it, got {Clat} -> {Ctop}")
+    _check_nhwc("fpn_lateral", "top", top, (N, H // 2, W // 2, Ctop))
+    _check_bias("fpn_lateral", bias, Ctop)
+    if out is not None:
+        _check_nhwc("fpn_lateral", "out", out, (N, H, W, Ctop))
+        if out.data_ptr() in (top.data_ptr(), lateral.data_ptr()):
+            raise ValueError("diner_amd: fpn_lateral: out must not be top or lateral")
+    return N, H, W, Ctop, Clat
+
+
+def fpn_lateral(top, lateral, weight, bias=None, out=None):
+    """FeatureNet's merge on channels-last maps (diner_fpn_lateral_f32): top (N,H/2,W/2,Ctop), lateral (N,H,W,Clat), weight the 1 x 1
+    convolution (Ctop,Clat[,1,1]) with bias (Ctop,) -> (N,H,W,Ctop) = nearest2x(top) + conv1x1(lateral), one launch."""
+    N, H, W, Ctop, Clat = _check_fpn_lateral_args(top, lateral, weight, bias, out)
+    _require_hip(top, lateral, weight, bias, out)
+    with torch.cuda.device(top.device):
+        y = out if out is not None else torch.empty(N, H, W, Ctop, dtype=torch.float32, device=top.device)
+        _lib.check(lib.diner_fpn_lateral_f32(_ptr(top), _ptr(lateral), _ptr(weight), _ptr(bias), _ptr(y), N, H, W, Ctop, Clat, _stream()))
     return y
 
 

@@ -1016,6 +1016,46 @@ int diner_fmt_layer_f32(const float* x, const float* pack, const float* state, f
 int diner_fpn_merge_f32(const float* top, const float* w, const float* lateral, float* reduced, float* y, int N, int H, int W, int Ctop,
                         int Clat, void* stream);
 
+/* ---- the depth estimator's FeatureNet (csrc/deform.hip, csrc/conv2d.hip) ---------------------------------------------------------------
+ * What TransMVSNet's FeatureNet (models/module.py:343-421) needs beyond diner_conv3x3_f32 and diner_encoder_input_f32 (pad 0, C 4).
+ * Activations are channels-last fp32 (N,H,W,C); every function refuses bad arguments with DINER_E_INVALID and a message before any
+ * device work; every output is computed in an order the shape alone fixes (no atomics), a tile never crosses images, so an image's
+ * values are the same bits at any batch position.  A BatchNorm that follows a layer is folded into its weights and bias by the caller.
+ *
+ * diner_deform_conv3x3_f32: torchvision's modulated deform_conv2d, 3 x 3, stride 1, padding 1, dilation 1, one offset group:
+ *   offmask (N,H,W,27), the raw output of the layer's conv_offset_mask: for tap k = 3 ky + kx, dy_k = offmask[2 k], dx_k = offmask[2 k + 1],
+ *   m_k = sigmoid(offmask[18 + k]);
+ *     y[n,h,w,o] = bias[o] + sum_k sum_c w[o,c,ky,kx] m_k S(x[n,:,:,c], h - 1 + ky + dy_k, w - 1 + kx + dx_k)   [then ReLU if relu]
+ *   S(., py, px) is torchvision's bilinear_interpolate in fp32: 0 when py <= -1, py >= H, px <= -1 or px >= W (or either is NaN);
+ *   otherwise y0 = floor(py), ly = py - y0, hy = 1 - ly (columns likewise), a corner outside the image contributes 0, and the value is
+ *   ((hy hx v00 + hy lx v01) + ly hx v10) + ly lx v11, every product and sum rounded.  Offsets may be any float: +-1e30, +-inf and NaN
+ *   are plain "outside" and no address is formed from them.  The sampled matrix never reaches global memory.
+ *   K order of an output: the bias, then taps k = 0 .. 8 ascending, within a tap channels c = 0 .. Cin - 1 ascending, one fmaf chain
+ *   (v_mfma_f32_16x16x4_f32).  Cin a multiple of 8 in [8, DINER_DEFORM_MAX_CIN]; any Cout >= 1; H, W <= 2^14; N <= 65535.
+ *   wpack: diner_deform_conv3x3_pack_floats(Cin, Cout) floats (0 for arguments the function refuses), 16-byte aligned,
+ *   [ceil(Cout / BN)][k][Cin][BN] with BN = 16 for Cout <= 16, else 32; element [t][k][c][j] = w[BN t + j][c][k / 3][k % 3], zeros beyond
+ *   Cout.  bias: Cout floats or NULL.  x 16-byte aligned; y must not be x or offmask.
+ * diner_conv5x5_s2_f32 / diner_conv1x1_f32: y = conv(x, w) + bias [then ReLU], 5 x 5 stride 2 zero padding 2 (Ho = (H - 1) / 2 + 1) and
+ *   1 x 1 stride 1, any Cin, Cout >= 1, N <= 65535, on diner_conv3x3_f32's kernel and in its K order (chunk of 8 channels, kernel row,
+ *   kernel column, channel).  wpack: diner_conv5x5_s2_pack_floats / diner_conv1x1_pack_floats floats, 16-byte aligned,
+ *   [ceil(Cin / 8)][ky R + kx][8][Cout rounded up to 64].  bias: Cout floats or NULL.  (diner_conv2d_s2_f32 itself keeps refusing R = 5.)
+ * diner_fpn_lateral_f32: y (N,H,W,Ctop) = top[n, h / 2, w / 2, :] + (bias + w lateral[n,h,w,:]): the pyramid's nearest 2 x upsampling
+ *   of top (N,H/2,W/2,Ctop) plus the 1 x 1 convolution w (Ctop,Clat), bias (Ctop or NULL) of lateral (N,H,W,Clat), one launch and no
+ *   intermediate; the convolution is one fmaf chain from the bias, k ascending, the coarse pixel is added last.  H, W even; Ctop a
+ *   multiple of 4 up to DINER_FPN_MAX_CHANNELS, Clat up to it; top and y 16-byte aligned; y must not be an input. */
+#define DINER_DEFORM_MAX_CIN 64
+size_t diner_deform_conv3x3_pack_floats(int Cin, int Cout);
+int diner_deform_conv3x3_f32(const float* x, const float* offmask, const float* wpack, const float* bias, float* y, int N, int H, int W,
+                             int Cin, int Cout, int relu, void* stream);
+size_t diner_conv5x5_s2_pack_floats(int Cin, int Cout);
+int diner_conv5x5_s2_f32(const float* x, const float* wpack, const float* bias, float* y, int N, int H, int W, int Cin, int Cout, int relu,
+                         void* stream);
+size_t diner_conv1x1_pack_floats(int Cin, int Cout);
+int diner_conv1x1_f32(const float* x, const float* wpack, const float* bias, float* y, int N, int H, int W, int Cin, int Cout, int relu,
+                      void* stream);
+int diner_fpn_lateral_f32(const float* top, const float* lateral, const float* w, const float* bias, float* y, int N, int H, int W, int Ctop,
+                          int Clat, void* stream);
+
 /* ---- measurement aid (bench.py): per-kernel durations of the two field kernels ------------------
  * With profiling enabled every field call brackets k_field_pre / k_field_post with HIP events on the
  * launch stream; diner_profile_collect waits for them, returns the summed durations (ms), the number
