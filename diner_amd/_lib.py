@@ -269,6 +269,16 @@ SIGNATURES = {
                                     C.c_void_p]),
     "diner_fpn_lateral_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                         C.c_int, C.c_void_p]),
+    "diner_mvs_loss_partial_doubles": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "diner_mvs_stage_loss_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.POINTER(C.c_double), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                           C.c_int, C.c_int, C.c_void_p]),
+    "diner_mvs_loss_finish_f32": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_void_p]),
+    "diner_mvs_stage_loss_grad_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double,
+                                                C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "diner_depth_scores_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_int, C.c_int,
+                                         C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 ABI_VERSION = 6          # DINER_ABI_VERSION of include/diner_hip.h
@@ -303,6 +313,7 @@ E_INVALID, E_UNSUPPORTED, E_HIP = -1, -2, -3            # DINER_E_* of include/d
 MAX_VIEWS = 16                                          # DINER_MAX_VIEWS: source views a scene may have
 OPTIM_CHUNK = 4096                                      # DINER_OPTIM_CHUNK: elements of one tensor per chunk of the optimiser's table
 MVS_PIXELWISE_FLOATS, MVS_MAX_DEPTHS, MVS_MAX_CHANNELS = 177, 256, 64   # DINER_MVS_*
+MVS_LOSS_SLOTS, MVS_LOSS_MAX_THRESHOLDS, MVS_LOSS_SCALARS, DEPTH_SCORES = 16, 8, 13, 10       # DINER_MVS_LOSS_*, DINER_DEPTH_SCORES
 ADAM_DECOUPLED_WD, ADAM_CLIP, ADAM_SKIP_NONFINITE, ADAM_ZERO_GRADS = 1, 2, 4, 8       # DINER_ADAM_*
 
 

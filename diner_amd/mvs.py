@@ -10,7 +10,7 @@ on the kernels of csrc/fmt.hip (DeviceFMT, DeviceFMTWithPathway), and the featur
 Every thin function takes the reference's tensor layouts (NCHW).  On HIP tensors it runs the kernels; on CPU tensors it runs a torch
 restatement of the same mathematics with the reference's own operations in the reference's order (`*_torch`, any floating dtype),
 which is the host oracle of the tests and the baseline of tools/time_mvs.py.  Inference only: nothing here has a backward pass;
-DeviceDepthNet uses torch operations whenever gradients are enabled or the module is in training mode."""
+DeviceDepthNet uses torch operations whenever gradients are enabled or the module is in training mode (fine-tuning: diner_amd.estimator)."""
 import numpy as np
 import torch
 import torch.nn as nn
@@ -232,11 +232,18 @@ class DeviceDepthNet(nn.Module):
     """A replacement for the reference's DepthNet: the same state-dict keys (pixel_wise_net.*), the same forward() signature and results.
     On HIP tensors, in eval mode and with gradients disabled it runs the kernels; otherwise torch operations (which are
     differentiable, so fine-tuning keeps working).  `model.DepthNet = DeviceDepthNet.from_module(model.DepthNet)` switches a loaded
-    TransMVSNet over."""
+    TransMVSNet over.
+
+    fused_readout (default False: every route is as it was, bit for bit).  When True and the module is on its torch route with gradients
+    enabled and float32 HIP tensors, it does not form the probability volume: depth and confidence come from the read-out kernel on the
+    detached cost, and the stage dict carries "cost" (the regulariser's output plus prob_volume_init, with its graph) and "prob_volume":
+    None -- what diner_amd.estimator's losses take.  The kernel's winner may differ from argmax(prob_volume) of the torch route on an exact
+    tie that exp creates (two planes whose probabilities round to the same float32 in one chain and not in the other), and nowhere else."""
 
     def __init__(self):
         super().__init__()
         self.pixel_wise_net = _PixelwiseNet()
+        self.fused_readout = False
         self._folded, self._folded_key = None, None
 
     @classmethod
@@ -272,7 +279,15 @@ class DeviceDepthNet(nn.Module):
             # the view weights from the module itself: differentiable down to its parameters, and in training mode on BatchNorm's batch
             # statistics (which it then also updates), like the reference
             similarity, weights = cost_volume_torch(features, proj_matrices, depth_values, None if given else self.pixel_wise_net, view_weights)
-            depth, conf, prob = select_depth_torch(cost_regularization(similarity).squeeze(1), depth_values, prob_volume_init)
+            cost = cost_regularization(similarity).squeeze(1)
+            if (self.fused_readout and torch.is_grad_enabled() and cost.is_cuda and cost.dtype == torch.float32
+                    and depth_values.dtype == torch.float32 and (prob_volume_init is None or prob_volume_init.dtype == torch.float32)):
+                # no probability volume: the read-out kernel on the detached cost, and the cost itself (with its graph) for the loss
+                depth, conf, _ = select_depth(cost, depth_values, prob_volume_init, return_prob=False)
+                out = {"depth": depth, "photometric_confidence": conf, "prob_volume": None, "depth_values": depth_values,
+                       "cost": cost if prob_volume_init is None else cost + prob_volume_init}
+                return out if given else (out, weights.detach())
+            depth, conf, prob = select_depth_torch(cost, depth_values, prob_volume_init)
         out = {"depth": depth, "photometric_confidence": conf.detach(), "prob_volume": prob, "depth_values": depth_values}
         return out if given else (out, weights.detach())
 

@@ -2090,3 +2090,107 @@ _want = os.environ.get("DINER_AMD_PRECISION", "f16x3").lower()
 if _want not in PRECISION_NAMES:
     raise ValueError(f"DINER_AMD_PRECISION={_want!r}: expected one of {sorted(PRECISION_NAMES)}")
 set_precision(_want)
+
+
+# ---- the depth estimator's fine-tuning objective and depth scores (csrc/mvsloss.hip) -------------------------------------------------------
+def _check_mvs_loss_args(vol, hypotheses, gt, mask, init=None):
+    """The argument checks of the stage loss that need no device -> (B, D, H, W)."""
+    if vol.dim() != 4 or tuple(hypotheses.shape) != tuple(vol.shape) or (init is not None and tuple(init.shape) != tuple(vol.shape)):
+        raise ValueError(f"diner_amd: mvs_stage_loss expects the volume, hypotheses [and init] of one shape (B,D,H,W), got {tuple(vol.shape)}, "
+                         f"{tuple(hypotheses.shape)}" + ("" if init is None else f", {tuple(init.shape)}"))
+    B, D, H, W = (int(v) for v in vol.shape)
+    if tuple(gt.shape) != (B, H, W) or tuple(mask.shape) != (B, H, W):
+        raise ValueError(f"diner_amd: mvs_stage_loss expects gt and mask ({B},{H},{W}), got {tuple(gt.shape)}, {tuple(mask.shape)}")
+    if min(B, D, H, W) < 1 or B * D * H * W >= 2 ** 31:
+        raise ValueError(f"diner_amd: mvs_stage_loss needs B, D, H, W >= 1 and B D H W < 2^31, got {B} x {D} x {H} x {W}")
+    return B, D, H, W
+
+
+def _thresholds(thresholds):
+    t = [float(v) for v in thresholds]
+    if len(t) > _lib.MVS_LOSS_MAX_THRESHOLDS:
+        raise ValueError(f"diner_amd: at most {_lib.MVS_LOSS_MAX_THRESHOLDS} thresholds, got {len(t)}")
+    return (C.c_double * max(len(t), 1))(*t), len(t)
+
+
+def mvs_stage_loss(vol, hypotheses, gt, mask, init=None, from_prob=False, unit=None, thresholds=(), weight=1.0, record=True):
+    """diner_mvs_stage_loss_f32 + diner_mvs_loss_finish_f32: one stage of the estimator's loss.  vol (B,D,H,W): the regularised cost
+    [+ init], or with from_prob a probability volume; hypotheses (B,D,H,W); gt, mask (B,H,W) float32, valid where mask > 0.5; unit: (B,)
+    float64 error unit of the scores or None; thresholds: host numbers.
+    -> dict: scalars (13 float32: weight 2 entropy, 2 entropy, depth_loss, mean |err|, mean |err| / unit, shares under the thresholds),
+    depth, confidence (B,H,W), record (B,H,W,4) or None, factors (B,) float64, sums (B,16) float64."""
+    B, D, H, W = _check_mvs_loss_args(vol, hypotheses, gt, mask, init)
+    if from_prob and init is not None:
+        raise ValueError("diner_amd: mvs_stage_loss: init belongs to the cost, not to a probability volume")
+    _require_hip(vol, hypotheses, gt, mask, init)
+    if unit is not None and (not unit.is_cuda or unit.dtype != torch.float64 or tuple(unit.shape) != (B,)):
+        raise ValueError(f"diner_amd: mvs_stage_loss expects unit as a ({B},) float64 HIP tensor")
+    vol, hypotheses, gt, mask = vol.contiguous(), hypotheses.contiguous(), gt.contiguous(), mask.contiguous()
+    init = init.contiguous() if init is not None else None
+    unit = unit.contiguous() if unit is not None else None
+    thr, n_thr = _thresholds(thresholds if unit is not None else ())
+    dev = vol.device
+    depth = torch.empty(B, H, W, device=dev, dtype=torch.float32)
+    conf = torch.empty_like(depth)
+    rec = torch.empty(B, H, W, 4, device=dev, dtype=torch.float32) if record else None
+    part = torch.empty(int(lib.diner_mvs_loss_partial_doubles(B, H, W)), device=dev, dtype=torch.float64)
+    scalars = torch.empty(_lib.MVS_LOSS_SCALARS, device=dev, dtype=torch.float32)
+    factors = torch.empty(B, device=dev, dtype=torch.float64)
+    sums = torch.empty(B, _lib.MVS_LOSS_SLOTS, device=dev, dtype=torch.float64)
+    with torch.cuda.device(dev):
+        _lib.check(lib.diner_mvs_stage_loss_f32(_ptr(None if from_prob else vol), _ptr(init), _ptr(vol if from_prob else None), _ptr(hypotheses),
+                                                _ptr(gt), _ptr(mask), _ptr(unit), thr, n_thr, _ptr(depth), _ptr(conf), _ptr(rec), _ptr(part),
+                                                B, D, H, W, _stream()))
+        _lib.check(lib.diner_mvs_loss_finish_f32(_ptr(part), B, H, W, n_thr, float(weight), _ptr(scalars), _ptr(factors), _ptr(sums), _stream()))
+    return dict(scalars=scalars, depth=depth, confidence=conf, record=rec, factors=factors, sums=sums)
+
+
+def mvs_stage_loss_grad(vol, init, from_prob, mask, record, factors, upstream, weight=1.0):
+    """diner_mvs_stage_loss_grad_f32: d(upstream weight 2 entropy) / d(vol) as a dense (B,D,H,W) volume, one launch.  vol, init, mask, record
+    and factors as mvs_stage_loss took and returned them; upstream: a 0-dim float32 HIP tensor, never read back."""
+    B, D, H, W = (int(v) for v in vol.shape)
+    if min(B, D, H, W) < 1 or B * D * H * W >= 2 ** 31:
+        raise ValueError(f"diner_amd: mvs_stage_loss_grad needs B, D, H, W >= 1 and B D H W < 2^31, got {B} x {D} x {H} x {W}")
+    if tuple(mask.shape) != (B, H, W) or tuple(record.shape) != (B, H, W, 4) or tuple(factors.shape) != (B,) or upstream.numel() != 1:
+        raise ValueError("diner_amd: mvs_stage_loss_grad: mask, record, factors or upstream do not belong to this volume")
+    _require_hip(vol, init, mask, record, upstream)
+    if not factors.is_cuda or factors.dtype != torch.float64:
+        raise TypeError("diner_amd: mvs_stage_loss_grad expects the factors mvs_stage_loss returned (float64, on the device)")
+    vol, mask, record, factors, upstream = vol.contiguous(), mask.contiguous(), record.contiguous(), factors.contiguous(), upstream.contiguous()
+    init = init.contiguous() if init is not None else None
+    grad = torch.empty(B, D, H, W, device=vol.device, dtype=torch.float32)
+    with torch.cuda.device(vol.device):
+        _lib.check(lib.diner_mvs_stage_loss_grad_f32(_ptr(vol), _ptr(init), 1 if from_prob else 0, _ptr(mask), _ptr(record), _ptr(factors),
+                                                     _ptr(upstream), float(weight), _ptr(grad), B, D, H, W, _stream()))
+    return grad
+
+
+def _check_depth_scores_args(est, gt, mask, thresholds):
+    if est.dim() != 3 or tuple(gt.shape) != tuple(est.shape) or tuple(mask.shape) != tuple(est.shape):
+        raise ValueError(f"diner_amd: depth_scores expects est, gt and mask of one shape (B,H,W), got {tuple(est.shape)}, {tuple(gt.shape)}, "
+                         f"{tuple(mask.shape)}")
+    B, H, W = (int(v) for v in est.shape)
+    if min(B, H, W) < 1 or B * H * W >= 2 ** 31:
+        raise ValueError(f"diner_amd: depth_scores needs B, H, W >= 1 and B H W < 2^31, got {B} x {H} x {W}")
+    if len(thresholds) > _lib.MVS_LOSS_MAX_THRESHOLDS:
+        raise ValueError(f"diner_amd: at most {_lib.MVS_LOSS_MAX_THRESHOLDS} thresholds, got {len(thresholds)}")
+    return B, H, W
+
+
+def depth_scores(est, gt, mask, thresholds=(), band=None):
+    """diner_depth_scores_f32: est, gt, mask (B,H,W) float32 (valid where mask > 0.5) -> (per_image (B,10), batch (10,)) float32:
+    [0] mean |est - gt|, [1] the same restricted to the errors inside band = (lo, hi) (0 when none is; 0 without a band), [2 + t] the share
+    of errors above thresholds[t]; batch is the mean of the per-image values."""
+    B, H, W = _check_depth_scores_args(est, gt, mask, thresholds)
+    _require_hip(est, gt, mask)
+    est, gt, mask = est.contiguous(), gt.contiguous(), mask.contiguous()
+    thr, n_thr = _thresholds(thresholds)
+    dev = est.device
+    part = torch.empty(int(lib.diner_mvs_loss_partial_doubles(B, H, W)), device=dev, dtype=torch.float64)
+    per_image = torch.empty(B, _lib.DEPTH_SCORES, device=dev, dtype=torch.float32)
+    batch = torch.empty(_lib.DEPTH_SCORES, device=dev, dtype=torch.float32)
+    lo, hi = (float(band[0]), float(band[1])) if band is not None else (0.0, 0.0)
+    with torch.cuda.device(dev):
+        _lib.check(lib.diner_depth_scores_f32(_ptr(est), _ptr(gt), _ptr(mask), B, H, W, thr, n_thr, 0 if band is None else 1, lo, hi, _ptr(part),
+                                              _ptr(per_image), _ptr(batch), _stream()))
+    return per_image, batch

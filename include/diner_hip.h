@@ -1056,6 +1056,55 @@ int diner_conv1x1_f32(const float* x, const float* wpack, const float* bias, flo
 int diner_fpn_lateral_f32(const float* top, const float* lateral, const float* w, const float* bias, float* y, int N, int H, int W, int Ctop,
                           int Clat, void* stream);
 
+/* ---- the depth estimator's fine-tuning objective and depth scores ------------------------------------------------------------------------
+ * New symbols without an ABI bump (mvsloss.hip): TransMVSNet's entropy_loss / focal_loss_bld / trans_mvsnet_loss (models/module.py:490-587)
+ * with the gradient, and Thres_metrics / AbsDepthError_metrics (utils.py:240-274).  No allocation, enqueue-only, no host read-back, no
+ * atomics.  A workgroup (256 pixels) belongs to one image and writes DINER_MVS_LOSS_SLOTS doubles to its own slot of `partials`
+ * (diner_mvs_loss_partial_doubles(B, H, W) doubles); an image's slots are added in an order the shape alone fixes, so two runs give the
+ * same bits and an image's sums, depth and gradient do not depend on its place in the batch (the 1 / B of the gradient is the same number
+ * everywhere).  Limits, refused with DINER_E_INVALID before any device work: B, D, H, W >= 1 and B D H W < 2^31.
+ *
+ * diner_mvs_stage_loss_f32: one stage's forward.  Exactly one of cost (B,D,H,W; init, the reference's prob_volume_init, is added first
+ *   when non-NULL) and prob (B,D,H,W, already a probability volume) is non-NULL.  hypotheses (B,D,H,W), gt (B,H,W), mask (B,H,W) float,
+ *   valid where > 0.5.  Per pixel, one thread, diner_mvs_select_depth_f32's operation chain: prob = exp(log_softmax(cost [+ init]));
+ *   g = the first index of min_d |hyp_d - gt| in fp32, 0 where the mask is off; ce = -logf(prob[g] + 1e-6f); depth (B,H,W) =
+ *   hyp[first argmax prob] and confidence (B,H,W) = max prob (the bits of diner_mvs_select_depth_f32); err = |depth - gt| and
+ *   smooth_l1(err), beta 1, in double.  record (B,H,W,4 floats, 16-byte aligned) when non-NULL: g (int bits), prob[g], the softmax's
+ *   maximum and log-sum -- what the gradient needs.  Partial sums per workgroup: valid, sum ce, sum smooth-L1, sum err, and, when
+ *   unit (B doubles: the scores' error unit per image, the reference's depth_interval 192 / 128) is non-NULL, sum err / unit and the counts
+ *   of err / unit < thresholds[t] (n_thresholds <= DINER_MVS_LOSS_MAX_THRESHOLDS host doubles).  A pixel whose mask is off adds exactly
+ *   nothing, whatever gt holds there (NaN, inf).
+ * diner_mvs_loss_finish_f32: one wave adds the per-image sums -> scalars (DINER_MVS_LOSS_SCALARS floats, each a double rounded once):
+ *   [0] weight 2 entropy, [1] 2 entropy with entropy = mean_b(sum_b ce / v_b), v_b = float32(valid_b) + 1e-6 rounded to float32 as the
+ *   reference's valid_pixel_num is (an image without a valid pixel adds 0),
+ *   [2] depth_loss = sum smooth-L1 / sum valid over the batch (NaN when nothing is valid), [3] sum err / sum valid, [4] sum (err / unit) /
+ *   sum valid, [5 + t] the share of valid pixels with err / unit < thresholds[t]; factors (B doubles) = 1 / (B v_b);
+ *   sums (B, DINER_MVS_LOSS_SLOTS doubles): the per-image sums in the slot order above, zeros beyond.
+ * diner_mvs_stage_loss_grad_f32: grad (B,D,H,W), every element written, = d(upstream weight 2 entropy) / d(cost) -- with
+ *   G = -upstream weight 2 factors[b] / (p_g + 1e-6), grad_j = G p_g ((j == g) - p_j), p_j recomputed from the record's maximum and
+ *   log-sum -- or, with from_prob, / d(prob): G at plane g, zero elsewhere (cost may then be NULL).  upstream: one float on the device.
+ *   Pixels whose mask is off get zeros.
+ * diner_depth_scores_f32: est, gt, mask (B,H,W) -> per_image (B, DINER_DEPTH_SCORES floats): over the image's valid pixels the mean of
+ *   err = |est - gt| (NaN without one), the mean of the errs inside [band_lo, band_hi] when has_band (0 when none is inside), and per
+ *   threshold t the share of errs > thresholds[t]; batch (DINER_DEPTH_SCORES floats): the mean of the per-image values, images in order,
+ *   as the reference's compute_metrics_for_each_image.  The same double sums; partials as above. */
+#define DINER_MVS_LOSS_SLOTS 16
+#define DINER_MVS_LOSS_MAX_THRESHOLDS 8
+#define DINER_MVS_LOSS_SCALARS 13
+#define DINER_DEPTH_SCORES 10
+size_t diner_mvs_loss_partial_doubles(int B, int H, int W);
+int diner_mvs_stage_loss_f32(const float* cost, const float* init, const float* prob, const float* hypotheses, const float* gt,
+                             const float* mask, const double* unit, const double* thresholds, int n_thresholds, float* depth,
+                             float* confidence, float* record, double* partials, int B, int D, int H, int W, void* stream);
+int diner_mvs_loss_finish_f32(const double* partials, int B, int H, int W, int n_thresholds, double weight, float* scalars, double* factors,
+                              double* sums, void* stream);
+int diner_mvs_stage_loss_grad_f32(const float* cost, const float* init, int from_prob, const float* mask, const float* record,
+                                  const double* factors, const float* upstream, double weight, float* grad, int B, int D, int H, int W,
+                                  void* stream);
+int diner_depth_scores_f32(const float* est, const float* gt, const float* mask, int B, int H, int W, const double* thresholds,
+                           int n_thresholds, int has_band, double band_lo, double band_hi, double* partials, float* per_image, float* batch,
+                           void* stream);
+
 /* ---- measurement aid (bench.py): per-kernel durations of the two field kernels ------------------
  * With profiling enabled every field call brackets k_field_pre / k_field_post with HIP events on the
  * launch stream; diner_profile_collect waits for them, returns the summed durations (ms), the number
