@@ -28,7 +28,8 @@ EXTRA_FLAGS = {
     "perceptual.hip": ["-Rpass-analysis=kernel-resource-usage"],
     "optim.hip": ["-Rpass-analysis=kernel-resource-usage"],     # k_adam and k_grad_stats must stay free of scratch
     "encoder.hip": ["-Rpass-analysis=kernel-resource-usage"],
-    "mvs.hip": ["-Rpass-analysis=kernel-resource-usage"],       # k_mvs_cost_volume<1 .. 16> must stay free of scratch
+    "mvs.hip": ["-Rpass-analysis=kernel-resource-usage"],       # k_mvs_cost_volume<1 .. 16> must stay free of scratch, and
+                                                                # k_mvs_similarity[_grad]<2 | 4 | 8>
     "costreg.hip": ["-Rpass-analysis=kernel-resource-usage"],   # k_conv3d<1 | 2> and k_deconv3d_s2 must stay free of scratch
     "fmt.hip": ["-Rpass-analysis=kernel-resource-usage"],       # k_fmt_kv and k_fmt_layer must stay free of scratch
     "deform.hip": ["-Rpass-analysis=kernel-resource-usage"],    # k_deform_conv3x3<1 | 2, 1 | 2 | 4> and k_fpn_lateral likewise
@@ -74,7 +75,7 @@ def build_variant(name, defines, verbose=False):
 def build(force=False, verbose=False):
     os.makedirs(OBJ, exist_ok=True)
     deps = [os.path.join(CSRC, "common.hpp"), os.path.join(CSRC, "field_common.hpp"), os.path.join(CSRC, "train_lin512.hpp"),
-            os.path.join(CSRC, "deform_geom.hpp"),
+            os.path.join(CSRC, "deform_geom.hpp"), os.path.join(CSRC, "mvs_geom.hpp"),
             os.path.join(CSRC, "train_lin512.hip"), os.path.join(CSRC, "train_wgrad512.hip"),      # included by train_512.hip
             os.path.join(ROOT, "include", "diner_hip.h")]
     hipcc = _hipcc()

@@ -1,6 +1,7 @@
 // The matching stage of the multi-view depth estimator (TransMVSNet's DepthNet.forward between its learned networks): the cost volume
 // of one reference view against NS source views, the winner-take-all read-out of the regularised cost, and the next stage's depth
-// hypotheses.  Inference only; layouts, limits and operation order are documented in include/diner_hip.h.
+// hypotheses; and for training the per-view similarity with its backward pass at the feature maps (k_mvs_similarity, k_mvs_similarity_grad).
+// Layouts, limits and operation order are documented in include/diner_hip.h.
 //
 // k_mvs_cost_volume never forms the warped (B,C,D,H,W) volume or a sampling grid: a thread owns (pixel, every DL-th depth), keeps the
 // reference pixel's C features in registers across depths and views, gathers the four bilinear taps of a sample as 16-byte loads from
@@ -10,6 +11,7 @@
 // by one thread only; the only exchange between threads is the maximum over a pixel's DL partial maxima.  No atomics, the order of every
 // sum is fixed by the shape alone, no tile crosses samples of the batch.
 #include "common.hpp"
+#include "mvs_geom.hpp"
 
 namespace diner {
 
@@ -286,6 +288,193 @@ __global__ void __launch_bounds__(kMvsThreads) k_mvs_hypotheses(const float* __r
   }
 }
 
+// ---- the per-view similarity and its backward pass (training: diner_amd.mvs.match_similarity / cost_volume_train) ----------------------
+// Both kernels keep k_mvs_cost_volume's structure -- a workgroup owns PB pixels of one sample, thread (p, dl) the pixel p and every DL-th
+// depth -- and take the tap geometry from mvs_taps (mvs_geom.hpp), which restates that kernel's operations in its order, so
+// k_mvs_similarity (the reference pixel's features in registers, like that kernel) writes the bits it keeps in its LDS slab.
+struct MvsSimArgs {
+  const float* ref_cl;        // (B,H,W,C)
+  const float* src_cl;        // (NS,B,H,W,C)
+  const float* hom;           // (B,NS,12)
+  const float* depth;         // (B,D,H,W)
+  float* sim;                 // (B,NS,D,H,W)
+  int B, NS, D, H, W, PB, blocks_per_sample;
+};
+
+template <int C4>
+__device__ __forceinline__ float tap_dot_at(const float4* __restrict__ map, int idx, const float4 (&rf)[C4]) {
+  const float4* t = map + (size_t)idx * C4;
+  float a = 0.0f;
+#pragma unroll
+  for (int c = 0; c < C4; ++c) {
+    const float4 f = t[c];
+    a = __fmaf_rn(f.x, rf[c].x, a);
+    a = __fmaf_rn(f.y, rf[c].y, a);
+    a = __fmaf_rn(f.z, rf[c].z, a);
+    a = __fmaf_rn(f.w, rf[c].w, a);
+  }
+  return a;
+}
+
+template <int C4>
+__global__ void __launch_bounds__(kMvsThreads) k_mvs_similarity(MvsSimArgs a) {
+  const int PB = a.PB, DL = kMvsThreads / PB, D = a.D, H = a.H, W = a.W;
+  const int tid = threadIdx.x;
+  const int p = tid % PB, dl = tid / PB;
+  const int b = blockIdx.x / a.blocks_per_sample;
+  const int pix = (blockIdx.x - b * a.blocks_per_sample) * PB + p;
+  const int HW = H * W;
+  const bool live = pix < HW;
+  const int pc = live ? pix : HW - 1;            // dead lanes compute on the last pixel and write nothing
+  const int y = pc / W, x = pc - y * W;
+  float4 rf[C4];
+  {
+    const float4* r = reinterpret_cast<const float4*>(a.ref_cl) + ((size_t)b * HW + pc) * C4;
+#pragma unroll
+    for (int c = 0; c < C4; ++c) rf[c] = r[c];
+  }
+  const float fc = (float)(4 * C4);
+  const float* dep = a.depth + (size_t)b * D * HW + pc;
+  for (int v = 0; v < a.NS; ++v) {
+    const float* hm = a.hom + ((size_t)b * a.NS + v) * 12;
+    const float4* map = reinterpret_cast<const float4*>(a.src_cl) + ((size_t)v * a.B + b) * HW * C4;
+    float* o = a.sim + ((size_t)b * a.NS + v) * D * HW + pc;
+    for (int d = dl; d < D; d += DL) {
+      const MvsTaps t = mvs_taps(hm, x, y, dep[(size_t)d * HW], H, W);
+      const float t00 = tap_dot_at<C4>(map, t.idx[0], rf), t01 = tap_dot_at<C4>(map, t.idx[1], rf);
+      const float t10 = tap_dot_at<C4>(map, t.idx[2], rf), t11 = tap_dot_at<C4>(map, t.idx[3], rf);
+      float s = __fmul_rn(t.wt[0], t00);
+      s = __fmaf_rn(t.wt[1], t01, s);
+      s = __fmaf_rn(t.wt[2], t10, s);
+      s = __fmaf_rn(t.wt[3], t11, s);
+      s = s / fc;
+      if (live) o[(size_t)d * HW] = s;
+    }
+  }
+}
+
+struct MvsGradArgs {
+  const float* ref_cl;        // (B,H,W,C)
+  const float* src_cl;        // (NS,B,H,W,C)
+  const float* hom;           // (B,NS,12)
+  const float* depth;         // (B,D,H,W)
+  const float* g_views;       // (B,NS,D,H,W): the upstream gradient per view, or null
+  const float* g_agg;         // (B,D,H,W): the upstream gradient of the aggregated similarity, with vw
+  const float* vw;            // (B,NS,H,W)
+  float* d_ref;               // (B,H,W,C): every element written
+  float* d_src;               // (NS,B,H,W,C): zeroed by the entry, added to atomically
+  int B, NS, D, H, W, PB, blocks_per_sample;
+};
+
+// d_ref: a thread adds G_vd bw_tap src[v,tap,:] / C over its views, depths and taps into registers; a pixel's DL partial sums meet in LDS
+// and are added by one thread in the order dl = 0, 1, ...: no atomics, the order fixed by the shape.  d_src: G_vd bw_tap ref[pixel,:] / C
+// goes to each tap's texel by float atomic adds, whose order is not fixed; a tap whose G bw is exactly 0 (outside the map, an invalid
+// sample, a masked upstream) is skipped and adds nothing to either.  The adds are issued by the wave together (sample, tap and pixel
+// travel by lane shuffles, the reference row is read again, coalesced): a lane a channel, so an instruction adds contiguous rows.
+template <int C4>
+__global__ void __launch_bounds__(kMvsThreads) k_mvs_similarity_grad(MvsGradArgs a) {
+  __shared__ float4 red[kMvsThreads];            // [DL][PB] one float4 of every thread's partial d_ref
+  const int PB = a.PB, DL = kMvsThreads / PB, D = a.D, H = a.H, W = a.W;
+  const int tid = threadIdx.x;
+  const int p = tid % PB, dl = tid / PB;
+  const int b = blockIdx.x / a.blocks_per_sample;
+  const int pix = (blockIdx.x - b * a.blocks_per_sample) * PB + p;
+  const int HW = H * W;
+  const bool live = pix < HW;
+  const int pc = live ? pix : HW - 1;            // dead lanes compute on the last pixel with a zero upstream: they add and write nothing
+  const int y = pc / W, x = pc - y * W;
+  float4 acc[C4];
+#pragma unroll
+  for (int c = 0; c < C4; ++c) acc[c] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+  const float fc = (float)(4 * C4);
+  const float* dep = a.depth + (size_t)b * D * HW + pc;
+  constexpr int C = 4 * C4, PER = 64 / C;        // rows of C floats one wave instruction covers
+  const int lane = tid & 63, se = lane / C, sc = lane - se * C;
+  const float* refb = a.ref_cl + (size_t)b * HW * C;
+  float wsum = 1e-5f;                            // the forward's sum, in its order
+  if (a.g_views == nullptr)
+    for (int v = 0; v < a.NS; ++v) wsum = __fadd_rn(wsum, a.vw[((size_t)b * a.NS + v) * HW + pc]);
+
+  for (int v = 0; v < a.NS; ++v) {
+    const float* hm = a.hom + ((size_t)b * a.NS + v) * 12;
+    const size_t moff = ((size_t)v * a.B + b) * HW * C4;
+    const float4* map = reinterpret_cast<const float4*>(a.src_cl) + moff;
+    float* gmap = a.d_src + moff * 4;
+    const float w = a.g_views == nullptr ? a.vw[((size_t)b * a.NS + v) * HW + pc] : 0.0f;
+    // every lane of a wave runs the same number of rounds (a lane beyond D, a dead lane or a zero upstream carries zero weights), so that
+    // the wave can scatter together
+    for (int d0 = 0; d0 < D; d0 += DL) {
+      const int d = d0 + dl;
+      const bool act = live && d < D;
+      const int dc = d < D ? d : D - 1;
+      float G = 0.0f;
+      if (act) {
+        if (a.g_views != nullptr) G = a.g_views[(((size_t)b * a.NS + v) * D + dc) * HW + pc];
+        else G = __fmul_rn(a.g_agg[((size_t)b * D + dc) * HW + pc], w) / wsum;
+      }
+      const float Gs = G / fc;
+      const MvsTaps t = mvs_taps(hm, x, y, dep[(size_t)dc * HW], H, W);
+      float cw[4];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        cw[k] = act ? __fmul_rn(Gs, t.wt[k]) : 0.0f;       // the weights are finite, so a zero upstream gives exact zeros
+        if (cw[k] == 0.0f) continue;
+        const float4* tp = map + (size_t)t.idx[k] * C4;
+#pragma unroll
+        for (int c = 0; c < C4; ++c) {
+          const float4 f = tp[c];
+          acc[c].x = __fmaf_rn(cw[k], f.x, acc[c].x);
+          acc[c].y = __fmaf_rn(cw[k], f.y, acc[c].y);
+          acc[c].z = __fmaf_rn(cw[k], f.z, acc[c].z);
+          acc[c].w = __fmaf_rn(cw[k], f.w, acc[c].w);
+        }
+      }
+      // the scatter: the wave's 64 samples of tap k, PER at a time, a lane a channel -- one instruction adds PER contiguous rows of C
+      // floats (neighbouring pixels hit neighbouring texels) instead of 64 lone floats a row apart
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        if (!__any(cw[k] != 0.0f)) continue;               // wave-uniform
+        for (int it = 0; it < (64 + PER - 1) / PER; ++it) {
+          const int sl = it * PER + se;                    // the lane whose sample this lane helps to add
+          const int sidx = __shfl(t.idx[k], sl & 63);
+          const float scw = __shfl(cw[k], sl & 63);
+          const int spc = __shfl(pc, sl & 63);
+          if (se < PER && sl < 64 && scw != 0.0f)
+            unsafeAtomicAdd(gmap + (size_t)sidx * C + sc, __fmul_rn(scw, refb[(size_t)spc * C + sc]));
+        }
+      }
+    }
+  }
+  float4* o = reinterpret_cast<float4*>(a.d_ref) + ((size_t)b * HW + pc) * C4;
+#pragma unroll
+  for (int c = 0; c < C4; ++c) {
+    red[dl * PB + p] = acc[c];
+    __syncthreads();
+    if (dl == 0 && live) {
+      float4 s = red[p];
+      for (int k = 1; k < DL; ++k) {
+        const float4 q = red[k * PB + p];
+        s.x = __fadd_rn(s.x, q.x);
+        s.y = __fadd_rn(s.y, q.y);
+        s.z = __fadd_rn(s.z, q.z);
+        s.w = __fadd_rn(s.w, q.w);
+      }
+      o[c] = s;
+    }
+    __syncthreads();                             // red[] is rewritten by the next float4
+  }
+}
+
+template <int C4>
+void launch_similarity(const MvsSimArgs& a, int grid, hipStream_t stream) {
+  hipLaunchKernelGGL(k_mvs_similarity<C4>, dim3(grid), dim3(kMvsThreads), 0, stream, a);
+}
+
+template <int C4>
+void launch_similarity_grad(const MvsGradArgs& a, int grid, hipStream_t stream) {
+  hipLaunchKernelGGL(k_mvs_similarity_grad<C4>, dim3(grid), dim3(kMvsThreads), 0, stream, a);
+}
+
 int pixels_per_block(int D) {                    // the LDS slab rule: 2 slabs x D x PB floats <= kMvsSlabBytes, PB a power of two <= 64
   int pb = 64;
   while (pb > 16 && 2 * D * pb * (int)sizeof(float) > kMvsSlabBytes) pb >>= 1;
@@ -329,6 +518,69 @@ extern "C" int diner_mvs_cost_volume_f32(const float* ref_cl, const float* src_c
     DINER_MVS_CASE(9) DINER_MVS_CASE(10) DINER_MVS_CASE(11) DINER_MVS_CASE(12) DINER_MVS_CASE(13) DINER_MVS_CASE(14) DINER_MVS_CASE(15) DINER_MVS_CASE(16)
 #undef DINER_MVS_CASE
   }
+  DINER_LAUNCH_OK();
+  return 0;
+}
+
+#define DINER_MVS_LIMITS(who)                                                                                                               \
+  DINER_CHECK_ARG(B >= 1 && H >= 1 && W >= 1, who ": B = %d, H = %d, W = %d must be >= 1", B, H, W);                                       \
+  DINER_CHECK_ARG(NS >= 1 && NS <= DINER_MAX_VIEWS - 1, who ": %d source views outside [1, %d]", NS, DINER_MAX_VIEWS - 1);                  \
+  DINER_CHECK_ARG(C >= 4 && C <= kMvsMaxC && C % 4 == 0, who ": C = %d must be a multiple of 4 in [4, %d]", C, kMvsMaxC);                   \
+  DINER_CHECK_ARG(D >= 1 && D <= kMvsMaxD, who ": D = %d outside [1, %d]", D, kMvsMaxD);                                                    \
+  DINER_CHECK_ARG((long long)B * D * H * W < (1ll << 31), who ": B D H W = %lld must stay below 2^31", (long long)B * D * H * W)
+
+#define DINER_MVS_DISPATCH(launch, ...)                                                                                                     \
+  switch (C / 4) {                                                                                                                          \
+    case 1: launch<1>(__VA_ARGS__); break;   case 2: launch<2>(__VA_ARGS__); break;   case 3: launch<3>(__VA_ARGS__); break;                \
+    case 4: launch<4>(__VA_ARGS__); break;   case 5: launch<5>(__VA_ARGS__); break;   case 6: launch<6>(__VA_ARGS__); break;                \
+    case 7: launch<7>(__VA_ARGS__); break;   case 8: launch<8>(__VA_ARGS__); break;   case 9: launch<9>(__VA_ARGS__); break;                \
+    case 10: launch<10>(__VA_ARGS__); break; case 11: launch<11>(__VA_ARGS__); break; case 12: launch<12>(__VA_ARGS__); break;              \
+    case 13: launch<13>(__VA_ARGS__); break; case 14: launch<14>(__VA_ARGS__); break; case 15: launch<15>(__VA_ARGS__); break;              \
+    case 16: launch<16>(__VA_ARGS__); break;                                                                                                \
+  }
+
+extern "C" int diner_mvs_similarity_f32(const float* ref_cl, const float* src_cl, const float* proj, const float* depth, float* similarity,
+                                        float* homography, int B, int NS, int C, int D, int H, int W, void* stream) {
+  DINER_CHECK_ARG(ref_cl && src_cl && proj && depth && similarity && homography, "mvs_similarity: null pointer");
+  DINER_MVS_LIMITS("mvs_similarity");
+  DINER_CHECK_ARG(((uintptr_t)ref_cl | (uintptr_t)src_cl) % 16 == 0, "mvs_similarity: the feature maps must be 16-byte aligned");
+  MvsSimArgs a;
+  a.ref_cl = ref_cl; a.src_cl = src_cl; a.hom = homography; a.depth = depth; a.sim = similarity;
+  a.B = B; a.NS = NS; a.D = D; a.H = H; a.W = W;
+  a.PB = pixels_per_block(D);
+  a.blocks_per_sample = (H * W + a.PB - 1) / a.PB;
+  const long long grid = (long long)a.blocks_per_sample * B;
+  DINER_CHECK_ARG(grid < (1ll << 31), "mvs_similarity: %lld workgroups", grid);
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(k_mvs_homography, dim3((B * NS + 63) / 64), dim3(64), 0, st, proj, homography, B, NS);
+  DINER_LAUNCH_OK();
+  DINER_MVS_DISPATCH(launch_similarity, a, (int)grid, st)
+  DINER_LAUNCH_OK();
+  return 0;
+}
+
+extern "C" int diner_mvs_similarity_grad_f32(const float* ref_cl, const float* src_cl, const float* homography, const float* depth,
+                                             const float* grad_views, const float* grad_aggregated, const float* view_weights, float* d_ref,
+                                             float* d_src, int B, int NS, int C, int D, int H, int W, void* stream) {
+  DINER_CHECK_ARG(ref_cl && src_cl && homography && depth && d_ref && d_src, "mvs_similarity_grad: null pointer");
+  DINER_CHECK_ARG((grad_views != nullptr) != (grad_aggregated != nullptr),
+                  "mvs_similarity_grad: give either the per-view gradient or the aggregated one, not both and not neither");
+  DINER_CHECK_ARG((grad_aggregated != nullptr) == (view_weights != nullptr),
+                  "mvs_similarity_grad: the view weights belong to the aggregated gradient, and it needs them");
+  DINER_MVS_LIMITS("mvs_similarity_grad");
+  DINER_CHECK_ARG(((uintptr_t)ref_cl | (uintptr_t)src_cl | (uintptr_t)d_ref | (uintptr_t)d_src) % 16 == 0,
+                  "mvs_similarity_grad: the feature maps and their gradients must be 16-byte aligned");
+  MvsGradArgs a;
+  a.ref_cl = ref_cl; a.src_cl = src_cl; a.hom = homography; a.depth = depth; a.g_views = grad_views; a.g_agg = grad_aggregated;
+  a.vw = view_weights; a.d_ref = d_ref; a.d_src = d_src;
+  a.B = B; a.NS = NS; a.D = D; a.H = H; a.W = W;
+  a.PB = pixels_per_block(D);
+  a.blocks_per_sample = (H * W + a.PB - 1) / a.PB;
+  const long long grid = (long long)a.blocks_per_sample * B;
+  DINER_CHECK_ARG(grid < (1ll << 31), "mvs_similarity_grad: %lld workgroups", grid);
+  hipStream_t st = (hipStream_t)stream;
+  DINER_HIP_OK(hipMemsetAsync(d_src, 0, (size_t)NS * B * H * W * C * sizeof(float), st));
+  DINER_MVS_DISPATCH(launch_similarity_grad, a, (int)grid, st)
   DINER_LAUNCH_OK();
   return 0;
 }

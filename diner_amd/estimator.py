@@ -305,7 +305,7 @@ class DeviceTransMVSNet(nn.Module):
     on batch statistics.  depth_interval: the base interval (max - min) / D0 as a host number; None reads it back from depth_values as the
     reference does (one synchronisation).  grad_method is kept for the reference's signature: the depth a stage hands on is a gather of
     hypotheses at an argmax, which carries no gradient to any parameter either way, and it is handed on detached.
-    fused_readout: DeviceDepthNet's switch (see there)."""
+    fused_readout, match_kernels: DeviceDepthNet's switches (see there)."""
 
     def __init__(self, ndepths=(48, 32, 8), depth_interals_ratio=(4, 2, 1), share_cr=False, cr_base_chs=(8, 8, 8), grad_method="detach"):
         super().__init__()
@@ -330,6 +330,14 @@ class DeviceTransMVSNet(nn.Module):
     @fused_readout.setter
     def fused_readout(self, value):
         self.DepthNet.fused_readout = bool(value)
+
+    @property
+    def match_kernels(self):
+        return self.DepthNet.match_kernels
+
+    @match_kernels.setter
+    def match_kernels(self, value):
+        self.DepthNet.match_kernels = bool(value)
 
     @classmethod
     def from_module(cls, model):
@@ -360,7 +368,7 @@ def warmup_multistep_lr(step, base_lr, milestones, gamma, warmup_factor=1.0 / 3,
 
 
 def fit_estimator(model, batches, *, steps, optimizer=None, lr=1e-3, weight_decay=1e-4, milestones=(), gamma=0.5, dlossw=(1, 1, 1),
-                  start_step=0, log_every=50, on_log=None):
+                  start_step=0, log_every=50, on_log=None, match_kernels=False):
     """`steps` fine-tuning steps k = start_step, ...: model.train(); outputs = model(imgs, proj_matrices, depth_values) with fused_readout;
     focal_loss_bld(outputs, depth, mask, depth_interval, dlossw=dlossw); total.backward(); optimizer.step at warmup_multistep_lr(k, lr,
     milestones, gamma).  batches: any iterable of the reference's sample dicts {"imgs", "proj_matrices", "depth_values", "depth": {"stage
@@ -369,7 +377,8 @@ def fit_estimator(model, batches, *, steps, optimizer=None, lr=1e-3, weight_deca
     None and the model is on a HIP device: coupled weight decay as the reference's Adam, skip_nonfinite, so a non-finite step changes
     nothing where the reference catches NanError on the host) or any torch optimiser (made here as torch.optim.Adam when the model is on
     the CPU).  The five scalars of a step go into a device ring of log_every rows that is read back once per log_every steps (and once at
-    the end): the loop's only wait.  on_log(rows) receives the rows just read.
+    the end): the loop's only wait.  on_log(rows) receives the rows just read.  match_kernels=True sets the model's switch of that name for
+    the loop (the cost volume and its gradients at the feature maps on the kernels of csrc/mvs.hip) and restores it afterwards.
     -> (history, optimizer); history: one dict {step, total, depth_loss, epe, less1, less3} per step."""
     params = [p for p in model.parameters() if p.requires_grad]
     dev = params[0].device
@@ -390,6 +399,9 @@ def fit_estimator(model, batches, *, steps, optimizer=None, lr=1e-3, weight_deca
     had_fused = getattr(model, "fused_readout", None)
     if had_fused is not None:
         model.fused_readout = True
+    had_match = getattr(model, "match_kernels", None) if match_kernels else None
+    if had_match is not None:
+        model.match_kernels = True
     optimizer.zero_grad()
     intervals = {}
 
@@ -433,6 +445,8 @@ def fit_estimator(model, batches, *, steps, optimizer=None, lr=1e-3, weight_deca
     finally:
         if had_fused is not None:
             model.fused_readout = had_fused
+        if had_match is not None:
+            model.match_kernels = had_match
     return history, optimizer
 
 

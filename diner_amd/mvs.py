@@ -9,8 +9,10 @@ on the kernels of csrc/fmt.hip (DeviceFMT, DeviceFMTWithPathway), and the featur
 
 Every thin function takes the reference's tensor layouts (NCHW).  On HIP tensors it runs the kernels; on CPU tensors it runs a torch
 restatement of the same mathematics with the reference's own operations in the reference's order (`*_torch`, any floating dtype),
-which is the host oracle of the tests and the baseline of tools/time_mvs.py.  Inference only: nothing here has a backward pass;
-DeviceDepthNet uses torch operations whenever gradients are enabled or the module is in training mode (fine-tuning: diner_amd.estimator)."""
+which is the host oracle of the tests and the baseline of tools/time_mvs.py.  The networks' kernels are inference only; the matching
+stage alone has a backward pass in HIP (match_similarity, cost_volume_train: the similarity's gradients at the feature maps).
+DeviceDepthNet uses torch operations whenever gradients are enabled or the module is in training mode (fine-tuning: diner_amd.estimator),
+and with match_kernels those kernels for the cost volume."""
 import numpy as np
 import torch
 import torch.nn as nn
@@ -182,6 +184,122 @@ def cost_volume(features, proj_matrices, depth_values, pixelwise=None, view_weig
     return sim.unsqueeze(1), weights
 
 
+# ---- the matching stage in training: the kernels with a backward pass ------------------------------------------------------------------
+def match_gate(features, proj_matrices, depth_values, view_weights=None):
+    """Whether match_similarity / cost_volume_train run the kernels: float32 HIP tensors inside diner_mvs_cost_volume_f32's limits."""
+    tensors = list(features) + [proj_matrices, depth_values] + ([] if view_weights is None else [view_weights])
+    if not all(torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 for t in tensors):
+        return False
+    B, Cf, H, W = (int(n) for n in features[0].shape)
+    try:
+        _ops()._check_mvs_limits(B, len(features) - 1, Cf, int(depth_values.shape[1]), H, W)
+    except ValueError:
+        return False
+    return True
+
+
+def _channels_last_stack(features):
+    return torch.stack([f.detach() for f in features], 0).permute(0, 1, 3, 4, 2).contiguous()         # the one repack: (NV,B,H,W,C)
+
+
+def _feature_grads(ctx, d_ref, d_src, first):
+    """The gradients as NCHW views of the kernels' channels-last results, None where a feature map needs none."""
+    maps = [d_ref] + list(torch.unbind(d_src, 0))
+    return tuple(m.permute(0, 3, 1, 2) if ctx.needs_input_grad[first + i] else None for i, m in enumerate(maps))
+
+
+class _MatchSimilarity(torch.autograd.Function):
+    """diner_mvs_similarity_f32 / diner_mvs_similarity_grad_f32 (per-view upstream).  Saves the channels-last features, the homography and
+    the depth; no gradient to proj or depth.  The backward pass is a kernel on detached tensors: once differentiable, a second derivative
+    raises."""
+
+    @staticmethod
+    def forward(ctx, proj, depth, *features):
+        cl = _channels_last_stack(features)
+        depth = depth.detach().contiguous()
+        sim, hom = _ops().mvs_similarity(cl[0], cl[1:], proj.detach(), depth)
+        ctx.save_for_backward(cl, hom, depth)
+        return sim
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad):
+        cl, hom, depth = ctx.saved_tensors
+        d_ref, d_src = _ops().mvs_similarity_grad(cl[0], cl[1:], hom, depth, grad_views=grad.to(torch.float32).contiguous())
+        return (None, None) + _feature_grads(ctx, d_ref, d_src, 2)
+
+
+class _CostVolumeGiven(torch.autograd.Function):
+    """diner_mvs_cost_volume_f32 with given view weights / diner_mvs_similarity_grad_f32 (aggregated upstream): no per-view volume in
+    either direction.  No gradient to proj, depth or the weights (DeviceDepthNet hands the weights on detached, as the reference does)."""
+
+    @staticmethod
+    def forward(ctx, proj, depth, view_weights, *features):
+        cl = _channels_last_stack(features)
+        depth, view_weights = depth.detach().contiguous(), view_weights.detach().contiguous()
+        sim, _, hom = _ops().mvs_cost_volume(cl[0], cl[1:], proj.detach(), depth, None, view_weights, return_homography=True)
+        ctx.save_for_backward(cl, hom, depth, view_weights)
+        return sim.unsqueeze(1)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad):
+        cl, hom, depth, view_weights = ctx.saved_tensors
+        d_ref, d_src = _ops().mvs_similarity_grad(cl[0], cl[1:], hom, depth, grad_aggregated=grad.to(torch.float32).squeeze(1).contiguous(),
+                                                  view_weights=view_weights)
+        return (None, None, None) + _feature_grads(ctx, d_ref, d_src, 3)
+
+
+def match_similarity_torch(features, proj_matrices, depth_values):
+    """The per-view similarity of cost_volume_torch, stacked: mean_c(homo_warping(src_v) ref) -> (B,NS,D,H,W), in features[0]'s dtype."""
+    dt = features[0].dtype
+    projs = torch.unbind(proj_matrices.to(dt), 1)
+    ref_feature, ref_proj = features[0], _full_proj(projs[0])
+    depth_values = depth_values.to(dt)
+    sims = []
+    for src_fea, src_pair in zip(features[1:], projs[1:]):
+        warped = warp_torch(src_fea, _full_proj(src_pair), ref_proj, depth_values)
+        sims.append((warped * ref_feature.unsqueeze(2)).mean(1))
+        del warped
+    return torch.stack(sims, 1)
+
+
+def match_similarity(features, proj_matrices, depth_values):
+    """features: [reference, source 1, ...] each (B,C,H,W); proj_matrices (B,NV,2,4,4); depth_values (B,D,H,W) -> the per-view similarity
+    (B,NV-1,D,H,W), differentiable in every feature map (the sampling positions carry no gradient, as in the reference).  On float32 HIP
+    tensors inside the kernels' limits: diner_mvs_similarity_f32 and, in the backward pass, diner_mvs_similarity_grad_f32, with neither a
+    sampling grid nor a warped volume; anything else (CPU tensors, other dtypes, C % 4 != 0) runs match_similarity_torch, the host oracle."""
+    _check_features(features, proj_matrices, depth_values)
+    if not match_gate(features, proj_matrices, depth_values):
+        return match_similarity_torch(features, proj_matrices, depth_values)
+    return _MatchSimilarity.apply(proj_matrices, depth_values, *features)
+
+
+def cost_volume_train(features, proj_matrices, depth_values, pixelwise_net=None, view_weights=None):
+    """cost_volume_torch's results -- (similarity (B,1,D,H,W), view weights (B,NS,H,W)) -- differentiable in the feature maps and the
+    pixelwise net's parameters, on the kernels where match_gate lets them run (otherwise cost_volume_torch itself).
+    Given view_weights: diner_mvs_cost_volume_f32 forward, the aggregated form of diner_mvs_similarity_grad_f32 backward.
+    Otherwise pixelwise_net, a callable similarity (B,1,D,H,W) -> weight (B,1,H,W) (the module itself: in training mode it runs on batch
+    statistics and updates them, view by view, as the reference does): match_similarity, then the reference's torch expressions on the
+    one-channel volumes."""
+    _check_features(features, proj_matrices, depth_values)
+    if (pixelwise_net is None) == (view_weights is None):
+        raise ValueError("diner_amd: cost_volume_train takes either pixelwise_net (a callable) or view_weights")
+    if not match_gate(features, proj_matrices, depth_values, view_weights):
+        return cost_volume_torch(features, proj_matrices, depth_values, pixelwise_net, view_weights)
+    if view_weights is not None:
+        return _CostVolumeGiven.apply(proj_matrices, depth_values, view_weights, *features), view_weights
+    s = _MatchSimilarity.apply(proj_matrices, depth_values, *features)
+    weights, sim_sum, w_sum = [], 0, 1e-5
+    for v in range(s.shape[1]):
+        similarity = s[:, v:v + 1]
+        w = pixelwise_net(similarity)
+        weights.append(w)
+        sim_sum = sim_sum + similarity * w.unsqueeze(1)
+        w_sum = w_sum + w.unsqueeze(1)
+    return sim_sum / w_sum, torch.cat(weights, dim=1)
+
+
 def select_depth(cost, depth_values, prob_init=None, return_prob=True):
     """cost (B,D,H,W) or (B,1,D,H,W) from the regulariser [+ prob_init], depth_values (B,D,H,W)
     -> (depth (B,H,W), confidence (B,H,W), prob volume (B,D,H,W) or None)."""
@@ -238,12 +356,18 @@ class DeviceDepthNet(nn.Module):
     enabled and float32 HIP tensors, it does not form the probability volume: depth and confidence come from the read-out kernel on the
     detached cost, and the stage dict carries "cost" (the regulariser's output plus prob_volume_init, with its graph) and "prob_volume":
     None -- what diner_amd.estimator's losses take.  The kernel's winner may differ from argmax(prob_volume) of the torch route on an exact
-    tie that exp creates (two planes whose probabilities round to the same float32 in one chain and not in the other), and nowhere else."""
+    tie that exp creates (two planes whose probabilities round to the same float32 in one chain and not in the other), and nowhere else.
+
+    match_kernels (default False: every route is as it was, bit for bit).  When True and the module is on its torch route, the cost volume
+    comes from cost_volume_train: on float32 HIP tensors inside the kernels' limits the similarity and its gradients at the feature maps
+    run on the kernels of csrc/mvs.hip (no sampling grid and no warped volume is kept for the backward pass), the pixelwise net and the
+    aggregation stay torch operations; any other input takes the torch route silently.  Composes with fused_readout."""
 
     def __init__(self):
         super().__init__()
         self.pixel_wise_net = _PixelwiseNet()
         self.fused_readout = False
+        self.match_kernels = False
         self._folded, self._folded_key = None, None
 
     @classmethod
@@ -278,7 +402,8 @@ class DeviceDepthNet(nn.Module):
         else:
             # the view weights from the module itself: differentiable down to its parameters, and in training mode on BatchNorm's batch
             # statistics (which it then also updates), like the reference
-            similarity, weights = cost_volume_torch(features, proj_matrices, depth_values, None if given else self.pixel_wise_net, view_weights)
+            matching = cost_volume_train if self.match_kernels else cost_volume_torch        # the former falls back to the latter by itself
+            similarity, weights = matching(features, proj_matrices, depth_values, None if given else self.pixel_wise_net, view_weights)
             cost = cost_regularization(similarity).squeeze(1)
             if (self.fused_readout and torch.is_grad_enabled() and cost.is_cuda and cost.dtype == torch.float32
                     and depth_values.dtype == torch.float32 and (prob_volume_init is None or prob_volume_init.dtype == torch.float32)):

@@ -1368,10 +1368,10 @@ def _check_mvs_cost_volume_args(ref_cl, src_cl, proj, depth, pixelwise, view_wei
     return B, NS, Cf, D, H, W
 
 
-def mvs_cost_volume(ref_cl, src_cl, proj, depth, pixelwise=None, view_weights=None):
+def mvs_cost_volume(ref_cl, src_cl, proj, depth, pixelwise=None, view_weights=None, return_homography=False):
     """diner_mvs_cost_volume_f32: channels-last features ref (B,H,W,C) and src (NS,B,H,W,C), camera pairs proj (B,NS+1,2,4,4), hypotheses
     depth (B,D,H,W) and either the folded pixelwise net (177 floats) or view weights (B,NS,H,W) -> (similarity (B,D,H,W), view weights
-    (B,NS,H,W): the computed ones, or the given ones)."""
+    (B,NS,H,W): the computed ones, or the given ones[, the homography (B,NS,12) that mvs_similarity_grad takes])."""
     B, NS, Cf, D, H, W = _check_mvs_cost_volume_args(ref_cl, src_cl, proj, depth, pixelwise, view_weights)
     _require_hip(ref_cl, src_cl, proj, depth, pixelwise, view_weights)
     ref_cl, src_cl, proj, depth = ref_cl.contiguous(), src_cl.contiguous(), proj.contiguous(), depth.contiguous()
@@ -1386,7 +1386,68 @@ def mvs_cost_volume(ref_cl, src_cl, proj, depth, pixelwise=None, view_weights=No
     with torch.cuda.device(dev):
         _lib.check(lib.diner_mvs_cost_volume_f32(_ptr(ref_cl), _ptr(src_cl), _ptr(proj), _ptr(depth), _ptr(pixelwise), _ptr(vw_in), _ptr(sim),
                                                  _ptr(vw_out), _ptr(hom), B, NS, Cf, D, H, W, _stream()))
+    if return_homography:
+        return sim, (vw_out if vw_out is not None else view_weights), hom
     return sim, (vw_out if vw_out is not None else view_weights)
+
+
+def _check_mvs_similarity_args(ref_cl, src_cl, depth, who="mvs_similarity"):
+    """The shape and limit checks the similarity entries share (no device needed) -> (B, NS, C, D, H, W)."""
+    if ref_cl.dim() != 4 or src_cl.dim() != 5 or depth.dim() != 4:
+        raise ValueError(f"diner_amd: {who} expects ref (B,H,W,C), src (NS,B,H,W,C), depth (B,D,H,W), got {tuple(ref_cl.shape)}, "
+                         f"{tuple(src_cl.shape)}, {tuple(depth.shape)}")
+    B, H, W, Cf = (int(v) for v in ref_cl.shape)
+    NS, D = int(src_cl.shape[0]), int(depth.shape[1])
+    if tuple(src_cl.shape[1:]) != (B, H, W, Cf) or tuple(depth.shape) != (B, D, H, W):
+        raise ValueError(f"diner_amd: {who} shapes disagree: ref {tuple(ref_cl.shape)}, src {tuple(src_cl.shape)}, depth {tuple(depth.shape)}")
+    _check_mvs_limits(B, NS, Cf, D, H, W)
+    return B, NS, Cf, D, H, W
+
+
+def mvs_similarity(ref_cl, src_cl, proj, depth):
+    """diner_mvs_similarity_f32: channels-last features ref (B,H,W,C) and src (NS,B,H,W,C), camera pairs proj (B,NS+1,2,4,4), hypotheses
+    depth (B,D,H,W) -> (per-view similarity (B,NS,D,H,W), homography (B,NS,12) for mvs_similarity_grad)."""
+    B, NS, Cf, D, H, W = _check_mvs_similarity_args(ref_cl, src_cl, depth)
+    if tuple(proj.shape) != (B, NS + 1, 2, 4, 4):
+        raise ValueError(f"diner_amd: mvs_similarity expects proj ({B},{NS + 1},2,4,4), got {tuple(proj.shape)}")
+    _require_hip(ref_cl, src_cl, proj, depth)
+    ref_cl, src_cl, proj, depth = ref_cl.contiguous(), src_cl.contiguous(), proj.contiguous(), depth.contiguous()
+    dev = ref_cl.device
+    sim = torch.empty(B, NS, D, H, W, device=dev, dtype=torch.float32)
+    hom = torch.empty(B, NS, 12, device=dev, dtype=torch.float32)
+    with torch.cuda.device(dev):
+        _lib.check(lib.diner_mvs_similarity_f32(_ptr(ref_cl), _ptr(src_cl), _ptr(proj), _ptr(depth), _ptr(sim), _ptr(hom), B, NS, Cf, D, H, W,
+                                                _stream()))
+    return sim, hom
+
+
+def mvs_similarity_grad(ref_cl, src_cl, homography, depth, grad_views=None, grad_aggregated=None, view_weights=None):
+    """diner_mvs_similarity_grad_f32: the feature maps and the homography of the forward, and the upstream gradient either per view,
+    grad_views (B,NS,D,H,W), or aggregated, grad_aggregated (B,D,H,W) with view_weights (B,NS,H,W)
+    -> (d_ref (B,H,W,C), d_src (NS,B,H,W,C)).  d_ref is the same bits on every run; d_src is summed by float atomics."""
+    who = "mvs_similarity_grad"
+    B, NS, Cf, D, H, W = _check_mvs_similarity_args(ref_cl, src_cl, depth, who)
+    if tuple(homography.shape) != (B, NS, 12):
+        raise ValueError(f"diner_amd: {who} expects the homography ({B},{NS},12) of the forward, got {tuple(homography.shape)}")
+    if (grad_views is None) == (grad_aggregated is None):
+        raise ValueError(f"diner_amd: {who} takes either grad_views or grad_aggregated with view_weights")
+    if (grad_aggregated is None) != (view_weights is None):
+        raise ValueError(f"diner_amd: {who}: view_weights belong to grad_aggregated, and it needs them")
+    if grad_views is not None and tuple(grad_views.shape) != (B, NS, D, H, W):
+        raise ValueError(f"diner_amd: {who} expects grad_views ({B},{NS},{D},{H},{W}), got {tuple(grad_views.shape)}")
+    if grad_aggregated is not None and (tuple(grad_aggregated.shape) != (B, D, H, W) or tuple(view_weights.shape) != (B, NS, H, W)):
+        raise ValueError(f"diner_amd: {who} expects grad_aggregated ({B},{D},{H},{W}) and view_weights ({B},{NS},{H},{W}), got "
+                         f"{tuple(grad_aggregated.shape)}, {tuple(view_weights.shape)}")
+    _require_hip(ref_cl, src_cl, homography, depth, grad_views, grad_aggregated, view_weights)
+    c = lambda t: None if t is None else t.contiguous()
+    ref_cl, src_cl, homography, depth = c(ref_cl), c(src_cl), c(homography), c(depth)
+    grad_views, grad_aggregated, view_weights = c(grad_views), c(grad_aggregated), c(view_weights)
+    d_ref, d_src = torch.empty_like(ref_cl), torch.empty_like(src_cl)
+    with torch.cuda.device(ref_cl.device):
+        _lib.check(lib.diner_mvs_similarity_grad_f32(_ptr(ref_cl), _ptr(src_cl), _ptr(homography), _ptr(depth), _ptr(grad_views),
+                                                     _ptr(grad_aggregated), _ptr(view_weights), _ptr(d_ref), _ptr(d_src), B, NS, Cf, D, H, W,
+                                                     _stream()))
+    return d_ref, d_src
 
 
 def mvs_select_depth(cost, hypotheses, prob_init=None, return_prob=True):

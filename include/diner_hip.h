@@ -939,6 +939,27 @@ int diner_mvs_select_depth_f32(const float* cost, const float* prob_init, const 
 int diner_mvs_hypotheses_f32(const float* cur_depth, float* hypotheses, int B, int h, int w, int H, int W, int scale, int D, float half_range,
                              void* stream);
 
+/* ---- the matching stage in training: the per-view similarity and its backward pass ---------------------------------------------------
+ * New symbols without an ABI bump (mvs.hip); layouts, limits, checks and the tap geometry are diner_mvs_cost_volume_f32's (the geometry
+ * is one function, csrc/mvs_geom.hpp, that restates that kernel's operations in its order).  No gradient goes to depth, proj or the view
+ * weights: the reference computes the sampling positions under no_grad.
+ *
+ * diner_mvs_similarity_f32: similarity (B,NS,D,H,W) out, similarity[b,v,d] = similarity_v[d] above -- the bits diner_mvs_cost_volume_f32
+ *   aggregates.  homography (B NS 12 floats) out: hand it to the backward pass.
+ * diner_mvs_similarity_grad_f32: the gradients of sum_{b,v,d,pixel} G similarity at the feature maps.  The upstream gradient is either
+ *   grad_views (B,NS,D,H,W) = G, or grad_aggregated (B,D,H,W) = g with view_weights (B,NS,H,W) = w, from which the kernel forms
+ *   G_v = g w_v / (1e-5 + sum_v w_v) (the sum in view order) without an NS-fold volume; the other form's pointers are NULL.
+ *   homography: what the forward entry (either of the two) wrote.
+ *   d_ref (B,H,W,C) = (1/C) sum_v sum_d G_vd sum_tap bw_tap src[v,tap,:]: no atomics, a pixel's partial sums are added in an order the
+ *   shape alone fixes, every element is written; the same bits on every run and at any place in the batch.
+ *   d_src (NS,B,H,W,C) += (1/C) G_vd bw_tap ref[pixel,:] at each tap: zeroed by one hipMemsetAsync here, then float atomic adds, whose
+ *   order is not fixed (the last bits may differ between runs).  A tap whose G bw is exactly 0 adds nothing to either. */
+int diner_mvs_similarity_f32(const float* ref_cl, const float* src_cl, const float* proj, const float* depth, float* similarity,
+                             float* homography, int B, int NS, int C, int D, int H, int W, void* stream);
+int diner_mvs_similarity_grad_f32(const float* ref_cl, const float* src_cl, const float* homography, const float* depth,
+                                  const float* grad_views, const float* grad_aggregated, const float* view_weights, float* d_ref,
+                                  float* d_src, int B, int NS, int C, int D, int H, int W, void* stream);
+
 /* ---- the depth estimator's cost regulariser: the layers of CostRegNet, a 3-D U-Net of 3 x 3 x 3 convolutions ---------------------------
  * New symbols without an ABI bump (costreg.hip); inference only, no allocation, enqueue-only, one launch each, everything fp32;
  * activations are channels-last (N,D,H,W,C) on the device -- a one-channel volume (N,1,D,H,W) is that layout already.  No atomics; every
