@@ -56,4 +56,31 @@ DINER_GEOM_HD inline DeformCorners deform_corners(int h, int w, int ky, int kx, 
   return c;
 }
 
+// The same sample with the derivatives of its four weights by the coordinate (deform_grad.hip, tools/deform_grad_geom_check.cpp):
+//   d wt / d py = (-hx, -lx, hx, lx),   d wt / d px = (-hy, hy, -ly, ly)
+// torchvision's rule (its get_coordinate_weight), which is also what autograd through floor() gives: at an exactly integer coordinate the
+// right-sided difference.  c is deform_corners() of the same arguments, bit for bit.  A sample that lies outside -- a NaN, an infinite or
+// a huge offset included -- has every derivative exactly 0, and no non-finite number is ever formed from a finite coordinate.
+struct DeformCornerGrads {
+  DeformCorners c;
+  float gy[4];      // d wt[i] / d py; 0 where the whole sample is outside
+  float gx[4];      // d wt[i] / d px
+};
+
+DINER_GEOM_HD inline DeformCornerGrads deform_corner_grads(int h, int w, int ky, int kx, float dy, float dx, int H, int W) {
+  DeformCornerGrads g;
+  g.c = deform_corners(h, w, ky, kx, dy, dx, H, W);
+  for (int i = 0; i < 4; ++i) {
+    g.gy[i] = 0.0f;
+    g.gx[i] = 0.0f;
+  }
+  const float py = (float)(h - 1 + ky) + dy, px = (float)(w - 1 + kx) + dx;
+  if (!(py > -1.0f && py < (float)H && px > -1.0f && px < (float)W)) return g;
+  const float fy = fminf(fmaxf(floorf(py), -1.0f), (float)(H - 1)), fx = fminf(fmaxf(floorf(px), -1.0f), (float)(W - 1));
+  const float ly = py - fy, lx = px - fx, hy = 1.0f - ly, hx = 1.0f - lx;
+  g.gy[0] = -hx; g.gy[1] = -lx; g.gy[2] = hx; g.gy[3] = lx;
+  g.gx[0] = -hy; g.gx[1] = hy; g.gx[2] = -ly; g.gx[3] = ly;
+  return g;
+}
+
 }  // namespace diner

@@ -918,6 +918,132 @@ def deform_conv2d_torch(input, offset, weight, bias=None, stride=(1, 1), padding
     return out if bias is None else out + bias.view(1, -1, 1, 1)
 
 
+def _deform_samples(x, offmask):
+    """The sampling geometry of the 3 x 3, stride 1, padding 1 layer, deform_conv2d_torch's expressions: x (B,Cin,H,W), offmask (B,27,H,W)
+    -> inside (B,9,H,W), (ly, lx, hy, hx), and per corner (y0,x0), (y0,x1), (y1,x0), (y1,x1): the index (B,9 H W) into the flattened map,
+    valid (B,9,H,W) and the values (B,Cin,9,H,W), zero where the corner is not valid."""
+    B, Cin, H, W = (int(n) for n in x.shape)
+    dt, dev = x.dtype, x.device
+    k = torch.arange(9, device=dev)
+    base_y = (torch.arange(H, device=dev) - 1).view(1, H, 1) + (k // 3).view(9, 1, 1)
+    base_x = (torch.arange(W, device=dev) - 1).view(1, 1, W) + (k % 3).view(9, 1, 1)
+    py = base_y.to(dt).unsqueeze(0) + offmask[:, 0:18:2]
+    px = base_x.to(dt).unsqueeze(0) + offmask[:, 1:18:2]
+    inside = (py > -1) & (py < H) & (px > -1) & (px < W)
+    py, px = torch.where(inside, py, torch.zeros_like(py)), torch.where(inside, px, torch.zeros_like(px))
+    y0, x0 = torch.floor(py), torch.floor(px)
+    ly, lx = py - y0, px - x0
+    y0i, x0i = y0.long(), x0.long()
+    flat = x.reshape(B, Cin, H * W)
+    corners = []
+    for yi, xi in ((y0i, x0i), (y0i, x0i + 1), (y0i + 1, x0i), (y0i + 1, x0i + 1)):
+        valid = inside & (yi >= 0) & (yi <= H - 1) & (xi >= 0) & (xi <= W - 1)
+        idx = (yi.clamp(0, H - 1) * W + xi.clamp(0, W - 1)).reshape(B, 9 * H * W)
+        v = flat.gather(2, idx.unsqueeze(1).expand(B, Cin, 9 * H * W)).reshape(B, Cin, 9, H, W)
+        corners.append((idx, valid, torch.where(valid.unsqueeze(1), v, torch.zeros_like(v))))
+    return inside, (ly, lx, 1 - ly, 1 - lx), corners
+
+
+def deform_conv3x3_grad_torch(x, offmask, weight, dy):
+    """The gradients of y = deform_conv2d_torch(x, offmask[:, :18], weight, bias, 1, 1, 1, mask=sigmoid(offmask[:, 18:])) under the upstream
+    dy (B,Cout,H,W), in closed form and in torch operations, any floating dtype: the host restatement of diner_deform_conv3x3_grad_f32.
+    x (B,Cin,H,W), the raw offmask (B,27,H,W), weight (Cout,Cin,3,3) -> (d_x, d_offmask, d_weight, d_bias).  With m the sigmoid, S the
+    sample, v_i its corner values (0 where not valid), G[b,c,k] = sum_o dy[b,o] w[o,c,k]: d_logit = m (1 - m) sum_c G S; d_dy = m sum_c G
+    (-hx v00 - lx v01 + hx v10 + lx v11), d_dx = m sum_c G (-hy v00 + hy v01 - ly v10 + ly v11) -- at an integer coordinate the
+    right-sided difference, as autograd through floor() gives it; d_x adds m wt_i G at every valid corner; d_weight = sum dy m S;
+    d_bias = sum dy.  A tap that lies outside (a NaN offset included) has gradients that are exactly 0."""
+    if x.dim() != 4 or offmask.dim() != 4 or weight.dim() != 4 or dy.dim() != 4:
+        raise ValueError("diner_amd: deform_conv3x3_grad_torch expects x (B,Cin,H,W), offmask (B,27,H,W), weight (Cout,Cin,3,3), dy (B,Cout,H,W)")
+    B, Cin, H, W = (int(n) for n in x.shape)
+    Cout = int(weight.shape[0])
+    if tuple(offmask.shape) != (B, 27, H, W) or tuple(weight.shape) != (Cout, Cin, 3, 3) or tuple(dy.shape) != (B, Cout, H, W):
+        raise ValueError(f"diner_amd: deform_conv3x3_grad_torch: shapes {tuple(x.shape)}, {tuple(offmask.shape)}, {tuple(weight.shape)}, "
+                         f"{tuple(dy.shape)} do not belong together")
+    x, offmask, weight, dy = x.detach(), offmask.detach(), weight.detach(), dy.detach()
+    inside, (ly, lx, hy, hx), corners = _deform_samples(x, offmask)
+    zero = torch.zeros_like(ly)
+    masked = lambda ts: [torch.where(inside, t, zero) for t in ts]
+    wt = masked((hy * hx, hy * lx, ly * hx, ly * lx))
+    gy = masked((-hx, -lx, hx, lx))
+    gx = masked((-hy, hy, -ly, ly))
+    m = torch.sigmoid(offmask[:, 18:])
+    G = torch.einsum("bohw,ock->bckhw", dy, weight.reshape(Cout, Cin, 9))
+    S = sum(w.unsqueeze(1) * v for w, (_, _, v) in zip(wt, corners))
+    d_logit = m * (1 - m) * (G * S).sum(1)
+    d_dy = m * (G * sum(w.unsqueeze(1) * v for w, (_, _, v) in zip(gy, corners))).sum(1)
+    d_dx = m * (G * sum(w.unsqueeze(1) * v for w, (_, _, v) in zip(gx, corners))).sum(1)
+    d_offmask = torch.cat((torch.stack((d_dy, d_dx), 2).reshape(B, 18, H, W), d_logit), 1)
+    d_x = torch.zeros(B, Cin, H * W, dtype=x.dtype, device=x.device)
+    for w, (idx, valid, _) in zip(wt, corners):
+        coef = torch.where(valid, m * w, zero)
+        d_x.scatter_add_(2, idx.unsqueeze(1).expand(B, Cin, 9 * H * W), (coef.unsqueeze(1) * G).reshape(B, Cin, 9 * H * W))
+    d_weight = torch.einsum("bohw,bckhw->ock", dy, m.unsqueeze(1) * S).reshape(Cout, Cin, 3, 3)
+    return d_x.view(B, Cin, H, W), d_offmask, d_weight, dy.sum((0, 2, 3))
+
+
+def _deform_torch(x, offmask, weight, bias):
+    return deform_conv2d_torch(x, offmask[:, :18], weight, bias, (1, 1), (1, 1), (1, 1), mask=torch.sigmoid(offmask[:, 18:]))
+
+
+def deform_gate(x, offmask, weight, bias=None):
+    """Whether deform_conv3x3 runs the kernels: float32 HIP tensors inside diner_deform_conv3x3_grad_f32's limits."""
+    tensors = [x, offmask, weight] + ([] if bias is None else [bias])
+    if not all(torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 for t in tensors):
+        return False
+    if x.dim() != 4 or weight.dim() != 4 or offmask.dim() != 4 or tuple(weight.shape[1:]) != (x.shape[1], 3, 3):
+        return False
+    B, Cin, H, W = (int(n) for n in x.shape)
+    Cout = int(weight.shape[0])
+    if tuple(offmask.shape) != (B, 27, H, W) or (bias is not None and tuple(bias.shape) != (Cout,)):
+        return False
+    return _ops().deform_grad_supported(Cin, Cout) and 1 <= B <= 65535 and 1 <= H <= 1 << 14 and 1 <= W <= 1 << 14
+
+
+class _DeformConv3x3(torch.autograd.Function):
+    """diner_deform_conv3x3_f32 / diner_deform_conv3x3_grad_f32.  Saves its inputs x, offmask and the weight and nothing else: no sampled
+    matrix, no index tensors.  The backward pass is a kernel on detached tensors and computes only the gradients that are needed; asked
+    for a graph of its own (a second derivative) it differentiates deform_conv2d_torch on the saved inputs instead."""
+
+    @staticmethod
+    def forward(ctx, x, offmask, weight, bias):
+        ops = _ops()
+        x_cl = x.detach().permute(0, 2, 3, 1).contiguous()
+        om_cl = offmask.detach().permute(0, 2, 3, 1).contiguous()
+        w = weight.detach().contiguous()
+        y = ops.deform_conv3x3(x_cl, om_cl, ops.pack_deform_conv3x3(w), None if bias is None else bias.detach().contiguous(), int(w.shape[0]))
+        ctx.save_for_backward(x, offmask, weight)
+        ctx.has_bias = bias is not None
+        return y.permute(0, 3, 1, 2)
+
+    @staticmethod
+    def backward(ctx, grad):
+        x, offmask, weight = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        if torch.is_grad_enabled():                 # create_graph=True: the torch restatement carries the second derivative
+            with torch.enable_grad():
+                bias = torch.zeros(weight.shape[0], dtype=weight.dtype, device=weight.device, requires_grad=True) if ctx.has_bias else None
+                inputs = [t for t, n in zip((x, offmask, weight, bias), need) if n]
+                got = iter(torch.autograd.grad(_deform_torch(x, offmask, weight, bias), inputs, grad, create_graph=True))
+            return tuple(next(got) if n else None for n in need)
+        want = (need[0], need[1], need[2], ctx.has_bias and need[3])
+        d_x, d_om, d_w, d_b = _ops().deform_conv3x3_grad(x.detach().permute(0, 2, 3, 1).contiguous(), offmask.detach().permute(0, 2, 3, 1).contiguous(),
+                                                         weight.detach().contiguous(), grad.detach().to(torch.float32).permute(0, 2, 3, 1).contiguous(),
+                                                         want=want)
+        return (None if d_x is None else d_x.permute(0, 3, 1, 2), None if d_om is None else d_om.permute(0, 3, 1, 2), d_w, d_b)
+
+
+def deform_conv3x3(x, offmask, weight, bias=None):
+    """The modulated deformable 3 x 3 convolution (stride 1, padding 1, one offset group) of a DCN layer, differentiable: x (B,Cin,H,W),
+    offmask (B,27,H,W) the raw conv_offset_mask output (channel 2 k the row and 2 k + 1 the column offset of tap k, 18 + k the logit of its
+    modulation), weight (Cout,Cin,3,3) -> (B,Cout,H,W).  On float32 HIP tensors with Cin a multiple of 8 up to 64 and Cout up to 64 it is
+    one autograd Function: diner_deform_conv3x3_f32 forward (the result is a PERMUTED VIEW OF CHANNELS-LAST MEMORY), in the backward pass
+    diner_deform_conv3x3_grad_f32, which computes only the gradients that are needed; d_x comes from float atomic adds and is not
+    bit-reproducible.  Anything else (CPU tensors, other dtypes, other sizes, a second derivative) runs deform_conv2d_torch."""
+    if not deform_gate(x, offmask, weight, bias):
+        return _deform_torch(x, offmask, weight, bias)
+    return _DeformConv3x3.apply(x, offmask, weight, bias)
+
+
 class _Conv2dBnReLU(nn.Module):
     """The reference's Conv2d block (models/module.py:24-62) with BatchNorm and ReLU, under its state-dict keys (conv.weight, bn.*)."""
 
@@ -931,10 +1057,12 @@ class _Conv2dBnReLU(nn.Module):
 
 
 class _DCN(nn.Module):
-    """The reference's DCN (models/dcn.py) under its state-dict keys (weight, bias, conv_offset_mask.*), on deform_conv2d_torch."""
+    """The reference's DCN (models/dcn.py) under its state-dict keys (weight, bias, conv_offset_mask.*), on deform_conv2d_torch; with
+    deform_kernels set (default False: bit for bit as it was) on deform_conv3x3, whose backward pass is a kernel."""
 
     def __init__(self, cin, cout):
         super().__init__()
+        self.deform_kernels = False
         self.weight = nn.Parameter(torch.empty(cout, cin, 3, 3))
         self.bias = nn.Parameter(torch.zeros(cout))
         self.conv_offset_mask = nn.Conv2d(cin, 27, 3, stride=1, padding=1, bias=True)
@@ -945,6 +1073,8 @@ class _DCN(nn.Module):
 
     def forward(self, x):
         out = self.conv_offset_mask(x)
+        if self.deform_kernels:
+            return deform_conv3x3(x, out, self.weight, self.bias)       # falls back to deform_conv2d_torch by itself
         o1, o2, mask = torch.chunk(out, 3, dim=1)
         return deform_conv2d_torch(x, torch.cat((o1, o2), dim=1), self.weight, self.bias, (1, 1), (1, 1), (1, 1), mask=torch.sigmoid(mask))
 
@@ -977,7 +1107,12 @@ class DeviceFeatureNet(nn.Module):
     modulation channels) followed by diner_deform_conv3x3_f32; BatchNorm is folded into the weights.  Its results then have the
     reference's shapes but are PERMUTED VIEWS OF CHANNELS-LAST MEMORY, which DeviceFMTWithPathway takes unchanged.  Otherwise it runs
     the reference's operations in the reference's order, the deformable convolution as deform_conv2d_torch: differentiable, on batch
-    statistics in training mode.  No torchvision anywhere.  `mvs.to_device(model)` switches a loaded TransMVSNet over."""
+    statistics in training mode.  No torchvision anywhere.  `mvs.to_device(model)` switches a loaded TransMVSNet over.
+
+    deform_kernels (default False: every route is as it was, bit for bit).  When True, the nine deformable convolutions of the torch
+    route run deform_conv3x3: diner_deform_conv3x3_f32 forward and diner_deform_conv3x3_grad_f32 in the backward pass, with no gathered
+    tensors kept for it; conv_offset_mask, the BatchNorms and the plain convolutions stay torch operations, and any input outside the
+    kernels' limits takes deform_conv2d_torch silently.  The kernel route of eval mode does not look at the switch."""
 
     def __init__(self, base_channels=8):
         super().__init__()
@@ -997,6 +1132,16 @@ class DeviceFeatureNet(nn.Module):
         self.out3 = head(_Conv2dBnReLU(f, f, 3, 1, 1), c)
         self.out_channels = [4 * c, 2 * c, c]
         self._packed, self._packed_key = None, None
+
+    @property
+    def deform_kernels(self):
+        return all(m.deform_kernels for m in self.modules() if isinstance(m, _DCN))
+
+    @deform_kernels.setter
+    def deform_kernels(self, value):
+        for m in self.modules():
+            if isinstance(m, _DCN):
+                m.deform_kernels = bool(value)
 
     @classmethod
     def from_module(cls, feature):

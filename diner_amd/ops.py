@@ -1847,6 +1847,72 @@ def deform_conv3x3(x, offmask, wpack, bias, Cout, relu=False, out=None):
     return y
 
 
+DEFORM_GRAD_MAX_COUT = 64        # the backward pass keeps a tap's Cout x Cin accumulators in registers
+DEFORM_GRAD_MAX_SLABS = 1024
+
+
+def deform_grad_supported(Cin, Cout):
+    """Whether diner_deform_conv3x3_grad_f32 takes these channel counts."""
+    Cin, Cout = int(Cin), int(Cout)
+    return 8 <= Cin <= DEFORM_MAX_CIN and Cin % 8 == 0 and 1 <= Cout <= DEFORM_GRAD_MAX_COUT
+
+
+def deform_grad_slabs(N, H, W, slabs=0):
+    """The number of per-workgroup slabs d_weight and d_bias are added from: a function of the shape alone, or the caller's `slabs`."""
+    tiles = int(N) * (-(-int(H) * int(W) // 64))
+    return min(tiles, min(int(slabs), DEFORM_GRAD_MAX_SLABS) if slabs else 128)
+
+
+def _check_deform_conv3x3_grad_args(x, offmask, weight, dy, want=(True, True, True, True), slabs=0):
+    """The argument checks of deform_conv3x3_grad that need no device -> (N, H, W, Cin, Cout)."""
+    N, H, W, Cin = _check_nhwc("deform_conv3x3_grad", "x", x)
+    if Cin < 8 or Cin > DEFORM_MAX_CIN or Cin % 8:
+        raise ValueError(f"diner_amd: deform_conv3x3_grad expects Cin a multiple of 8 in [8, {DEFORM_MAX_CIN}], got {Cin}")
+    if (not torch.is_tensor(weight) or weight.dtype != torch.float32 or weight.dim() != 4 or tuple(weight.shape[1:]) != (Cin, 3, 3)
+            or not weight.is_contiguous()):
+        raise ValueError(f"diner_amd: deform_conv3x3_grad expects weight float32 contiguous (Cout, {Cin}, 3, 3), got "
+                         f"{tuple(weight.shape) if torch.is_tensor(weight) else type(weight).__name__}")
+    Cout = int(weight.shape[0])
+    if Cout < 1 or Cout > DEFORM_GRAD_MAX_COUT:
+        raise ValueError(f"diner_amd: deform_conv3x3_grad expects Cout in [1, {DEFORM_GRAD_MAX_COUT}], got {Cout}")
+    if max(H, W) > 1 << 14 or N > 65535 or N * (-(-H * W // 64)) >= 1 << 30:
+        raise ValueError(f"diner_amd: deform_conv3x3_grad expects H, W <= 2^14, at most 65535 images and fewer than 2^30 tiles, got "
+                         f"{N} x {H} x {W}")
+    _check_nhwc("deform_conv3x3_grad", "offmask", offmask, (N, H, W, 3 * DEFORM_TAPS))
+    _check_nhwc("deform_conv3x3_grad", "dy", dy, (N, H, W, Cout))
+    if len(tuple(want)) != 4:
+        raise ValueError("diner_amd: deform_conv3x3_grad expects want = (d_x, d_offmask, d_weight, d_bias) as four flags")
+    if isinstance(slabs, bool) or not isinstance(slabs, int) or slabs < 0:
+        raise ValueError(f"diner_amd: deform_conv3x3_grad expects slabs an int >= 0 (0: the default), got {slabs!r}")
+    return N, H, W, Cin, Cout
+
+
+def deform_conv3x3_grad(x, offmask, weight, dy, want=(True, True, True, True), slabs=0):
+    """The backward pass of deform_conv3x3 with relu=False (diner_deform_conv3x3_grad_f32): x (N,H,W,Cin), the raw offmask (N,H,W,27) and
+    the upstream gradient dy (N,H,W,Cout) channels-last, weight the plain (Cout,Cin,3,3) tensor -> (d_x (N,H,W,Cin), d_offmask (N,H,W,27)
+    in the forward's channel order with the sigmoid's derivative included, d_weight (Cout,Cin,3,3), d_bias (Cout,)); an output whose `want`
+    flag is False is None and its work is skipped.  d_offmask, d_weight and d_bias have the same bits on every run; d_x is added with
+    float atomics and is NOT bit-reproducible.  slabs: 0, or the number of partial sums d_weight and d_bias are added from."""
+    N, H, W, Cin, Cout = _check_deform_conv3x3_grad_args(x, offmask, weight, dy, want, slabs)
+    _require_hip(x, offmask, weight, dy)
+    wx, wo, ww, wb = (bool(f) for f in want)
+    with torch.cuda.device(x.device):
+        new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=x.device)
+        d_x = new(N, H, W, Cin) if wx else None
+        d_om = new(N, H, W, 3 * DEFORM_TAPS) if wo else None
+        d_w = new(Cout, Cin, 3, 3) if ww else None
+        d_b = new(Cout) if wb else None
+        work = None
+        if ww or wb:
+            floats = int(lib.diner_deform_conv3x3_grad_workspace_floats(N, H, W, Cin, Cout, int(slabs)))
+            if floats != deform_grad_slabs(N, H, W, slabs) * (DEFORM_TAPS * Cout * Cin + Cout):
+                raise RuntimeError("diner_amd: deform_conv3x3_grad: the library and the host disagree on the workspace")
+            work = new(floats)
+        _lib.check(lib.diner_deform_conv3x3_grad_f32(_ptr(x), _ptr(offmask), _ptr(weight), _ptr(dy), _ptr(d_x), _ptr(d_om), _ptr(d_w),
+                                                     _ptr(d_b), _ptr(work), N, H, W, Cin, Cout, int(slabs), _stream()))
+    return d_x, d_om, d_w, d_b
+
+
 def pack_conv5x5(weight):
     """A torch Conv2d weight (Cout,Cin,5,5) in the layout diner_conv5x5_s2_f32 reads: [ceil(Cin / 8)][ky 5 + kx][8][Cout rounded up to 64]."""
     return _pack_conv2d("pack_conv5x5", weight, (5,))

@@ -1077,6 +1077,30 @@ int diner_conv1x1_f32(const float* x, const float* wpack, const float* bias, flo
 int diner_fpn_lateral_f32(const float* top, const float* lateral, const float* w, const float* bias, float* y, int N, int H, int W, int Ctop,
                           int Clat, void* stream);
 
+/* ---- the deformable convolution's gradients (csrc/deform_grad.hip) -----------------------------------------------------------------------
+ * New symbols without an ABI bump.  diner_deform_conv3x3_grad_f32: the backward pass of diner_deform_conv3x3_f32 with relu = 0, from the
+ * upstream gradient dy (N,H,W,Cout), channels-last fp32 like x (N,H,W,Cin) and the raw offmask (N,H,W,27); weight is the plain
+ * (Cout,Cin,3,3) tensor, not the forward's packed one.  With m = sigmoid(offmask[18 + k]), S the forward's sample, v00 .. v11 its corner
+ * values (0 where a corner is not valid) and G[p,k,c] = sum_o dy[p,o] w[o,c,k]:
+ *   d_offmask[p,18 + k] = m (1 - m) sum_c G S                                     (the sigmoid's derivative included)
+ *   d_offmask[p,2 k]    = m sum_c G (-hx v00 - lx v01 + hx v10 + lx v11)          d_offmask[p,2 k + 1] = m sum_c G (-hy v00 + hy v01 - ly v10 + ly v11)
+ *   d_x[corner i, c]   += m wt_i G[p,k,c]     d_weight[o,c,k] = sum_p dy[p,o] m S     d_bias[o] = sum_p dy[p,o]
+ * torchvision's rule, and autograd's through the floor: at an exactly integer coordinate the right-sided difference.  A tap whose offset
+ * puts it outside (NaN, +-inf, +-1e30 included) reads nothing and every gradient of it is exactly 0.
+ *   Outputs: d_x (N,H,W,Cin), d_offmask (N,H,W,27), d_weight (Cout,Cin,3,3), d_bias (Cout); each may be NULL ("not wanted": its work is
+ *   skipped, the others' bits do not change).  d_offmask, d_weight and d_bias are written once per element in an order the shape (and
+ *   `slabs`) alone fixes: the same bits on every run, d_offmask also at any batch position.  d_x is zeroed with hipMemsetAsync and then
+ *   added to with native float atomics, whose order is free: d_x IS NOT BIT-REPRODUCIBLE from run to run.
+ *   workspace: diner_deform_conv3x3_grad_workspace_floats(N, H, W, Cin, Cout, slabs) floats (0 for arguments the function refuses), needed
+ *   for d_weight or d_bias: S slabs of per-workgroup sums, which a finish launch adds in slab order in double, rounded once.  slabs: 0
+ *   for the default S = min(tiles, 128) with tiles = N ceil(H W / 64); a positive value forces S = min(slabs, tiles, 1024).
+ *   Limits, refused with DINER_E_INVALID before any device work: Cin a multiple of 8 in [8, DINER_DEFORM_MAX_CIN]; Cout in
+ *   [1, DINER_DEFORM_MAX_CIN]; H, W <= 2^14; N <= 65535; fewer than 2^30 tiles; x 16-byte aligned; d_x and d_offmask none of the inputs. */
+size_t diner_deform_conv3x3_grad_workspace_floats(int N, int H, int W, int Cin, int Cout, int slabs);
+int diner_deform_conv3x3_grad_f32(const float* x, const float* offmask, const float* weight, const float* dy, float* d_x, float* d_offmask,
+                                  float* d_weight, float* d_bias, float* workspace, int N, int H, int W, int Cin, int Cout, int slabs,
+                                  void* stream);
+
 /* ---- the depth estimator's fine-tuning objective and depth scores ------------------------------------------------------------------------
  * New symbols without an ABI bump (mvsloss.hip): TransMVSNet's entropy_loss / focal_loss_bld / trans_mvsnet_loss (models/module.py:490-587)
  * with the gradient, and Thres_metrics / AbsDepthError_metrics (utils.py:240-274).  No allocation, enqueue-only, no host read-back, no
