@@ -13,7 +13,7 @@ ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(ROOT, "build", "obj")
 LIB = os.path.join(HERE, "libdiner_hip.so")
-SOURCES = ["api.cpp", "sampler.hip", "composite.hip", "stage_ops.hip", "prep.hip", "train.hip", "train_512.hip", "mlp.hip", "mlp_h3n.hip", "generic.hip", "metrics.hip", "objective.hip", "cull.hip", "geometry.hip", "surface.hip", "raycast.hip", "cloud.hip", "conv2d.hip", "perceptual.hip", "optim.hip", "encoder.hip", "mvs.hip", "costreg.hip", "fmt.hip", "deform.hip", "deform_grad.hip", "mvsloss.hip"]
+SOURCES = ["api.cpp", "sampler.hip", "composite.hip", "stage_ops.hip", "prep.hip", "train.hip", "train_512.hip", "mlp.hip", "mlp_h3n.hip", "generic.hip", "metrics.hip", "objective.hip", "cull.hip", "geometry.hip", "surface.hip", "raycast.hip", "cloud.hip", "conv2d.hip", "perceptual.hip", "optim.hip", "encoder.hip", "mvs.hip", "costreg.hip", "fmt.hip", "deform.hip", "deform_grad.hip", "fmt_grad.hip", "mvsloss.hip"]
 # -ffp-contract=off: every fp32 op of the geometry path rounds where the reference's torch ops round;
 # fused multiply-adds are written explicitly (fmaf / MFMA) where they are wanted.
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-Wno-unused-value",
@@ -34,6 +34,7 @@ EXTRA_FLAGS = {
     "fmt.hip": ["-Rpass-analysis=kernel-resource-usage"],       # k_fmt_kv and k_fmt_layer must stay free of scratch
     "deform.hip": ["-Rpass-analysis=kernel-resource-usage"],    # k_deform_conv3x3<1 | 2, 1 | 2 | 4> and k_fpn_lateral likewise
     "deform_grad.hip": ["-Rpass-analysis=kernel-resource-usage"],   # k_deform_grad_data / _weight<1 | 2 | 4> must stay free of scratch
+    "fmt_grad.hip": ["-Rpass-analysis=kernel-resource-usage"],  # k_fmt_grad_query and k_fmt_grad_source must stay free of scratch
     "mvsloss.hip": ["-Rpass-analysis=kernel-resource-usage"],   # every kernel of the estimator's loss must stay free of scratch
 }
 

@@ -305,7 +305,8 @@ class DeviceTransMVSNet(nn.Module):
     on batch statistics.  depth_interval: the base interval (max - min) / D0 as a host number; None reads it back from depth_values as the
     reference does (one synchronisation).  grad_method is kept for the reference's signature: the depth a stage hands on is a gather of
     hypotheses at an argmax, which carries no gradient to any parameter either way, and it is handed on detached.
-    fused_readout, match_kernels: DeviceDepthNet's switches (see there); deform_kernels: DeviceFeatureNet's (see there)."""
+    fused_readout, match_kernels: DeviceDepthNet's switches (see there); deform_kernels: DeviceFeatureNet's (see there); fmt_kernels:
+    DeviceFMT's (see there)."""
 
     def __init__(self, ndepths=(48, 32, 8), depth_interals_ratio=(4, 2, 1), share_cr=False, cr_base_chs=(8, 8, 8), grad_method="detach"):
         super().__init__()
@@ -347,6 +348,14 @@ class DeviceTransMVSNet(nn.Module):
     def deform_kernels(self, value):
         self.feature.deform_kernels = bool(value)
 
+    @property
+    def fmt_kernels(self):
+        return self.FMT_with_pathway.fmt_kernels
+
+    @fmt_kernels.setter
+    def fmt_kernels(self, value):
+        self.FMT_with_pathway.fmt_kernels = bool(value)
+
     @classmethod
     def from_module(cls, model):
         """A reference TransMVSNet (or a DeviceTransMVSNet) -> a DeviceTransMVSNet with its state, device and mode."""
@@ -376,7 +385,7 @@ def warmup_multistep_lr(step, base_lr, milestones, gamma, warmup_factor=1.0 / 3,
 
 
 def fit_estimator(model, batches, *, steps, optimizer=None, lr=1e-3, weight_decay=1e-4, milestones=(), gamma=0.5, dlossw=(1, 1, 1),
-                  start_step=0, log_every=50, on_log=None, match_kernels=False, deform_kernels=False):
+                  start_step=0, log_every=50, on_log=None, match_kernels=False, deform_kernels=False, fmt_kernels=False):
     """`steps` fine-tuning steps k = start_step, ...: model.train(); outputs = model(imgs, proj_matrices, depth_values) with fused_readout;
     focal_loss_bld(outputs, depth, mask, depth_interval, dlossw=dlossw); total.backward(); optimizer.step at warmup_multistep_lr(k, lr,
     milestones, gamma).  batches: any iterable of the reference's sample dicts {"imgs", "proj_matrices", "depth_values", "depth": {"stage
@@ -388,7 +397,8 @@ def fit_estimator(model, batches, *, steps, optimizer=None, lr=1e-3, weight_deca
     the end): the loop's only wait.  on_log(rows) receives the rows just read.  match_kernels=True sets the model's switch of that name for
     the loop (the cost volume and its gradients at the feature maps on the kernels of csrc/mvs.hip) and restores it afterwards;
     deform_kernels=True does the same with that switch (FeatureNet's deformable convolutions and their gradients on the kernels of
-    csrc/deform.hip and csrc/deform_grad.hip).  The two compose with each other and with fused_readout.
+    csrc/deform.hip and csrc/deform_grad.hip); fmt_kernels=True with that one (the feature transformer's layers and their gradients on the
+    kernels of csrc/fmt.hip and csrc/fmt_grad.hip).  The three compose with each other and with fused_readout.
     -> (history, optimizer); history: one dict {step, total, depth_loss, epe, less1, less3} per step."""
     params = [p for p in model.parameters() if p.requires_grad]
     dev = params[0].device
@@ -415,6 +425,9 @@ def fit_estimator(model, batches, *, steps, optimizer=None, lr=1e-3, weight_deca
     had_deform = getattr(model, "deform_kernels", None) if deform_kernels else None
     if had_deform is not None:
         model.deform_kernels = True
+    had_fmt = getattr(model, "fmt_kernels", None) if fmt_kernels else None
+    if had_fmt is not None:
+        model.fmt_kernels = True
     optimizer.zero_grad()
     intervals = {}
 
@@ -462,6 +475,8 @@ def fit_estimator(model, batches, *, steps, optimizer=None, lr=1e-3, weight_deca
             model.match_kernels = had_match
         if had_deform is not None:
             model.deform_kernels = had_deform
+        if had_fmt is not None:
+            model.fmt_kernels = had_fmt
     return history, optimizer
 
 

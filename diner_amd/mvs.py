@@ -656,6 +656,153 @@ def _maps(tokens, H):
     return tokens.reshape(N, H, L // H, C).permute(0, 3, 1, 2)
 
 
+# the short names of one encoder layer's sixteen tensors in ops.FMT_LAYER_KEYS' order
+FMT_LAYER_SHORT = ("wq", "wk", "wv", "wo", "w1", "w2", "bq", "bk", "bv", "bo", "g1", "be1", "b1", "b2", "g2", "be2")
+
+
+def _layer_parameters(layer):
+    """An _EncoderLayer's sixteen parameters in ops.FMT_LAYER_KEYS' order."""
+    a = layer.attention
+    return (a.query_projection.weight, a.key_projection.weight, a.value_projection.weight, a.out_projection.weight, layer.linear1.weight,
+            layer.linear2.weight, a.query_projection.bias, a.key_projection.bias, a.value_projection.bias, a.out_projection.bias,
+            layer.norm1.weight, layer.norm1.bias, layer.linear1.bias, layer.linear2.bias, layer.norm2.weight, layer.norm2.bias)
+
+
+def fmt_layer_grad_torch(x, source, weights, dy):
+    """The gradients of one encoder layer y = _EncoderLayer(x, source) under the upstream dy, in closed form and in torch operations, any
+    floating dtype: the host restatement of diner_fmt_layer_grad_f32.  x (N,L,32), source (R,S,32) with image n reading source n mod R,
+    weights a dict under FMT_LAYER_SHORT's names (torch's (out, in) matrices), dy (N,L,32) -> (d_x, d_source, {name: gradient}).  When
+    `source is x` (a self layer) both paths are added into d_x and d_source is None.  relu'(0) = 0; elu'(v) = 1 for v > 0, else exp(v);
+    LayerNorm with the biased variance and eps 1e-5."""
+    if x.dim() != 3 or source.dim() != 3 or dy.shape != x.shape or x.shape[0] % source.shape[0] or x.shape[2] != source.shape[2]:
+        raise ValueError(f"diner_amd: fmt_layer_grad_torch: shapes {tuple(x.shape)}, {tuple(source.shape)}, {tuple(dy.shape)} do not belong together")
+    self_layer = source is x
+    w = {k: v.detach() for k, v in weights.items()}
+    x, source, dy = x.detach(), source.detach(), dy.detach()
+    N, L, C = (int(n) for n in x.shape)
+    R, S = int(source.shape[0]), int(source.shape[1])
+    H = 8
+    rows = torch.arange(N, device=x.device) % R
+    slope = lambda v: torch.where(v > 0, torch.ones_like(v), torch.exp(v))
+    kp = source @ w["wk"].T + w["bk"]
+    K = (F.elu(kp) + 1).view(R, S, H, -1)
+    V = (source @ w["wv"].T + w["bv"]).view(R, S, H, -1)
+    kv, ksum = torch.einsum("rshd,rshm->rhmd", K, V)[rows], K.sum(1)[rows]
+    qp = x @ w["wq"].T + w["bq"]
+    Q = (F.elu(qp) + 1).view(N, L, H, -1)
+    den = torch.einsum("nlhd,nhd->nlh", Q, ksum) + 1e-6
+    A = torch.einsum("nlhd,nhmd->nlhm", Q, kv) / den.unsqueeze(-1)
+
+    def norm(v):
+        mean = v.mean(-1, keepdim=True)
+        rstd = 1 / torch.sqrt(((v - mean) ** 2).mean(-1, keepdim=True) + 1e-5)
+        return (v - mean) * rstd, rstd
+
+    def norm_back(g, hat, rstd, gamma):
+        gh = g * gamma
+        return rstd * (gh - gh.mean(-1, keepdim=True) - hat * (gh * hat).mean(-1, keepdim=True))
+
+    hat1, rstd1 = norm(x + A.reshape(N, L, C) @ w["wo"].T + w["bo"])
+    x1 = hat1 * w["g1"] + w["be1"]
+    hp = x1 @ w["w1"].T + w["b1"]
+    hr = torch.relu(hp)
+    hat2, rstd2 = norm(x1 + hr @ w["w2"].T + w["b2"])
+    g = {"g2": (dy * hat2).sum((0, 1)), "be2": dy.sum((0, 1))}
+    dv2 = norm_back(dy, hat2, rstd2, w["g2"])
+    g["w2"], g["b2"] = torch.einsum("nlj,nlk->jk", dv2, hr), dv2.sum((0, 1))
+    dh = (dv2 @ w["w2"]) * (hp > 0).to(x.dtype)
+    g["w1"], g["b1"] = torch.einsum("nlk,nli->ki", dh, x1), dh.sum((0, 1))
+    dx1 = dv2 + dh @ w["w1"]
+    g["g1"], g["be1"] = (dx1 * hat1).sum((0, 1)), dx1.sum((0, 1))
+    dv1 = norm_back(dx1, hat1, rstd1, w["g1"])
+    g["wo"], g["bo"] = torch.einsum("nlj,nlm->jm", dv1, A.reshape(N, L, C)), dv1.sum((0, 1))
+    dA = (dv1 @ w["wo"]).view(N, L, H, -1)
+    dnum = dA / den.unsqueeze(-1)
+    dden = -(dA * A).sum(-1) / den
+    dqp = ((torch.einsum("nlhm,nhmd->nlhd", dnum, kv) + dden.unsqueeze(-1) * ksum.unsqueeze(1)) * slope(qp).view(N, L, H, -1)).reshape(N, L, C)
+    g["wq"], g["bq"] = torch.einsum("nld,nli->di", dqp, x), dqp.sum((0, 1))
+    d_x = dv1 + dqp @ w["wq"]
+    d_kv = torch.einsum("nlhm,nlhd->nhmd", dnum, Q).view(N // R, R, H, 4, 4).sum(0)          # d_state: the images that share a row
+    d_ksum = torch.einsum("nlh,nlhd->nhd", dden, Q).view(N // R, R, H, 4).sum(0)
+    dkp = ((torch.einsum("rhmd,rshm->rshd", d_kv, V) + d_ksum.unsqueeze(1)) * slope(kp).view(R, S, H, -1)).reshape(R, S, C)
+    dV = torch.einsum("rhmd,rshd->rshm", d_kv, K).reshape(R, S, C)
+    g["wk"], g["bk"] = torch.einsum("rsd,rsi->di", dkp, source), dkp.sum((0, 1))
+    g["wv"], g["bv"] = torch.einsum("rsm,rsi->mi", dV, source), dV.sum((0, 1))
+    d_source = dkp @ w["wk"] + dV @ w["wv"]
+    if self_layer:
+        return d_x + d_source, None, g
+    return d_x, d_source, g
+
+
+def _layer_torch(layer, x, source):
+    """_EncoderLayer.forward with fmt_layer's row rule: image n of x reads source n mod R."""
+    if source is not x and source.shape[0] != x.shape[0]:
+        source = source.repeat(x.shape[0] // source.shape[0], 1, 1)
+    return layer(x, source)
+
+
+def fmt_layer_gate(x, source, layer):
+    """Whether fmt_layer runs the kernels: float32 HIP tokens and parameters at d_model 32 with 8 heads, inside diner_fmt_layer_grad_f32's
+    limits."""
+    params = _layer_parameters(layer)
+    if not all(torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 for t in (x, source) + params):
+        return False
+    if layer.attention.n_heads != 8 or tuple(layer.linear1.weight.shape) != (64, 32) or x.dim() != 3 or source.dim() != 3:
+        return False
+    N, L, R, S = int(x.shape[0]), int(x.shape[1]), int(source.shape[0]), int(source.shape[1])
+    top = FMT_PE_SHAPE[0] * FMT_PE_SHAPE[1]
+    return x.shape[2] == 32 and source.shape[2] == 32 and 1 <= R <= N <= 65535 and N % R == 0 and 1 <= L <= top and 1 <= S <= top
+
+
+class _FmtLayer(torch.autograd.Function):
+    """diner_fmt_kv_f32 + diner_fmt_layer_f32 / diner_fmt_layer_grad_f32.  Saves x, the source, the layer pack and the 160-float state and
+    nothing else.  source None is the self layer (the source is x).  The backward pass is one entry on detached tensors and computes only
+    what is needed; asked for a graph of its own (a second derivative) it differentiates _EncoderLayer.forward on the saved inputs."""
+
+    @staticmethod
+    def forward(ctx, x, source, layer, pack, *params):
+        ops = _ops()
+        xs = x.detach().contiguous()
+        src = xs if source is None else source.detach().contiguous()
+        if pack is None:
+            pack = ops.pack_fmt_layer(dict(zip(ops.FMT_LAYER_KEYS, (p.detach() for p in params))))
+        state = ops.fmt_kv(src, pack)
+        y = ops.fmt_layer(xs, pack, state)
+        ctx.save_for_backward(x, source, pack, state)
+        ctx.layer = layer
+        return y
+
+    @staticmethod
+    def backward(ctx, grad):
+        x, source, pack, state = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        params = _layer_parameters(ctx.layer)
+        if torch.is_grad_enabled():                 # create_graph=True: the torch layer carries the second derivative
+            with torch.enable_grad():
+                inputs = [t for t, n in zip((x, source, None, None) + params, need) if n]
+                got = iter(torch.autograd.grad(_layer_torch(ctx.layer, x, x if source is None else source), inputs, grad, create_graph=True))
+            return tuple(next(got) if n else None for n in need)
+        ops = _ops()
+        xs = x.detach().contiguous()
+        src = xs if source is None else source.detach().contiguous()
+        d_x, d_src, d_par = ops.fmt_layer_grad(xs, src, pack, state, grad.detach().to(torch.float32).contiguous(),
+                                               want=(need[0], need[1], any(need[4:])))
+        d_params = ops.unpack_fmt_layer_grad(d_par) if d_par is not None else [None] * 16
+        return (d_x, d_src, None, None) + tuple(g if n else None for g, n in zip(d_params, need[4:]))
+
+
+def fmt_layer(x, source, layer, pack=None):
+    """One encoder layer of the feature transformer, differentiable: x (N,L,32), source (R,S,32) with N a multiple of R (image n reads
+    source n mod R), layer an _EncoderLayer -> (N,L,32).  On float32 HIP tensors and parameters it is one once-differentiable autograd
+    Function over x, source and the sixteen parameters: ops.fmt_kv + ops.fmt_layer forward (the bits of DeviceFMT.encode_tokens),
+    diner_fmt_layer_grad_f32 in the backward pass, which has no atomics and gives the same bits on every run.  `source is x` is the self
+    layer: one gradient for x.  pack: the layer's ops.pack_fmt_layer when the caller keeps it.  Anything else (CPU tensors, other dtypes,
+    other sizes, a second derivative) runs _EncoderLayer.forward."""
+    if not fmt_layer_gate(x, source, layer):
+        return _layer_torch(layer, x, source)
+    return _FmtLayer.apply(x, None if source is x else source, layer, pack, *_layer_parameters(layer))
+
+
 class DeviceFMT(nn.Module):
     """A replacement for the reference's FMT (models/FMT.py:114-174): the same state-dict keys (layers.{i}.attention.*_projection.*,
     linear1/2, norm1/2; the positional encoding `pe` is a non-persistent buffer), the same forward(ref_feature, src_feature, feat).
@@ -673,6 +820,7 @@ class DeviceFMT(nn.Module):
                 nn.init.xavier_uniform_(p)
         self.register_buffer("pe", sine_position_encoding(self.d_model).unsqueeze(0), persistent=False)
         self._packed, self._packed_key = None, None
+        self.fmt_kernels = False
 
     @classmethod
     def from_module(cls, fmt):
@@ -701,6 +849,14 @@ class DeviceFMT(nn.Module):
         reference's layer schedule at d_model 32 with 8 heads."""
         return (x.is_cuda and x.dtype == torch.float32 and self.layers[0].linear1.weight.dtype == torch.float32 and not self.training
                 and not torch.is_grad_enabled() and tuple(self.layer_names) == FMT_LAYER_NAMES and self.d_model == 32 and self.nhead == 8
+                and x.dim() == 4 and x.shape[1] == 32 and 1 <= x.shape[2] <= FMT_PE_SHAPE[0] and 1 <= x.shape[3] <= FMT_PE_SHAPE[1])
+
+    def trains_on_kernels(self, x):
+        """The training gate: fmt_kernels set, gradients enabled, a float32 HIP map (B,32,H,W) with H, W <= 600, float32 parameters and the
+        reference's layer schedule at d_model 32 with 8 heads."""
+        return (self.fmt_kernels and torch.is_grad_enabled() and x.is_cuda and x.dtype == torch.float32
+                and self.layers[0].linear1.weight.dtype == torch.float32 and self.layers[0].linear1.weight.is_cuda
+                and tuple(self.layer_names) == FMT_LAYER_NAMES and self.d_model == 32 and self.nhead == 8
                 and x.dim() == 4 and x.shape[1] == 32 and 1 <= x.shape[2] <= FMT_PE_SHAPE[0] and 1 <= x.shape[3] <= FMT_PE_SHAPE[1])
 
     def pos_encoding(self, x):
@@ -755,6 +911,28 @@ class DeviceFMT(nn.Module):
                 ops.fmt_layer(src, packs[2 * j + 1], cross[j], out=src)          # image n = view B + b reads row n mod B
         return tok
 
+    def encode_train(self, views):
+        """encode_tokens' schedule out of place through fmt_layer, differentiable: views a list of (B,32,H,W), view 0 the reference ->
+        (ref', [source', ...]).  The reference view runs its four self layers; all source views run as one batch of NS B images through
+        the eight layers, cross layer 2 j + 1 reading the reference output j as a (B, S, 32) source, so the sum over the views reaches
+        that output's gradient through d_state."""
+        B, _, H, W = (int(n) for n in views[0].shape)
+        packs = self.packed()
+        ref = _tokens(self.pos_encoding(views[0]))
+        outs = []
+        for j in range(4):
+            ref = fmt_layer(ref, ref, self.layers[2 * j], pack=packs[2 * j])
+            outs.append(ref)
+        if len(views) == 1:
+            return _maps(ref, H), []
+        NS = len(views) - 1
+        src = _tokens(self.pos_encoding(torch.stack(views[1:], 0).view(NS * B, 32, H, W)))
+        for j in range(4):
+            src = fmt_layer(src, src, self.layers[2 * j], pack=packs[2 * j])
+            src = fmt_layer(src, outs[j], self.layers[2 * j + 1], pack=packs[2 * j + 1])      # image n = view B + b reads row n mod B
+        src = src.view(NS, B, H * W, 32)
+        return _maps(ref, H), [_maps(src[v], H) for v in range(NS)]
+
     def encode(self, ref, sources):
         """The device route of one sample batch: ref (B,32,H,W), sources a list of (B,32,H,W) -> (ref', [source', ...]), each (B,32,H,W)
         as a permuted view of channels-last memory.  Outside the gate: forward() per view, as the reference's FMT_with_pathway calls it."""
@@ -764,6 +942,8 @@ class DeviceFMT(nn.Module):
             tok = self.encode_tokens(torch.stack([v.detach() for v in views], 0))
             out = [tok[v].view(B, H, W, 32).permute(0, 3, 1, 2) for v in range(len(views))]
             return out[0], out[1:]
+        if self.trains_on_kernels(ref) and all(v.shape == ref.shape and v.is_cuda and v.dtype == torch.float32 for v in views):
+            return self.encode_train(views)
         refs = self.forward(ref.clone(), feat="ref")
         return refs[-1], [self.forward([r.clone() for r in refs], s.clone(), feat="src") for s in sources]
 
@@ -798,6 +978,14 @@ class DeviceFMTWithPathway(nn.Module):
         new.load_state_dict(module.state_dict())
         new.train(module.training)
         return new
+
+    @property
+    def fmt_kernels(self):
+        return self.FMT.fmt_kernels
+
+    @fmt_kernels.setter
+    def fmt_kernels(self, value):
+        self.FMT.fmt_kernels = bool(value)
 
     def invalidate(self):
         """Forget the packed weights of the pathway and of the FMT: call after writing a parameter through `.data`."""
@@ -848,8 +1036,20 @@ class DeviceFMTWithPathway(nn.Module):
         m3 = ops.fpn_merge(s2, self.dim_reduction_2.weight.detach(), lateral3, out=lateral3)
         return s2, ops.conv3x3(m3, p2, None, 8)
 
+    def forward_train(self, features):
+        """forward_torch with the transformer on DeviceFMT.encode's training route (fmt_kernels); the pathway stays torch, per view."""
+        ref, sources = self.FMT.encode(features[0]["stage1"], [f["stage1"] for f in features[1:]])
+        for f, stage1 in zip(features, [ref] + list(sources)):
+            f["stage1"] = stage1
+            f["stage2"] = self.smooth_1(self._upsample_add(self.dim_reduction_1(f["stage1"]), f["stage2"]))
+            f["stage3"] = self.smooth_2(self._upsample_add(self.dim_reduction_2(f["stage2"]), f["stage3"]))
+        return features
+
     def forward(self, features):
         if not self.uses_kernels(features):
+            if features and self.FMT.trains_on_kernels(features[0]["stage1"]) and all(
+                    f["stage1"].shape == features[0]["stage1"].shape and f["stage1"].is_cuda and f["stage1"].dtype == torch.float32 for f in features):
+                return self.forward_train(features)
             return self.forward_torch(features)
         NV = len(features)
         B, _, H, W = (int(n) for n in features[0]["stage1"].shape)

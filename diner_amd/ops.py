@@ -1744,6 +1744,79 @@ def fmt_layer(x, pack, state, out=None):
     return y
 
 
+FMT_GRAD_TOKENS, FMT_GRAD_QUERY_SLAB_FLOATS, FMT_GRAD_SOURCE_SLAB_FLOATS, FMT_GRAD_MAX_SLABS = 128, 6432, 2112, 1024      # DINER_FMT_GRAD_*
+
+
+def fmt_grad_slabs(N, L, R, S, slabs=0):
+    """(query side, source side): the per-workgroup slabs the parameter gradients are added from -- a function of the shape alone, or the
+    caller's `slabs`; a tile is FMT_GRAD_TOKENS tokens of one image."""
+    want = int(slabs) if slabs else 128
+    return min(int(N) * -(-int(L) // FMT_GRAD_TOKENS), want), min(int(R) * -(-int(S) // FMT_GRAD_TOKENS), want)
+
+
+def fmt_grad_workspace_floats(N, L, R, S, slabs=0):
+    """diner_fmt_layer_grad_workspace_floats on the host: the tiles' shares of d_state as doubles, d_state, then per side the slabs and
+    their carries."""
+    sq, ss = fmt_grad_slabs(N, L, R, S, slabs)
+    return (2 * int(N) * -(-int(L) // FMT_GRAD_TOKENS) * FMT_STATE_FLOATS + int(R) * FMT_STATE_FLOATS
+            + 2 * (sq * FMT_GRAD_QUERY_SLAB_FLOATS + ss * FMT_GRAD_SOURCE_SLAB_FLOATS))
+
+
+def _check_fmt_layer_grad_args(x, source, pack, state, dy, want=(True, True, True), slabs=0):
+    """The argument checks of fmt_layer_grad that need no device -> (N, L, R, S, self layer)."""
+    N, L = _check_tokens("fmt_layer_grad", "x", x)
+    R, S = _check_tokens("fmt_layer_grad", "source", source)
+    _check_tokens("fmt_layer_grad", "dy", dy, (N, L, FMT_D_MODEL))
+    _check_fmt_pack("fmt_layer_grad", pack)
+    if N % R:
+        raise ValueError(f"diner_amd: fmt_layer_grad expects the source's {R} images to divide x's {N} (image n reads row n mod R)")
+    if not torch.is_tensor(state) or state.dtype != torch.float32 or tuple(state.shape) != (R, FMT_STATE_FLOATS) or not state.is_contiguous():
+        raise ValueError(f"diner_amd: fmt_layer_grad expects state float32 ({R},{FMT_STATE_FLOATS}), contiguous (fmt_kv of the source), got "
+                         f"{tuple(state.shape) if torch.is_tensor(state) else type(state).__name__}")
+    if len(tuple(want)) != 3:
+        raise ValueError("diner_amd: fmt_layer_grad expects want = (d_x, d_source, parameters) as three flags")
+    if isinstance(slabs, bool) or not isinstance(slabs, int) or not 0 <= slabs <= FMT_GRAD_MAX_SLABS:
+        raise ValueError(f"diner_amd: fmt_layer_grad expects slabs an int in [0, {FMT_GRAD_MAX_SLABS}] (0: the default), got {slabs!r}")
+    return N, L, R, S, source is x
+
+
+def fmt_layer_grad(x, source, pack, state, dy, want=(True, True, True), slabs=0):
+    """The backward pass of fmt_layer(x, pack, fmt_kv(source, pack)) (diner_fmt_layer_grad_f32): x (N,L,32), source (R,S,32) with R a
+    divisor of N, state (R,160) the forward's, dy (N,L,32) -> (d_x (N,L,32), d_source (R,S,32), d_params (8544,) in the pack's order with
+    the matrices as torch keeps them, (out, in)); an output whose `want` flag is False is None and its work is skipped.  When `source is
+    x` it is the self layer: the two paths add into d_x and d_source is None.  No atomics: the same bits on every run.  slabs: 0, or the
+    number of partial sums the parameter gradients are added from."""
+    N, L, R, S, self_layer = _check_fmt_layer_grad_args(x, source, pack, state, dy, want, slabs)
+    _require_hip(x, source, pack, state, dy)
+    wx, ws, wp = (bool(f) for f in want)
+    if self_layer:
+        wx, ws = wx or ws, False
+    with torch.cuda.device(x.device):
+        new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=x.device)
+        d_x = new(N, L, FMT_D_MODEL) if wx else None
+        d_src = new(R, S, FMT_D_MODEL) if ws else None
+        d_par = new(FMT_PACK_FLOATS) if wp else None
+        work = None
+        if ws or wp or (self_layer and wx):
+            floats = int(lib.diner_fmt_layer_grad_workspace_floats(N, L, R, S, int(slabs)))
+            if floats != fmt_grad_workspace_floats(N, L, R, S, slabs):
+                raise RuntimeError("diner_amd: fmt_layer_grad: the library and the host disagree on the workspace")
+            work = new(floats)
+        _lib.check(lib.diner_fmt_layer_grad_f32(_ptr(x), _ptr(source), _ptr(pack), _ptr(state), _ptr(dy), N, L, R, S, _ptr(d_x), _ptr(d_src),
+                                                _ptr(d_par), _ptr(work), int(self_layer), int(slabs), _stream()))
+    return d_x, d_src, d_par
+
+
+def unpack_fmt_layer_grad(d_params):
+    """d_params (8544,) of fmt_layer_grad -> the sixteen gradients in FMT_LAYER_KEYS' order, as views in the parameters' own shapes."""
+    out, at = [], 0
+    for shape in _FMT_LAYER_SHAPES:
+        n = int(np.prod(shape))
+        out.append(d_params[at:at + n].view(shape))
+        at += n
+    return out
+
+
 def _check_fpn_merge_args(top, weight, lateral, out=None):
     """-> (N, H, W, Ctop, Clat)."""
     N, H, W, Ctop = _check_nhwc("fpn_merge", "top", top)

@@ -1101,6 +1101,37 @@ int diner_deform_conv3x3_grad_f32(const float* x, const float* offmask, const fl
                                   float* d_weight, float* d_bias, float* workspace, int N, int H, int W, int Cin, int Cout, int slabs,
                                   void* stream);
 
+/* ---- the feature transformer's gradients (csrc/fmt_grad.hip) ----------------------------------------------------------------------------
+ * New symbols without an ABI bump.  diner_fmt_layer_grad_f32: the backward pass of one encoder layer, diner_fmt_kv_f32 on `source`
+ * (R,S,32) followed by diner_fmt_layer_f32 on x (N,L,32) with state_rows = R, from the upstream gradient dy (N,L,32).  pack and state
+ * are the forward's; nothing else is saved from the forward, the kernels compute it again with the forward's own fmaf chains.  With
+ * Q = elu(x Wq^T + bq) + 1, den_h = Q_h . Ksum_h + 1e-6, A = (Q KV) / den and dA the gradient at A:
+ *   d_state[r]: dKV[h][m][d] = sum dA[h][m] Q[h][d] / den_h, dKsum[h][d] = sum -(sum_m dA[h][m] A[h][m]) Q[h][d] / den_h over the tokens of
+ *     every image n with n mod R = r; products and sums in double, in (image, tile) order, rounded once.  It stays in the workspace.
+ *   d_source: dK = dKV V + dKsum, dV = dKV^T K, dkp = dK elu'(kp), d_source = dkp Wk + dV Wv.
+ *   d_x: through LN2, the feed-forward (relu'(0) = 0), LN1, the out projection, the query side and both residuals.
+ *   d_params, DINER_FMT_PACK_FLOATS floats: the sixteen parameter gradients in the pack's order with the matrices as torch keeps them,
+ *     (out, in): Wq Wk Wv Wo W1 W2, then bq bk bv bo g1 be1 b1 b2 g2 be2.
+ *   Each of d_x, d_source, d_params may be NULL ("not wanted": its work is skipped, the others' bits do not change).  accumulate != 0
+ *   is the self layer: source must be x, R = N, S = L, d_source NULL, and d_x receives the sum of both paths.
+ *   A tile is DINER_FMT_GRAD_TOKENS tokens of one image, one thread a token.  A workgroup walks ceil(tiles / slabs) consecutive tiles and
+ *   keeps one slab of parameter sums (DINER_FMT_GRAD_QUERY_SLAB_FLOATS on the query side, DINER_FMT_GRAD_SOURCE_SLAB_FLOATS on the source
+ *   side): a tile's sum is one fmaf chain from 0 in token order, the slab adds its tiles in order as a (sum, carry) pair of floats; a
+ *   finish launch adds the slabs with their carries in slab order in double and rounds once.  slabs: 0 for
+ *   min(tiles, 128) on either side, or a count up to DINER_FMT_GRAD_MAX_SLABS.  No atomics: every output has the same bits on every run,
+ *   and an image's d_x does not depend on its place in the batch.
+ *   workspace: diner_fmt_layer_grad_workspace_floats(N, L, R, S, slabs) floats (0 for arguments the function refuses), 16-byte aligned;
+ *   needed unless only d_x of a cross layer is asked for.
+ *   Limits, refused with DINER_E_INVALID before any device work: N <= 65535; R a divisor of N; L, S in [1, DINER_FMT_MAX_HW^2]; the
+ *   tokens, the pack and the token gradients 16-byte aligned; d_x and d_source none of the inputs. */
+#define DINER_FMT_GRAD_TOKENS 128
+#define DINER_FMT_GRAD_QUERY_SLAB_FLOATS 6432
+#define DINER_FMT_GRAD_SOURCE_SLAB_FLOATS 2112
+#define DINER_FMT_GRAD_MAX_SLABS 1024
+size_t diner_fmt_layer_grad_workspace_floats(int N, int L, int R, int S, int slabs);
+int diner_fmt_layer_grad_f32(const float* x, const float* source, const float* pack, const float* state, const float* dy, int N, int L, int R,
+                             int S, float* d_x, float* d_source, float* d_params, float* workspace, int accumulate, int slabs, void* stream);
+
 /* ---- the depth estimator's fine-tuning objective and depth scores ------------------------------------------------------------------------
  * New symbols without an ABI bump (mvsloss.hip): TransMVSNet's entropy_loss / focal_loss_bld / trans_mvsnet_loss (models/module.py:490-587)
  * with the gradient, and Thres_metrics / AbsDepthError_metrics (utils.py:240-274).  No allocation, enqueue-only, no host read-back, no
